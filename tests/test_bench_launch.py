@@ -64,9 +64,9 @@ def test_self_launch_two_ranks_on_one_gpu():
 @pytest.mark.gpu
 def test_single_gpu_bench_prints_exactly_one_line():
     """The driver's N = 1 invocation shape on a tiny evaluation: stdout carries the JSON line and nothing else (the product's
-    progress prints go to stderr), the run completes one evaluation and the line carries roofline + config."""
+    progress prints go to stderr), the run completes one evaluation and the line carries roofline + config (--full)."""
     rec, err = _run(["--gpus", "1", "--samples", "40", "--batch", "24", "--denoise-steps", "20", "--steps", "20", "--warmup", "2",
-                     "--no-cpu-baseline", "--no-live-traffic"], 900)
+                     "--full", "--no-cpu-baseline", "--no-live-traffic"], 900)
     assert rec["n_gpus"] == 1 and rec["config"]["passes_completed"] == 1 and rec["value"] > 0
     assert "Generate 40, Total 40." in err and "roofline" in rec and rec["config"]["mode"] == "eval"
 
@@ -97,3 +97,42 @@ def test_uneven_strong_split_on_one_gpu(samples, per_rank):
                    "--denoise-steps", "20", "--steps", "20", "--warmup", "2", "--no-cpu-baseline", "--no-live-traffic"], 900)
     assert rec["config"]["samples_total"] == samples and rec["config"]["molecules_per_gpu"] == per_rank[0]
     assert rec["value"] > 0 and rec["config"]["passes_completed"] == 1
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 files only, at most DUMP_LIMIT_BYTES of data, and the same seeded molecule sample every time."""
+    import numpy as np
+    import torch
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200_000)
+    g = torch.Generator().manual_seed(0)
+    per_mol = {"edge_types": torch.randint(0, 4, (500, 29, 29), generator=g), "positions": torch.randn(500, 29, 3, generator=g)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), per_mol, {"loss": torch.tensor([0.5], dtype=torch.float64)})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["edge_types.npy", "loss.npy", "positions.npy", "sample_rows.npy"]
+    arrays = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(a.nbytes for a in arrays.values()) <= 200_000
+    assert arrays["positions.npy"].dtype == np.float32 and arrays["edge_types.npy"].dtype == np.float64
+    rows = arrays["sample_rows.npy"].astype(np.int64)
+    assert np.array_equal(arrays["positions.npy"], per_mol["positions"].numpy()[rows])
+    for f in files:
+        assert np.array_equal(arrays[f], np.load(tmp_path / "b" / f))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_given_steps_and_dumps_outputs(tmp_path):
+    """A plain run times exactly --steps steps and carries none of the --full figures; --dump-outputs writes the evaluation's result
+    when the last step closed it and the sampler state it advanced otherwise."""
+    import numpy as np
+    common = ["--gpus", "1", "--samples", "40", "--batch", "24", "--denoise-steps", "20", "--warmup", "1"]
+    rec, _ = _run([*common, "--steps", "20", "--dump-outputs", str(tmp_path / "whole")], 900)
+    assert rec["steps"] == 20 and rec["ms_per_step"] > 0 and rec["config"]["passes_completed"] == 1
+    assert rec["roofline"] is None and "cpu_baseline" not in rec and "config5" not in rec
+    pos, n_atoms = np.load(tmp_path / "whole" / "positions.npy"), np.load(tmp_path / "whole" / "n_atoms.npy")
+    assert pos.shape == (40, 29, 3) and pos.dtype == np.float32 and np.isfinite(pos).all() and n_atoms.dtype == np.float64
+    rec, _ = _run([*common, "--steps", "3", "--dump-outputs", str(tmp_path / "part")], 900)
+    assert rec["steps"] == 3 and "partial" in rec["metric"]
+    x = np.load(tmp_path / "part" / "x.npy")
+    assert x.dtype == np.float32 and x.shape[0] == np.load(tmp_path / "part" / "slots.npy").shape[0] and np.isfinite(x).all()

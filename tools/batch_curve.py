@@ -22,7 +22,7 @@ def main():
     rows = []
     for m in [int(x) for x in args.mols.split(",")]:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mols", str(m), "--steps", "4", "--warmup", "1",
-               "--no-cpu-baseline", "--mode", "resident", "--no-live-traffic"] + args.extra.split()
+               "--full", "--no-cpu-baseline", "--mode", "resident", "--no-live-traffic"] + args.extra.split()
         out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

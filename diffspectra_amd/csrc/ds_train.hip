@@ -19,7 +19,6 @@ namespace {
 #ifndef DST_SPEC_SLICES
 #define DST_SPEC_SLICES 2   // workgroups per (batch, head) in the SpecFormer attention kernels: each stages K and V of the head once
 #endif
-#define DST_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? DS_OK : DS_ERR_LAUNCH)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -1618,13 +1617,10 @@ int dst_attn_bwd(const dst_layout* L, const float* qkv, const float* te0, const 
   if (!DST_L_OK(L) || !qkv || !te0 || !te1 || ld_te < 256 || !alpha || !dout || !dqkv || !dte0 || !dte1) return DS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)2 * 812 * 16 * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_bwd<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_bwd<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_bwd<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
+  static std::atomic<uint64_t> lds_set[3];
+  if (!dst::allow_dynamic_lds(lds_set[0], &k_attn_bwd<0>, lds) || !dst::allow_dynamic_lds(lds_set[1], &k_attn_bwd<1>, lds) ||
+      !dst::allow_dynamic_lds(lds_set[2], &k_attn_bwd<2>, lds))
+    return DS_ERR_LAUNCH;
   if (scratch && scratch_cap >= (int64_t)2 * L->Pp * 16 && L->Pp > 0) {
     hipLaunchKernelGGL(k_attn_bwd<1>, dim3(L->B), dim3(1024), lds, s, *L, qkv, te0, te1, ld_te, alpha, dout, dqkv, dte0, dte1, (int)te_is_tanh, scratch);
     hipLaunchKernelGGL(k_attn_bwd<2>, dim3(L->B, 4), dim3(1024), lds / 2, s, *L, qkv, te0, te1, ld_te, alpha, dout, dqkv, dte0, dte1, (int)te_is_tanh, scratch);

@@ -21,6 +21,7 @@
 
 #include "../../include/diffspectra_hip.h"
 #include "../../include/diffspectra_train.h"
+#include "ds_train_common.h"
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -28,8 +29,6 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8_t __attribute__((ext_vector_type(8)));
 
 namespace {
-
-#define DST_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? DS_OK : DS_ERR_LAUNCH)
 
 constexpr int DK = 8, DM = 128, ROWLD = 3 * DM;   // head slice, model width, row stride of a q | k | v buffer
 constexpr int KLD = 40;                           // bf16 per LDS row of the concatenated slices: 32 + 8 of padding (80 bytes)
@@ -53,13 +52,9 @@ __device__ __forceinline__ bf16x8_t load8(const float* p, float mul) {          
 }
 // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2): with (molecule, head) = blockIdx the 16 heads of a molecule -
 // which read 32-byte slices of the SAME 128-byte lines of q | k | v - land on eight different L2s.  Remapped, an XCD runs consecutive
-// (molecule, head) pairs, so a line is fetched once per XCD that needs it instead of once per head (profiles/r05_sfa_prologue.txt).
+// (molecule, head) pairs, so a line is fetched once per XCD that needs it instead of once per head.
 __device__ __forceinline__ int xcd_local(int block, int nblocks) {
-#ifdef SFA_NO_XCD_MAP
-  return block;
-#else
   return (nblocks & 7) == 0 ? (block & 7) * (nblocks >> 3) + (block >> 3) : block;
-#endif
 }
 // x as a sum of two bf16 (hi + lo, residual ~2^-17 |x|): the per-row offsets of the backward (row maximum + log2 row sum, D = dO . O) ride
 // in SPARE columns of the products that need them - S - m = [q | -m_hi | -m_lo] [k | 1 | 1]^T - instead of one subtraction per score.
@@ -87,7 +82,7 @@ __device__ __forceinline__ bf16x8_t cvt8(const Raw8& v, float mul) {
 }
 // The table fills of a workgroup REQUEST everything first and write LDS afterwards (FILL_U items per thread and round): written as
 // load - convert - store per item, each round was a dependent memory round trip (the stores may alias the loads for all the compiler
-// knows) - 8 - 12 of them, 12 us of a workgroup's 30 - 60 us (profiles/r05_sfa_prologue.txt).
+// knows) - 8 - 12 of them, 12 us of a workgroup's 30 - 60 us.
 constexpr int FILL_U = 4;
 __device__ __forceinline__ bf16x8_t acc8(const f32x16_t& x, int s) {              // registers 8 s .. 8 s + 7 of an accumulator as a B fragment
   bf16x8_t r;
@@ -156,9 +151,6 @@ __global__ __launch_bounds__(SFA_NW * 64) void k_sfa_fwd(QkvPtrs qkv, int nl, fl
     }
   }
   __syncthreads();
-#ifdef SFA_PROLOGUE_ONLY
-  if (L > 0) return;
-#endif
   const float qmul = scale * LOG2E;
   for (int qt = wave; qt < NT; qt += SFA_NW) {
     const int q = qt * 32 + r, qc = q < L ? q : L - 1;
@@ -250,9 +242,6 @@ __global__ __launch_bounds__(SFA_NW * 64) void k_sfa_bwd_q(QkvPtrs qkv, int nl, 
     if (vlive) *reinterpret_cast<bf16x8_t*>(Vk + vk * DK) = cvt8(vv, 1.0f);
   }
   __syncthreads();
-#ifdef SFA_PROLOGUE_ONLY
-  if (L > 0) return;
-#endif
   const float qmul = scale * LOG2E;
   for (int qt = wave; qt < NT; qt += SFA_NW) {
     const int q = qt * 32 + r, qc = q < L ? q : L - 1;
@@ -369,9 +358,6 @@ __global__ __launch_bounds__(SFA_NW * 64, SFA_K_MINB) void k_sfa_bwd_kv(QkvPtrs 
     }
   }
   __syncthreads();
-#ifdef SFA_PROLOGUE_ONLY
-  if (L > 0) return;
-#endif
   const float* vsrc = qkv.p[nl - 1];
   for (int kt = wave; kt < NT; kt += SFA_NW) {
     const int k = kt * 32 + r, kc = k < L ? k : L - 1;

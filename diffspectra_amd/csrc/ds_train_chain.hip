@@ -37,8 +37,6 @@ typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 
 namespace {
 
-#define DST_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? DS_OK : DS_ERR_LAUNCH)
-
 constexpr int CH_NW = 4, CH_NT = CH_NW * 64;      // waves per workgroup
 constexpr int LD_Y = 72, LD_S = 136, LD_F = 68, LD_ST = 36;   // LDS row strides: bf16 tiles in halves (16-byte rows), fp32 tiles in floats
 
@@ -1379,16 +1377,13 @@ int dst_pair_chain_fwd(const dst_layout* L, const dst_pair_chain_args* a, void* 
   if (L->B <= 0 || (a->ld_feat & 3) || (a->ld_wed & 7) || (a->ada_ld & 3) || ((a->gate1_off | a->shift_off | a->scale_off | a->gate2_off) & 3) ||
       !(a->drop_p >= 0.0f && a->drop_p < 1.0f))
     return DS_ERR_ARG;
-  const void* ptrs[] = {a->u, a->n2e_bias, a->e_in, a->feat, a->ada, a->W3, a->W4, a->Wed, a->Wro, a->he, a->xe1, a->ye1, a->f3, a->s3, a->f4, a->e_out, a->X2, a->ed, a->ro};
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return DS_ERR_ARG;               // 16-byte accesses throughout
+  if (!dst::all_aligned16({a->u, a->n2e_bias, a->e_in, a->feat, a->ada, a->W3, a->W4, a->Wed, a->Wro, a->he, a->xe1, a->ye1, a->f3, a->s3, a->f4,
+                           a->e_out, a->X2, a->ed, a->ro}))
+    return DS_ERR_ARG;                                                          // 16-byte accesses throughout
   if (L->Pp <= 0) return DS_OK;
-  static bool attr_done = false;
   const size_t lds = sizeof(ChainLds);
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_chain_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DS_ERR_LAUNCH;
-    attr_done = true;
-  }
+  static std::atomic<uint64_t> lds_set{0};
+  if (!dst::allow_dynamic_lds(lds_set, &k_pair_chain_fwd, lds)) return DS_ERR_LAUNCH;
   hipLaunchKernelGGL(k_pair_chain_fwd, dim3((L->Pp + 31) / 32), dim3(CH_NT), lds, (hipStream_t)stream, *L, *a, a->pair_a, a->pair_b, a->pair_mol);
   return DST_CHECK_LAUNCH();
 }
@@ -1396,16 +1391,11 @@ int dst_pair_chain_fwd(const dst_layout* L, const dst_pair_chain_args* a, void* 
 int dst_pair_front_fwd(const dst_layout* L, const dst_pair_front_args* a, void* stream) {
   if (!L || !a || !a->pair_a || !a->pair_b || !a->pair_mol || !a->pos || !a->ada || !a->means || !a->stds || !a->e_in || !a->Wee || !a->bee || !a->Wte || !a->X1 || !a->te) return DS_ERR_ARG;
   if (L->B <= 0 || (a->ada_ld & 3) || ((a->shift_off | a->scale_off) & 3)) return DS_ERR_ARG;
-  const void* ptrs[] = {a->ada, a->e_in, a->Wee, a->Wte, a->X1, a->e1, a->en, a->te};
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return DS_ERR_ARG;
+  if (!dst::all_aligned16({a->ada, a->e_in, a->Wee, a->Wte, a->X1, a->e1, a->en, a->te})) return DS_ERR_ARG;
   if (L->Pp <= 0) return DS_OK;
-  static bool attr_done = false;
   const size_t lds = sizeof(FrontLds);
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_front_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DS_ERR_LAUNCH;
-    attr_done = true;
-  }
+  static std::atomic<uint64_t> lds_set{0};
+  if (!dst::allow_dynamic_lds(lds_set, &k_pair_front_fwd, lds)) return DS_ERR_LAUNCH;
   hipLaunchKernelGGL(k_pair_front_fwd, dim3((L->Pp + 31) / 32), dim3(CH_NT), lds, (hipStream_t)stream, *L, *a, a->pair_a, a->pair_b, a->pair_mol);
   return DST_CHECK_LAUNCH();
 }
@@ -1413,16 +1403,11 @@ int dst_pair_front_fwd(const dst_layout* L, const dst_pair_front_args* a, void* 
 int dst_dir_chain_fwd(const dst_layout* L, const dst_dir_chain_args* a, void* stream) {
   if (!L || !a || !a->pair_a || !a->pair_b || !a->pair_mol || !a->ac || !a->ed || !a->ada || !a->W0 || !a->b0 || !a->W2 || !a->c2) return DS_ERR_ARG;
   if (L->B <= 0 || (a->ada_ld & 3) || ((a->shift_off | a->scale_off) & 3)) return DS_ERR_ARG;
-  const void* ptrs[] = {a->ac, a->ed, a->ada, a->W0, a->W2, a->zz, a->zn, a->c0, a->sc0};
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return DS_ERR_ARG;
+  if (!dst::all_aligned16({a->ac, a->ed, a->ada, a->W0, a->W2, a->zz, a->zn, a->c0, a->sc0})) return DS_ERR_ARG;
   if (L->Pp <= 0) return DS_OK;
-  static bool attr_done = false;
   const size_t lds = sizeof(DirLds);
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dir_chain_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DS_ERR_LAUNCH;
-    attr_done = true;
-  }
+  static std::atomic<uint64_t> lds_set{0};
+  if (!dst::allow_dynamic_lds(lds_set, &k_dir_chain_fwd, lds)) return DS_ERR_LAUNCH;
   hipLaunchKernelGGL(k_dir_chain_fwd, dim3((2 * L->Pp + 31) / 32), dim3(CH_NT), lds, (hipStream_t)stream, *L, *a, a->pair_a, a->pair_b, a->pair_mol);
   return DST_CHECK_LAUNCH();
 }
@@ -1433,16 +1418,12 @@ int dst_node_chain_fwd(const dst_layout* L, const dst_node_chain_args* a, void* 
     return DS_ERR_ARG;
   if (L->B <= 0 || (a->ada_ld & 3) || ((a->gate1_off | a->shift_off | a->scale_off | a->gate2_off) & 3) || !(a->drop_p >= 0.0f && a->drop_p < 1.0f))
     return DS_ERR_ARG;
-  const void* ptrs[] = {a->h_in, a->attn, a->ada, a->W1, a->W2, a->Wac, a->Wn, a->x1, a->y1, a->f1, a->s1, a->f2, a->h_out, a->ac, a->rn};
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return DS_ERR_ARG;
+  if (!dst::all_aligned16({a->h_in, a->attn, a->ada, a->W1, a->W2, a->Wac, a->Wn, a->x1, a->y1, a->f1, a->s1, a->f2, a->h_out, a->ac, a->rn}))
+    return DS_ERR_ARG;
   if (L->Nn <= 0) return DS_OK;
-  static bool attr_done = false;
   const size_t lds = sizeof(NodeLds);
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_node_chain_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DS_ERR_LAUNCH;
-    attr_done = true;
-  }
+  static std::atomic<uint64_t> lds_set{0};
+  if (!dst::allow_dynamic_lds(lds_set, &k_node_chain_fwd, lds)) return DS_ERR_LAUNCH;
   hipLaunchKernelGGL(k_node_chain_fwd, dim3((L->Nn + 31) / 32), dim3(NC_NT), lds, (hipStream_t)stream, *L, *a);
   return DST_CHECK_LAUNCH();
 }
@@ -1452,18 +1433,13 @@ int dst_dir_chain_bwd(const dst_layout* L, const dst_dir_bwd_args* a, void* stre
       !a->W0T || !a->dc0 || !a->dz || !a->part)
     return DS_ERR_ARG;
   if (L->B <= 0 || a->n_tiles < 0 || (a->ada_ld & 3) || ((a->shift_off | a->scale_off) & 3)) return DS_ERR_ARG;
-  const void* ptrs[] = {a->c0, a->zz, a->ada, a->W2, a->W0T, a->dc0, a->dz};
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return DS_ERR_ARG;
+  if (!dst::all_aligned16({a->c0, a->zz, a->ada, a->W2, a->W0T, a->dc0, a->dz})) return DS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (a->n_tiles > 0) {
-    static bool attr_done = false;
     static_assert(sizeof(DirBwdLds) <= CHAIN_BWD_LDS, "");
     const size_t lds = CHAIN_BWD_LDS;
-    if (!attr_done) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dir_chain_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DS_ERR_LAUNCH;
-      attr_done = true;
-    }
+    static std::atomic<uint64_t> lds_set{0};
+    if (!dst::allow_dynamic_lds(lds_set, &k_dir_chain_bwd, lds)) return DS_ERR_LAUNCH;
     hipLaunchKernelGGL(k_dir_chain_bwd, dim3(a->n_tiles), dim3(CH_NT), lds, s, *L, *a);
   }
   hipLaunchKernelGGL(k_dir_bwd_finish, dim3(L->B), dim3(512), 0, s, *a);     // (molecules without pairs: zero sums)
@@ -1477,18 +1453,15 @@ int dst_pair_chain_bwd(const dst_layout* L, const dst_pair_bwd_args* a, void* st
   if (L->B <= 0 || a->n_tiles < 0 || (a->ada_ld & 3) || (a->ld_dro & 3) || ((a->gate1_off | a->shift_off | a->scale_off | a->gate2_off) & 3) ||
       !(a->drop_p >= 0.0f && a->drop_p < 1.0f))
     return DS_ERR_ARG;
-  const void* ptrs[] = {a->de, a->dro, a->ded, a->f4, a->f3, a->xe1, a->he, a->ada, a->WedT, a->WroT, a->W4T, a->W3T, a->dfeat, a->df4, a->df3, a->de_in, a->dhe};
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return DS_ERR_ARG;
+  if (!dst::all_aligned16({a->de, a->dro, a->ded, a->f4, a->f3, a->xe1, a->he, a->ada, a->WedT, a->WroT, a->W4T, a->W3T, a->dfeat, a->df4, a->df3,
+                           a->de_in, a->dhe}))
+    return DS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (a->n_tiles > 0) {
-    static bool attr_done = false;
     static_assert(sizeof(PairBwdLds) <= CHAIN_BWD_LDS, "");
     const size_t lds = CHAIN_BWD_LDS;
-    if (!attr_done) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_chain_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DS_ERR_LAUNCH;
-      attr_done = true;
-    }
+    static std::atomic<uint64_t> lds_set{0};
+    if (!dst::allow_dynamic_lds(lds_set, &k_pair_chain_bwd, lds)) return DS_ERR_LAUNCH;
     hipLaunchKernelGGL(k_pair_chain_bwd, dim3(a->n_tiles), dim3(CH_NT), lds, s, *L, *a);
   }
   hipLaunchKernelGGL(k_pair_bwd_finish, dim3(L->B), dim3(256), 0, s, *a);
@@ -1502,17 +1475,14 @@ int dst_node_chain_bwd(const dst_layout* L, const dst_node_bwd_args* a, void* st
   if (L->B <= 0 || a->n_tiles < 0 || (a->ada_ld & 3) || (a->ld_drn & 3) || ((a->gate1_off | a->shift_off | a->scale_off | a->gate2_off) & 3) ||
       !(a->drop_p >= 0.0f && a->drop_p < 1.0f))
     return DS_ERR_ARG;
-  const void* ptrs[] = {a->dh, a->drn, a->dac, a->f2, a->f1, a->x1, a->attn, a->ada, a->WacT, a->WnT, a->W2T, a->W1T, a->df2, a->df1, a->dh_in, a->dattn};
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return DS_ERR_ARG;
+  if (!dst::all_aligned16({a->dh, a->drn, a->dac, a->f2, a->f1, a->x1, a->attn, a->ada, a->WacT, a->WnT, a->W2T, a->W1T, a->df2, a->df1, a->dh_in,
+                           a->dattn}))
+    return DS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (a->n_tiles > 0) {
-    static bool attr_done = false;
     const size_t lds = sizeof(NodeBwdLds);
-    if (!attr_done) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_node_chain_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DS_ERR_LAUNCH;
-      attr_done = true;
-    }
+    static std::atomic<uint64_t> lds_set{0};
+    if (!dst::allow_dynamic_lds(lds_set, &k_node_chain_bwd, lds)) return DS_ERR_LAUNCH;
     hipLaunchKernelGGL(k_node_chain_bwd, dim3(a->n_tiles), dim3(NC_NT), lds, s, *L, *a);
   }
   hipLaunchKernelGGL(k_node_bwd_finish, dim3(L->B), dim3(1024), 0, s, *a);

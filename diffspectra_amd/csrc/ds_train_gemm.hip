@@ -34,8 +34,6 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 
-#define DST_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? DS_OK : DS_ERR_LAUNCH)
-
 // ------------------------------------------------------------------------------------------------------------------ epilogue
 // One output element.  v = acc + bias; v *= f'(ref) (dact); act: C <- v (pre-activation) and C2 <- drop(f(v)) when C2 is given, else
 // C <- drop(f(v)); no act: C (+)= drop(v).  Column N is the fused row sum (the virtual all-ones column of B).
@@ -609,11 +607,13 @@ int env_int(const char* name, int dflt) {
 
 extern "C" {
 
-int dst_struct_sizes(int64_t* out) {
-  if (!out) return DS_ERR_ARG;
-  out[0] = sizeof(dst_gemm_args);
-  out[1] = sizeof(dst_layout);
-  out[2] = sizeof(dst_piece);
+int dst_struct_sizes(int64_t* out, int32_t cap) {
+  const int64_t sizes[] = {sizeof(dst_gemm_args),       sizeof(dst_layout),          sizeof(dst_piece),         sizeof(dst_pair_chain_args),
+                           sizeof(dst_pair_front_args), sizeof(dst_dir_chain_args),  sizeof(dst_node_chain_args), sizeof(dst_dir_bwd_args),
+                           sizeof(dst_pair_bwd_args),   sizeof(dst_node_bwd_args)};
+  const int32_t n = (int32_t)(sizeof(sizes) / sizeof(sizes[0]));
+  if (!out || cap < n) return DS_ERR_ARG;
+  for (int32_t i = 0; i < n; ++i) out[i] = sizes[i];
   return DS_OK;
 }
 
@@ -664,12 +664,12 @@ int dst_gemm(const dst_gemm_args* a, void* stream) {
     const int max_groups = (256 + nchunks - 1) / nchunks;                     // one workgroup per CU (the resident weight takes most of its LDS)
     if (ngroups > max_groups) ngroups = max_groups;
     const dim3 grid(8 * ((ngroups + 7) / 8) * nchunks), blk(512);
-    static bool attr_done[2] = {false, false};
+    static std::atomic<uint64_t> lds_set[2];
     if (nct == 4) {
-      if (!attr_done[0]) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tr_gemm_ws<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_done[0] = true; }
+      if (!dst::allow_dynamic_lds(lds_set[0], &k_tr_gemm_ws<4>, 160 * 1024)) return DS_ERR_LAUNCH;
       hipLaunchKernelGGL((k_tr_gemm_ws<4>), grid, blk, lds, s, g, (int)b_r, Kp, nchunks, ngroups);
     } else {
-      if (!attr_done[1]) { hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tr_gemm_ws<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_done[1] = true; }
+      if (!dst::allow_dynamic_lds(lds_set[1], &k_tr_gemm_ws<2>, 160 * 1024)) return DS_ERR_LAUNCH;
       hipLaunchKernelGGL((k_tr_gemm_ws<2>), grid, blk, lds, s, g, (int)b_r, Kp, nchunks, ngroups);
     }
     return DST_CHECK_LAUNCH();

@@ -145,7 +145,7 @@ class SpecTrainGraph:
         B, L = t["B"], self.L
         g: Dict[str, torch.Tensor] = {}
         o.async_dw = bool(int(os.environ.get("DIFFSPECTRA_ASYNC_DW", "1")))     # weight gradients on the side stream (train_engine.Ops.lin_bwd_w)
-        two_streams = bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and getattr(o, "main_stream", None) is not None
+        two_streams = bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and o.main_stream is not None
 
         gbuf = getattr(self, "gbuf", None)
 

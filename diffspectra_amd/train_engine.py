@@ -17,7 +17,8 @@ import contextlib
 import ctypes as C
 import os
 import re
-from typing import Dict, List, Optional
+import struct as _struct
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -30,18 +31,67 @@ NODE_OFF, EDGE_OFF, EQUI_OFF, DIST_OFF = (E.CONSTS[k] for k in ("DS_ADA_NODE", "
 NB = E.NB
 SILU, GELU, TANH = 1, 2, 3
 ADDREF = 4                 # dst_gemm `dact` code: the epilogue adds ref (a residual operand) instead of multiplying by f'(ref)
+DW_STREAMS = 2             # weight-gradient streams (1: 19.2 ms per step, 2: 17.9, 3: 18.2; profiles/r05_train_ab_final.txt)
 
 
-class DstGemmArgs(C.Structure):
-    _fields_ = [("A", C.c_void_p), ("a_rs", C.c_int64), ("a_cs", C.c_int64), ("B", C.c_void_p), ("b_rs", C.c_int64), ("b_cs", C.c_int64),
-                ("C", C.c_void_p), ("ldc", C.c_int64), ("bias", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-                ("accumulate", C.c_int32), ("partial", C.c_void_p), ("partial_cap", C.c_int64), ("bf16", C.c_int32), ("_pad", C.c_int32), ("rowsum", C.c_void_p),
-                ("act", C.c_int32), ("dact", C.c_int32), ("ref", C.c_void_p), ("ldref", C.c_int64), ("C2", C.c_void_p), ("ldc2", C.c_int64),
-                ("drop_p", C.c_float), ("drop_stream", C.c_uint32), ("drop_seed", C.c_uint64), ("drop_ld", C.c_int64)]
+# ---- the argument structs of the C-ABI, read from include/diffspectra_train.h (the one description of their layouts; the library reports
+#      its sizes, load_train_library compares)
+_FIELD_CODES = {"int64_t": "q", "int32_t": "i", "uint32_t": "I", "uint64_t": "Q", "float": "f"}
+_CTYPES = {"P": C.c_void_p, "q": C.c_int64, "i": C.c_int32, "I": C.c_uint32, "Q": C.c_uint64, "f": C.c_float}
+# the order in which dst_struct_sizes reports them
+STRUCT_NAMES = ("dst_gemm_args", "dst_layout", "dst_piece", "dst_pair_chain_args", "dst_pair_front_args", "dst_dir_chain_args",
+                "dst_node_chain_args", "dst_dir_bwd_args", "dst_pair_bwd_args", "dst_node_bwd_args")
 
 
-class DstPiece(C.Structure):
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("src_ld", C.c_int64), ("dst_ld", C.c_int64)]
+def _header_text() -> str:
+    """The training header without its comments."""
+    with open(TRAIN_HEADER) as f:
+        return re.sub(r"/\*.*?\*/|//[^\n]*", "", f.read(), flags=re.S)
+
+
+def train_exports() -> List[str]:
+    return re.findall(r"^\s*int\s+(dst_\w+)\s*\(", _header_text(), flags=re.M)
+
+
+def header_structs() -> Dict[str, List[Tuple[str, str]]]:
+    """``{struct name: [(field, struct code)]}`` of every ``typedef struct dst_* { ... }`` of the header: any pointer is ``P``, scalars map
+    through ``_FIELD_CODES``; a declaration may list several fields (``int32_t a, b;``, ``float *x, *y;``)."""
+    txt = _header_text()
+    out = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(dst_\w+)\s*\{(.*?)\}", txt, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            typ, rest = re.fullmatch(r"(?:const\s+)?(\w+)\s*(.*)", decl, flags=re.S).groups()
+            for f_ in rest.split(","):
+                f_ = f_.strip()
+                fields.append((f_.lstrip("* "), "P" if f_.startswith("*") else _FIELD_CODES[typ]))
+        out[name] = fields
+    return out
+
+
+def _native_format(fields) -> str:
+    return "@" + "".join(code for _, code in fields)          # native alignment: the C compiler's layout
+
+
+_FIELDS = header_structs()
+# Call sites pack positionally: keyword packing or a ctypes Structure built field by field costs ~10 us per call, and a step makes ~600 products
+STRUCTS = {n: _struct.Struct(_native_format(fl)) for n, fl in _FIELDS.items()}
+_GEMM_PACK = STRUCTS["dst_gemm_args"].pack
+_CHAIN_PACK = STRUCTS["dst_pair_chain_args"].pack
+_FRONT_PACK = STRUCTS["dst_pair_front_args"].pack
+_DIR_PACK = STRUCTS["dst_dir_chain_args"].pack
+_NODE_PACK = STRUCTS["dst_node_chain_args"].pack
+_DIRB_PACK = STRUCTS["dst_dir_bwd_args"].pack
+_PAIRB_PACK = STRUCTS["dst_pair_bwd_args"].pack
+_NODEB_PACK = STRUCTS["dst_node_bwd_args"].pack
+
+
+def _ctypes_struct(name: str):
+    return type(name, (C.Structure,), {"_fields_": [(f_, _CTYPES[code]) for f_, code in _FIELDS[name]]})
+
+
+DstPiece = _ctypes_struct("dst_piece")
+DstLayout = _ctypes_struct("dst_layout")
 
 
 def copy_pieces(lib, dev, dst: List[torch.Tensor], src: List[torch.Tensor], cache: dict, key: str, stream=None):
@@ -85,37 +135,6 @@ def pack_bf16_pieces(lib, dev, dst: List[torch.Tensor], src: List[torch.Tensor],
     E._check(lib.dst_pack_bf16_pieces(C.c_void_p(ent[1].data_ptr()), C.c_int32(ent[2]), stream if stream is not None else E._stream()), "dst_pack_bf16_pieces")
 
 
-# dst_gemm_args as one struct.pack (a ctypes Structure built field by field costs ~10 us per product, ~600 products per step)
-import struct as _struct
-_GEMM_STRUCT = _struct.Struct("@PqqPqqPqPiiiiPqiiPiiPqPqfIQq")
-assert _GEMM_STRUCT.size == C.sizeof(DstGemmArgs), (_GEMM_STRUCT.size, C.sizeof(DstGemmArgs))
-_GEMM_PACK = _GEMM_STRUCT.pack
-# dst_pair_chain_args (include/diffspectra_train.h): 4 pointers, ld_feat | ada, ada_ld | 4 offsets | W3 b3 W4 b4 Wed, ld_wed | bed Wro bro |
-# drop_p, stream3, stream4, pad | seed | 11 output pointers
-_CHAIN_PACK = _struct.Struct("@PPP PPPPq Pq iiii PPPPP q PPP f III Q PPPPPPPPPPP").pack
-# dst_pair_front_args: pos, ada, ada_ld | dist_off, shift_off, scale_off, pad | means stds e_in Wee bee Wte | X1 xs d2 e1 st en te
-_FRONT_PACK = _struct.Struct("@PPP PPq iiii PPPPPP PPPPPPP").pack
-# dst_node_bwd_args: 4 tables, n_tiles | dh drn ld_drn dac | f2 f1 x1 st attn | ada d_ada ada_ld | 4 offsets | WacT WnT W2T W1T | drop | seed | 5 outputs
-_NODEB_PACK = _struct.Struct("@PPPPq PPqP PPPPP PPq iiii PPPP f III Q PPPPP").pack
-# dst_pair_bwd_args: 4 tables, n_tiles | de dro ld_dro ded | f4 f3 xe1 st he | ada d_ada ada_ld | 4 offsets | WedT WroT W4T W3T | drop | seed | 6 outputs
-_PAIRB_PACK = _struct.Struct("@PPPPq PPqP PPPPP PPq iiii PPPP f III Q PPPPPP").pack
-# dst_dir_bwd_args: 4 tables, n_tiles | dc2 c0 zz st | ada d_ada ada_ld | shift_off scale_off | W2 W0T | dc0 dz part
-_DIRB_PACK = _struct.Struct("@PPPPq PPPP PPq ii PP PPP").pack
-# dst_node_chain_args: node_mol h_in attn | ada, ada_ld | 4 offsets | W1 b1 W2 b2 Wac Wn bn | drop_p, stream1, stream2, pad | seed | 9 outputs
-_NODE_PACK = _struct.Struct("@PPP Pq iiii PPPPPPP f III Q PPPPPPPPP").pack
-# dst_dir_chain_args: ac, ed, ada, ada_ld | shift_off, scale_off | W0 b0 W2 | zz st zn c0 sc0 c2
-_DIR_PACK = _struct.Struct("@PPP PPPq ii PPP PPPPPP").pack
-
-
-class DstLayout(C.Structure):
-    _fields_ = [("B", C.c_int32), ("Nn", C.c_int32), ("Pp", C.c_int32), ("_pad", C.c_int32), ("node_off", C.c_void_p), ("pair_off", C.c_void_p)]
-
-
-def train_exports() -> List[str]:
-    txt = re.sub(r"/\*.*?\*/", "", open(TRAIN_HEADER).read(), flags=re.S)
-    return re.findall(r"^\s*int\s+(dst_\w+)\s*\(", txt, flags=re.M)
-
-
 _lib = None
 
 
@@ -126,11 +145,11 @@ def load_train_library() -> C.CDLL:
         lib = E.load_library()
         for name in train_exports():
             getattr(lib, name).restype = C.c_int
-        sizes = (C.c_int64 * 3)()
-        lib.dst_struct_sizes(sizes)
-        mine = [C.sizeof(DstGemmArgs), C.sizeof(DstLayout), C.sizeof(DstPiece)]
-        if list(sizes) != mine:
-            raise RuntimeError(f"C-ABI struct layout mismatch (training): library {list(sizes)} vs binding {mine}")
+        sizes = (C.c_int64 * len(STRUCT_NAMES))()
+        E._check(lib.dst_struct_sizes(sizes, C.c_int32(len(sizes))), "dst_struct_sizes")
+        bad = [(n, lib_n, STRUCTS[n].size) for n, lib_n in zip(STRUCT_NAMES, sizes) if STRUCTS[n].size != lib_n]
+        if bad:
+            raise RuntimeError(f"C-ABI struct layout mismatch (training): (struct, library, binding) {bad}")
         _lib = lib
     return _lib
 
@@ -179,13 +198,15 @@ class Ops:
         # dW, so the ~200 split-K products of a step need not sit in the dependent chain of input-gradient kernels - they fill the CUs the
         # small kernels of that chain leave idle.  The side stream has its own split-K scratch; operands are kept alive until join_dw().
         self.async_dw = False
-        self.stream_ptr = None
-        self._side = None
-        self._side_scratch = None
-        self._sides = []           # the weight-gradient streams (DIFFSPECTRA_DW_STREAMS of them, round-robin), each with its split-K scratch
+        self.main_stream = None    # torch's current stream between begin() and end()
+        self.stream_ptr = None     # the HIP stream launches go to (main, or the node / a weight-gradient stream inside _OnStream)
+        self.cur_stream = None     # the torch stream of stream_ptr inside a node section or a weight-gradient product, else None (main)
+        self._node = None          # the node stream (_OnStream), created by the first node section
+        self._sides = []           # the weight-gradient streams (_OnStream, DW_STREAMS of them, round-robin)
         self._side_of = {}         # output pointer -> stream index: products that accumulate into the same gradient stay on one stream, in order
         self._side_next = 0
         self._dw_keep = []
+        self._parts = {}           # scratch of the fused backward kernels' column sums, grown on demand
 
     def _s(self):
         """The HIP stream the kernels are issued on.  ``torch.cuda.current_stream()`` costs ~8 us and a step makes ~1 200 calls: the training
@@ -230,13 +251,8 @@ class Ops:
         they go there, like ``lin_bwd_w``; X must then not be overwritten before ``join_dw``."""
         assert out.numel() == X.cols
         if param_grad and self.async_dw:
-            self._to_side(X.t, out, out=out)
-            saved = (self.scratch, self.stream_ptr)
-            self.scratch, self.stream_ptr = self._side_scratch, C.c_void_p(self._side.cuda_stream)
-            try:
+            with self._to_side(X.t, out, out=out):
                 return self.colsum(X, out, acc)
-            finally:
-                self.scratch, self.stream_ptr = saved
         E._check(self.lib.dst_colsum(C.c_void_p(X.ptr), C.c_int64(X.ld), C.c_int32(X.rows), C.c_int32(X.cols), E._ptr(out), C.c_int32(int(acc)),
                                      E._ptr(self.scratch), C.c_int64(self.scratch.numel()), self._s()), "dst_colsum")
 
@@ -246,8 +262,7 @@ class Ops:
         gradient is a split-K product plus its reduction, two dependent launches that fill a fraction of the chip - on one stream they ran one
         after the other and that stream, not the main one, ended the backward (leaving every weight gradient out shortened the step by 3.9 ms)."""
         if not self._sides:
-            n = max(1, int(os.environ.get("DIFFSPECTRA_DW_STREAMS", "2")))     # (2 -> 3: no further gain; profiles/r05_train_dw_streams.txt)
-            self._sides = [(torch.cuda.Stream(device=self.dev), torch.empty_like(self.scratch)) for _ in range(n)]
+            self._sides = [_OnStream(self, torch.cuda.Stream(device=self.dev), torch.empty_like(self.scratch)) for _ in range(DW_STREAMS)]
         key = None if out is None else out.data_ptr()
         k = self._side_of.get(key) if key is not None else None
         if k is None:
@@ -255,12 +270,13 @@ class Ops:
             self._side_next = (k + 1) % len(self._sides)
             if key is not None:
                 self._side_of[key] = k
-        self._side, self._side_scratch = self._sides[k]
-        src = getattr(self, "cur_stream", None)
-        if src is None:
-            src = self.main_stream if getattr(self, "main_stream", None) is not None else torch.cuda.current_stream(self.dev)
-        self._side.wait_stream(src)
+        side = self._sides[k]
+        side.stream.wait_stream(self.cur_stream if self.cur_stream is not None else self._main())
         self._dw_keep.append(keep)
+        return side
+
+    def _main(self):
+        return self.main_stream if self.main_stream is not None else torch.cuda.current_stream(self.dev)
 
     # y = x W^T + b ; dx (+)= dy W ; dW = dy^T x ; db = colsum(dy)
     def lin_fwd(self, x: MV, W: MV, b, y: MV, act: int = 0, out2: Optional[MV] = None, drop=None):
@@ -276,13 +292,8 @@ class Ops:
         if not self.async_dw:
             self.gemm(dy, x, dW, True, False, acc=acc, rowsum=db)       # db = column sums of dy = row sums of dy^T, fused into the product
             return
-        self._to_side(dy.t, x.t, dW.t, db, out=dW.t)                    # dy (and x) are complete on their stream at this point
-        main_scratch, self.scratch = self.scratch, self._side_scratch
-        main_ptr, self.stream_ptr = self.stream_ptr, C.c_void_p(self._side.cuda_stream)
-        try:
+        with self._to_side(dy.t, x.t, dW.t, db, out=dW.t):              # dy (and x) are complete on their stream at this point
             self.gemm(dy, x, dW, True, False, acc=acc, rowsum=db)
-        finally:
-            self.scratch, self.stream_ptr = main_scratch, main_ptr
 
     # ---- node stream (forward): the node-row chain of a block (4 600 rows: ten launches, each shorter than its launch latency) runs beside
     #      the pair-row chain instead of in front of it.  Rules that make it safe with torch's caching allocator (all tensors come from
@@ -290,26 +301,29 @@ class Ops:
     #      memory the section allocates was freed before that point, so its earlier users are covered), and nothing a section touches is
     #      freed before the join at the end of the pass (the graph holds the references).
     def node_section(self):
-        return _NodeSection(self)
+        if self._node is None:
+            self._node = _OnStream(self, torch.cuda.Stream(device=self.dev), torch.empty(4 * 1024 * 1024, dtype=torch.float32, device=self.dev))
+        self._node.stream.wait_stream(self.main_stream)
+        return self._node
 
     def node_event(self):
         ev = torch.cuda.Event()
-        ev.record(self._node)
+        ev.record(self._node.stream)
         return ev
 
     def main_wait(self, ev=None):
         """The main stream waits for the node stream (as of now) or for one recorded event."""
         if ev is None:
-            self.main_stream.wait_stream(self._node)
+            self.main_stream.wait_stream(self._node.stream)
         else:
             self.main_stream.wait_event(ev)
 
     def join_dw(self):
         """The main stream waits for every weight-gradient product issued so far; their operands may be reused after it."""
         if self._sides and self._dw_keep:
-            main = self.main_stream if getattr(self, "main_stream", None) is not None else torch.cuda.current_stream(self.dev)
-            for st, _ in self._sides:
-                main.wait_stream(st)
+            main = self._main()
+            for side in self._sides:
+                main.wait_stream(side.stream)
         self._side_of = {}
         self._dw_keep = []
 
@@ -369,19 +383,24 @@ class Ops:
         args = _DIR_PACK(*TL.pair_tables, ptr(ac), ptr(ed), ptr(ada), ADA, sh, sc, ptr(W0), ptr(b0), ptr(W2), *(ptr(out.get(k)) for k in ("zz", "st", "zn", "c0", "sc0", "c2")))
         E._check(self.lib.dst_dir_chain_fwd(C.byref(TL.c), args, self._s()), "dst_dir_chain_fwd")
 
+    def _part(self, kernel: str, n: int) -> int:
+        """Data pointer of the column-sum scratch of fused backward kernel ``kernel`` (at least ``n`` floats; one buffer per kernel, kept and
+        grown on demand)."""
+        t = self._parts.get(kernel)
+        if t is None or t.numel() < n:
+            t = self._parts[kernel] = torch.empty(max(n, 1), dtype=torch.float32, device=self.dev)
+        return t.data_ptr()
+
     def pair_chain_bwd(self, TL, de, dro, ld_dro, ded, f4, f3, xe1, st, he, ada, d_ada, g1, sh, sc, g2, WedT, WroT, W4T, W3T, drop, dfeat, df4, df3, de_in, dhe):
         """Backward of the pair rows of a block behind the attention as one kernel + its finishing kernel (``dst_pair_chain_bwd``).  ``dro``: a
         data pointer (the read-out slice's gradient is a column window of a wider tensor) with row stride ``ld_dro``; ``drop = (p, seed, stream3,
         stream4)``."""
         assert all(w_.dtype == torch.bfloat16 for w_ in (WedT, WroT, W4T, W3T))
         tt = TL.pair_tiles
-        need = tt[4] * 256
-        if getattr(self, "_pairb_part", None) is None or self._pairb_part.numel() < need:
-            self._pairb_part = torch.empty(max(need, 1), dtype=torch.float32, device=self.dev)
         dp_ = lambda t: t.data_ptr()
         args = _PAIRB_PACK(tt[0], tt[1], tt[2], tt[3], tt[4], dp_(de), int(dro), ld_dro, dp_(ded), dp_(f4), dp_(f3), dp_(xe1), dp_(st), dp_(he), dp_(ada), dp_(d_ada), ADA,
                            g1, sh, sc, g2, dp_(WedT), dp_(WroT), dp_(W4T), dp_(W3T), float(drop[0]), int(drop[2]), int(drop[3]), 0, int(drop[1]),
-                           dp_(dfeat), dp_(df4), dp_(df3), dp_(de_in), dp_(dhe), self._pairb_part.data_ptr())
+                           dp_(dfeat), dp_(df4), dp_(df3), dp_(de_in), dp_(dhe), self._part("pair", tt[4] * 256))
         E._check(self.lib.dst_pair_chain_bwd(C.byref(TL.c), args, self._s()), "dst_pair_chain_bwd")
 
     def node_chain_bwd(self, TL, dh, drn, ld_drn, dac, f2, f1, x1, st, attn, ada, d_ada, g1, sh, sc, g2, WacT, WnT, W2T, W1T, drop, df2, df1, dh_in, dattn):
@@ -389,25 +408,18 @@ class Ops:
         pointer with row stride ``ld_drn``; ``drop = (p, seed, stream1, stream2)``."""
         assert all(w_.dtype == torch.bfloat16 for w_ in (WacT, WnT, W2T, W1T))
         tt = TL.node_tiles
-        need = tt[4] * 1024
-        part = getattr(self, "_nodeb_part", None)
-        if part is None or part.numel() < need:
-            part = self._nodeb_part = torch.empty(max(need, 1), dtype=torch.float32, device=self.dev)
         dp_ = lambda t: t.data_ptr()
         args = _NODEB_PACK(tt[0], tt[1], tt[2], tt[3], tt[4], dp_(dh), int(drn), ld_drn, dp_(dac), dp_(f2), dp_(f1), dp_(x1), dp_(st), dp_(attn), dp_(ada), dp_(d_ada), ADA,
                            g1, sh, sc, g2, dp_(WacT), dp_(WnT), dp_(W2T), dp_(W1T), float(drop[0]), int(drop[2]), int(drop[3]), 0, int(drop[1]),
-                           dp_(df2), dp_(df1), dp_(dh_in), dp_(dattn), part.data_ptr())
+                           dp_(df2), dp_(df1), dp_(dh_in), dp_(dattn), self._part("node", tt[4] * 1024))
         E._check(self.lib.dst_node_chain_bwd(C.byref(TL.c), args, self._s()), "dst_node_chain_bwd")
 
     def dir_chain_bwd(self, TL, dc2, c0, zz, st, ada, d_ada, sh, sc, W2, W0T, dc0, dz):
         """Backward of the directed rows of a block as one kernel + its finishing kernel (``dst_dir_chain_bwd``)."""
         assert W0T.dtype == torch.bfloat16 and W2.dtype == torch.float32
         tt = TL.dir_tiles
-        need = tt[4] * 512
-        if getattr(self, "_dirb_part", None) is None or self._dirb_part.numel() < need:
-            self._dirb_part = torch.empty(max(need, 1), dtype=torch.float32, device=self.dev)
         args = _DIRB_PACK(tt[0], tt[1], tt[2], tt[3], tt[4], dc2.data_ptr(), c0.data_ptr(), zz.data_ptr(), st.data_ptr(), ada.data_ptr(), d_ada.data_ptr(), ADA, sh, sc,
-                          W2.data_ptr(), W0T.data_ptr(), dc0.data_ptr(), dz.data_ptr(), self._dirb_part.data_ptr())
+                          W2.data_ptr(), W0T.data_ptr(), dc0.data_ptr(), dz.data_ptr(), self._part("dir", tt[4] * 512))
         E._check(self.lib.dst_dir_chain_bwd(C.byref(TL.c), args, self._s()), "dst_dir_chain_bwd")
 
     def pair_front_fwd(self, TL, pos, ada, dist_off, sh, sc, means, stds, e_in, Wee, bee, Wte, out):
@@ -427,19 +439,18 @@ class Ops:
                                            C.c_uint32(stream), self._s()), "dst_gate_add_bwd")
 
 
-class _NodeSection:
-    def __init__(self, ops):
-        self.o = ops
+class _OnStream:
+    """A stream of its own with its own scratch: inside ``with``, the launches of ``Ops`` go to it.  One object per stream, entered by one
+    ``with`` at a time (the node stream and each weight-gradient stream; a weight-gradient product may be issued from inside a node section)."""
+    __slots__ = ("o", "stream", "ptr", "scratch", "saved")
+
+    def __init__(self, ops, stream, scratch):
+        self.o, self.stream, self.ptr, self.scratch = ops, stream, C.c_void_p(stream.cuda_stream), scratch
 
     def __enter__(self):
         o = self.o
-        if getattr(o, "_node", None) is None:
-            o._node = torch.cuda.Stream(device=o.dev)
-            o._node_ptr = C.c_void_p(o._node.cuda_stream)
-            o._node_scratch = torch.empty(4 * 1024 * 1024, dtype=torch.float32, device=o.dev)
-        o._node.wait_stream(o.main_stream)
-        self.saved = (o.stream_ptr, o.scratch, getattr(o, "cur_stream", None))
-        o.stream_ptr, o.scratch, o.cur_stream = o._node_ptr, o._node_scratch, o._node
+        self.saved = (o.stream_ptr, o.scratch, o.cur_stream)
+        o.stream_ptr, o.scratch, o.cur_stream = self.ptr, self.scratch, self.stream
         return self
 
     def __exit__(self, *exc):
@@ -681,10 +692,11 @@ class DmtTrainGraph:
         t.update(X0n=X0n, X0p=X0p, xs0=xs0, d2c=d2c, adj=adj, h0=h, e0=e)
         node_hids, edge_hids = [h], [e]
         blocks = []
-        ns = bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and getattr(o, "main_stream", None) is not None
+        ns = bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and o.main_stream is not None
         sec = o.node_section if ns else contextlib.nullcontext
         # fused row chains: bf16 mode only (their products are bf16 MFMAs; the fp32 mode keeps the per-operation kernels golden G13 / G17 pin)
         fused_chain = bool(o.bf16) and Pp > 0 and os.environ.get("DIFFSPECTRA_FUSED_CHAIN", "1") != "0"
+        t.update(node_stream=ns, fused_chain=fused_chain)        # the backward walks this tape with the same choices
         for i in range(NB):
             bp = f"e_block_{i}."
             a0 = i * ADA_STRIDE
@@ -887,13 +899,11 @@ class DmtTrainGraph:
         de = self.z(Pp, 64)
         dpos_out = dpos
         dd2_buf = self.f(max(Pp, 1))
-        ns = bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and getattr(o, "main_stream", None) is not None
+        ns = t["node_stream"]
         sec = o.node_section if ns else contextlib.nullcontext
-        fused_chain = bool(o.bf16) and Pp > 0 and os.environ.get("DIFFSPECTRA_FUSED_CHAIN", "1") != "0" and getattr(self, "wb", None) is not None
-        # which fused BACKWARD kernels run (DIFFSPECTRA_FUSED_BWD, default all three; the pair- and directed-row kernels take a CU's LDS alone,
+        # the fused forward's tape feeds the fused backward kernels (the pair- and directed-row kernels take a CU's LDS alone,
         # csrc/ds_train_chain.hip CHAIN_BWD_LDS: sharing a CU with a weight-gradient product they were not bit-reproducible)
-        _fb = os.environ.get("DIFFSPECTRA_FUSED_BWD", "node,pair,dir")
-        fused_node_b, fused_pair_b, fused_dir_b = (fused_chain and k in _fb for k in ("node", "pair", "dir"))
+        fused_chain = t["fused_chain"]
         for i in reversed(range(NB)):
             bt = t["blocks"][i]
             bp = f"e_block_{i}."
@@ -903,10 +913,10 @@ class DmtTrainGraph:
             drn, dre = mv(dAH, 256 + 64 * i, 256 + 64 * (i + 1)), mv(dEH, 64 + 16 * i, 64 + 16 * (i + 1))
             with sec():
                 o.lin_bwd_w(drn, mv(bt["h_out"]), mv(gw(f"node_{i}.weight")), gw(f"node_{i}.bias"))
-                if not fused_node_b:                              # (fused: inside dst_node_chain_bwd)
+                if not fused_chain:                               # (fused: inside dst_node_chain_bwd)
                     o.lin_bwd_x(drn, mv(p[f"node_{i}.weight"]), mv(dh), acc=True)
             o.lin_bwd_w(dre, mv(bt["e_out"]), mv(gw(f"edge_{i}.weight")), gw(f"edge_{i}.bias"))
-            if not fused_pair_b:                                  # (fused: inside dst_pair_chain_bwd)
+            if not fused_chain:                                  # (fused: inside dst_pair_chain_bwd)
                 o.lin_bwd_x(dre, mv(p[f"edge_{i}.weight"]), mv(de), acc=True)
             # equivariant update
             dpos_in, dc2 = self.f(Nn, 3), self.f(max(D, 1), 3)
@@ -919,7 +929,7 @@ class DmtTrainGraph:
             o.lin_bwd_w(mv(dc2, r1=D), mv(bt["sc0"], r1=D), mv(gw(bp + "equi_update.coord_mlp.2.weight")))
             dc0 = self.f(max(D, 1), 256)
             dz = self.f(max(D, 1), 256)                      # (not dc0: the coord_mlp.0 weight gradient may still be reading it on the side stream)
-            if fused_dir_b:
+            if fused_chain:
                 # coord_mlp.2's and coord_mlp.0's input gradients and the LayerNorm backward as ONE kernel (csrc/ds_train_chain.hip)
                 o.dir_chain_bwd(TL, dc2, bt["c0"], bt["zz"], bt["st_z"], ada, d_ada, a0 + EQUI_OFF + 0, a0 + EQUI_OFF + 256,
                                 p[bp + "equi_update.coord_mlp.2.weight"], self.wb["W0T"][i], dc0, dz)
@@ -935,7 +945,7 @@ class DmtTrainGraph:
             # node stream (the section waits for dac)
             with sec():
                 o.lin_bwd_w(mv(dac), mv(bt["h_out"]), mv(dcat["Wac"][i]))           # both node parts at once; scattered into dWin[:, 0:512] at the end
-                if fused_node_b:
+                if fused_chain:
                     # the five input gradients, both gated residuals and the LayerNorm backward of the node chain as ONE kernel (csrc/ds_train_chain.hip)
                     df2, df1, dh_in, dattn = self.f(Nn, 256), self.f(Nn, 512), self.f(Nn, 256), self.f(Nn, 256)
                     o.node_chain_bwd(TL, dh, dAH.data_ptr() + 4 * (256 + 64 * i), 768, dac, bt["f2"], bt["f1"], bt["x1"], bt["st_n2"], bt["attn"], ada, d_ada,
@@ -958,7 +968,7 @@ class DmtTrainGraph:
                     o.gate_add_bwd(dx1, bt["attn"], 256, TL.node_off, 1, B, ada, d_ada, a0 + NODE_OFF + 512, dh_in, False, dattn)
             # edge stream
             o.lin_bwd_w(mv(ded), mv(bt["X2"]), mv(dWin, 512, 640), gw(bp + "equi_update.input_lin.bias"))
-            if fused_pair_b:
+            if fused_chain:
                 # the five input gradients, both gated residuals and the LayerNorm backward of the rear chain as ONE kernel (csrc/ds_train_chain.hip)
                 dfeat2, df4, df3, de_in, dhe = self.f(Pp, 64), self.f(Pp, 64), self.f(Pp, 128), self.f(Pp, 64), self.f(Pp, 64)
                 o.pair_chain_bwd(TL, de, dEH.data_ptr() + 4 * (64 + 16 * i), 192, ded, bt["f4"], bt["f3"], bt["xe1"], bt["st_e2"], bt["he"], ada, d_ada,

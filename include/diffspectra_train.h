@@ -64,9 +64,10 @@ typedef struct dst_gemm_args {
 } dst_gemm_args;
 int dst_gemm(const dst_gemm_args* a, void* stream);
 
-/* out[0] = sizeof(dst_gemm_args), out[1] = sizeof(dst_layout), out[2] = sizeof(dst_piece): the binding checks its own struct layouts
- * against the library's. */
-int dst_struct_sizes(int64_t* out);
+/* sizeof of every argument struct of this header, in this order: dst_gemm_args, dst_layout, dst_piece, dst_pair_chain_args,
+ * dst_pair_front_args, dst_dir_chain_args, dst_node_chain_args, dst_dir_bwd_args, dst_pair_bwd_args, dst_node_bwd_args (ten values;
+ * DS_ERR_ARG when cap < 10).  The binding builds its layouts from this header and checks each against the library's. */
+int dst_struct_sizes(int64_t* out, int32_t cap);
 
 /* n strided 2-D copies in ONE launch: dst[r*dst_ld + c] = src[r*src_ld + c] for r < rows, c < cols of every piece; `table` is a DEVICE
  * array.  (The per-step concatenation of Linears that share an input - q | k | v, the adaLN table, ... - and the scatter of the

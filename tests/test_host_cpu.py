@@ -31,6 +31,28 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(tl, name), name
 
 
+def test_training_structs_parsed_from_the_header():
+    """The binding packs the training C-ABI's argument structs in the layouts parsed from include/diffspectra_train.h: pinned to the
+    layouts the kernels were validated with (the library checks the sizes at load time)."""
+    from diffspectra_amd import train_engine as T
+    expected = {
+        "dst_gemm_args": "@PqqPqqPqPiiiiPqiiPiiPqPqfIQq",
+        "dst_layout": "@iiiiPP",
+        "dst_piece": "@PPiiqq",
+        "dst_pair_chain_args": "@PPP PPPPq Pq iiii PPPPP q PPP f III Q PPPPPPPPPPP",
+        "dst_pair_front_args": "@PPP PPq iiii PPPPPP PPPPPPP",
+        "dst_dir_chain_args": "@PPP PPPq ii PPP PPPPPP",
+        "dst_node_chain_args": "@PPP Pq iiii PPPPPPP f III Q PPPPPPPPP",
+        "dst_dir_bwd_args": "@PPPPq PPPP PPq ii PP PPP",
+        "dst_pair_bwd_args": "@PPPPq PPqP PPPPP PPq iiii PPPP f III Q PPPPPP",
+        "dst_node_bwd_args": "@PPPPq PPqP PPPPP PPq iiii PPPP f III Q PPPPP",
+    }
+    assert {n: s.format for n, s in T.STRUCTS.items()} == {n: f.replace(" ", "") for n, f in expected.items()}
+    assert sorted(T.STRUCT_NAMES) == sorted(expected)
+    assert [f for f, _ in T.header_structs()["dst_pair_chain_args"]][-11:] == ["he", "xe1", "st", "ye1", "f3", "s3", "f4", "e_out", "X2", "ed", "ro"]
+    assert ctypes.sizeof(T.DstLayout) == T.STRUCTS["dst_layout"].size and ctypes.sizeof(T.DstPiece) == T.STRUCTS["dst_piece"].size
+
+
 def test_training_surface_refuses_cpu():
     """Row N1 has no CPU path either: optimizer, loss function and graphs raise off the GPU."""
     from diffspectra_amd import losses as Lh, train_engine as T

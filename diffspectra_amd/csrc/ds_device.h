@@ -27,16 +27,6 @@ __device__ __forceinline__ float ds_tanh(float x) {
   const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);
   return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
-// Two at a time: the multiply, add and fma become packed-fp32 issues (v_pk_*), 7 VALU issues per 2 values instead of 10.
-__device__ __forceinline__ f32x2 ds_tanh2(f32x2 x) {
-  const f32x2 t = x * 2.8853900817779268f;
-  f32x2 e;
-  e.x = __builtin_amdgcn_exp2f(t.x); e.y = __builtin_amdgcn_exp2f(t.y);
-  const f32x2 d = e + 1.0f;
-  f32x2 r;
-  r.x = __builtin_amdgcn_rcpf(d.x); r.y = __builtin_amdgcn_rcpf(d.y);
-  return r * -2.0f + 1.0f;
-}
 // tanh of a pair that already carries the factor 2 log2(e) (DS_TANH_PRESCALE, folded into the packed lin_edge0 / lin_edge1 weights by
 // engine.py): one packed multiply per pair less next to the transcendental-bound projection of k_attn_fused
 __device__ __forceinline__ f32x2 ds_tanh2_prescaled(f32x2 t) {
@@ -364,9 +354,7 @@ __device__ __forceinline__ void wave_mma_h(const _Float16* X, int K_tile, const 
 // no second MFMA wave to fill the gap every k-block then waits for its weights (k_equi_pairs: ISA showed s_waitcnt vmcnt
 // in front of every block).  NKB (k-blocks) is a compile-time constant so that the ring indices are.  `ring` carries the
 // first PF blocks in (requested by the caller with wring_h, e.g. under the previous epilogue) - no request is exposed at all.
-#ifndef DS_MMA_XD
-#define DS_MMA_XD 1   // X fragments ahead of the MFMAs (k-blocks); measured 1 / 2 / 3: no difference, 1 costs the fewest registers
-#endif
+constexpr int DS_MMA_XD = 1;   // X fragments ahead of the MFMAs (k-blocks); measured 1 / 2 / 3: no difference, 1 costs the fewest registers
 template <int PF>
 struct WRingH {
   h8 w1[PF], w2[PF];
@@ -557,38 +545,6 @@ __device__ __forceinline__ void acc_store(const f32x16 (&acc)[MT], float* __rest
       for (int i = 0; i < 16; ++i) {
         const int row = m * 32 + (i & 3) + 8 * (i >> 2);
         if (row + 4 * hh < rows_valid) row_put(st, row * LD * 4, f(r, acc[m][i]));
-      }
-  }
-}
-
-// acc_store with a two-wide epilogue f2(f32x2) -> f32x2 (packed-fp32 arithmetic for activation epilogues).
-template <int MT, int LD, class F2>
-__device__ __forceinline__ void acc_store2(const f32x16 (&acc)[MT], float* __restrict__ dst, int rows_valid, F2 f2) {
-  const int hh = (threadIdx.x & 63) >> 5;
-  const RowStore st = row_store<LD>(dst);
-  if (rows_valid >= 32 * MT) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int i = 0; i < 16; i += 2) {   // i even: registers i, i+1 are two consecutive rows
-        f32x2 v;
-        v.x = acc[m][i]; v.y = acc[m][i + 1];
-        v = f2(v);
-        const int row0 = m * 32 + (i & 3) + 8 * (i >> 2);
-        row_put(st, row0 * LD * 4, v.x);
-        row_put(st, (row0 + 1) * LD * 4, v.y);
-      }
-  } else {
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int i = 0; i < 16; i += 2) {
-        f32x2 v;
-        v.x = acc[m][i]; v.y = acc[m][i + 1];
-        v = f2(v);
-        const int row0 = m * 32 + (i & 3) + 8 * (i >> 2);
-        if (row0 + 4 * hh < rows_valid) row_put(st, row0 * LD * 4, v.x);
-        if (row0 + 1 + 4 * hh < rows_valid) row_put(st, (row0 + 1) * LD * 4, v.y);
       }
   }
 }

@@ -7,36 +7,21 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <atomic>
+#include <mutex>
 #include <utility>
 #include <vector>
 
 #include "../../include/diffspectra_hip.h"
 #include "ds_device.h"
+#include "ds_train_common.h"   // DST_CHECK_LAUNCH: the one launch-status rule of the library
 
 #define ADAC DS_ADA_COLS
 // k-blocks of weights in flight per wave in the 16-block GEMMs (ds_device.h, wave_mma_h_deep); measured 4 / 8 / 12: 8
-#ifndef DS_NODE_PF
-#define DS_NODE_PF 8
-#endif
-#ifndef DS_NODE_PF2
-#define DS_NODE_PF2 4   // per ring when two chunks share the X fragments
-#endif
-#ifndef DS_QKV_PF
-#define DS_QKV_PF 4
-#endif
-#ifndef DS_TWO_STREAM_MAX_PAIRS
-#define DS_TWO_STREAM_MAX_PAIRS 400000   // ds_forward: side stream for batches below this many pair rows (~2 500 molecules)
-#endif
-#ifndef DS_ATTN_FMA
-#define DS_ATTN_FMA 1
-#endif
-#ifndef DS_EQUI_T2
-#define DS_EQUI_T2 1   // k_equi_pairs: a MFMA wave runs its two feature chunks against shared X fragments
-#endif
-#ifndef DS_EQUI_NCW
-#define DS_EQUI_NCW 4   // MFMA waves of k_equi_pairs (each owns 8 / NCW feature chunks)
-#define DS_EQUI_NLW 4   // loader waves (each owns 32 / NLW pairs of a tile); 4 + 4 leaves both roles 256 registers
-#endif
+constexpr int DS_NODE_PF = 8;
+constexpr int DS_NODE_PF2 = 4;   // per ring when two chunks share the X fragments
+constexpr int DS_QKV_PF = 4;
+constexpr int DS_TWO_STREAM_MAX_PAIRS = 400000;   // ds_forward: side stream for batches below this many pair rows (~2 500 molecules)
 
 // Diagnostic build only (-DDS_STAMPS): per-phase shader-clock sums of wave 0 of every workgroup, accumulated into
 // registers and flushed once at kernel exit to the tail of ws.flags (64-bit counters at int32 index 16 + 2*phase).  Never compiled into the shipped library.
@@ -604,13 +589,9 @@ __global__ __launch_bounds__(1024) void k_attn_fused(Ctx c, int blk) {
               for (int j = 0; j < 3; ++j) { e[j] = t0[j0 + j]; xa[j] = qa[j0 + j]; xb[j] = qb[j0 + j]; ya[j] = ka[j0 + j]; yb[j] = kb[j0 + j]; }
 #pragma unroll
               for (int j = 0; j < 3; ++j) {
-#if DS_ATTN_FMA   // one multiply + one fused multiply-add per term (4-cycle issues) instead of the packed multiply + add the compiler forms (8 + 4)
+                // one multiply + one fused multiply-add per term (4-cycle issues) instead of the packed multiply + add the compiler forms (8 + 4)
                 s_ab = __builtin_fmaf(xb[j].x * ya[j].x, e[j].x, s_ab); s_ab = __builtin_fmaf(xb[j].y * ya[j].y, e[j].y, s_ab);
                 s_ba = __builtin_fmaf(xa[j].x * yb[j].x, e[j].x, s_ba); s_ba = __builtin_fmaf(xa[j].y * yb[j].y, e[j].y, s_ba);
-#else
-                s_ab += (xb[j].x * ya[j].x) * e[j].x; s_ab += (xb[j].y * ya[j].y) * e[j].y;
-                s_ba += (xa[j].x * yb[j].x) * e[j].x; s_ba += (xa[j].y * yb[j].y) * e[j].y;
-#endif
               }
             }
             out[2 + hs] = s_ab / 4.0f;        // / sqrt(out_channels = 16) (layers.py:167)
@@ -1249,14 +1230,17 @@ __global__ __launch_bounds__(256, 2) void k_edge_update(Ctx c, int blk) {
 // consumers waited for weights requested one k-block ahead - their weight stream now runs 4 k-blocks ahead per chunk through
 // register rings that are refilled for the next tile under the epilogue and the barrier.  4 + 4 waves: both roles need more
 // than the 168 registers a 12-wave workgroup leaves.
-template <int NCW, int NLW>
-__global__ __launch_bounds__((NCW + NLW) * 64) void k_equi_pairs(Ctx c, int blk) {
+constexpr int EQUI_NCW = 4;   // MFMA waves of k_equi_pairs (each owns 8 / NCW feature chunks)
+constexpr int EQUI_NLW = 4;   // loader waves (each owns 32 / NLW pairs of a tile); 4 + 4 leaves both roles 256 registers
+__global__ __launch_bounds__((EQUI_NCW + EQUI_NLW) * 64) void k_equi_pairs(Ctx c, int blk) {
   ds_fp16_saturate();
+  constexpr int NCW = EQUI_NCW, NLW = EQUI_NLW;
   constexpr int T = 64, TP = 32, LDH = 2 * 256 + 8, NCH = 8;
   constexpr int CPW = NCH / NCW;     // 32-feature chunks of the hidden layer per consumer wave
   constexpr int PPW = TP / NLW;      // pairs per loader wave and tile
   constexpr int NPASS = PPW / 2;     // LayerNorm passes (two pairs = four rows each)
   static_assert(NCH % NCW == 0 && TP % NLW == 0 && PPW % 2 == 0, "role split");
+  static_assert(CPW == 2, "a consumer wave runs its two feature chunks against shared X fragments");
   // X tile in the split-fp16 layout of ds_device.h (x = x1 + x2 / 2048): [buffer][row][plane 0 | plane 1 | pad].  A row's
   // 1040-byte slot first receives the fp32 `ed` row by LDS-DMA, then the split LayerNorm output.
   __shared__ __attribute__((aligned(16))) _Float16 Xh[2][T][LDH];      // 133,120 B
@@ -1320,16 +1304,14 @@ __global__ __launch_bounds__((NCW + NLW) * 64) void k_equi_pairs(Ctx c, int blk)
   if (consumer) {
     // The weights do not depend on anything the workgroup computes: their stream runs PF k-blocks ahead through a register
     // ring that is refilled for the next chunk as soon as a chunk's MFMAs are issued (ds_device.h, wave_mma_h_deep).
-    constexpr int PF = DS_EQUI_T2 ? 4 : 8;
+    constexpr int PF = 4;
     WStreamH wsh[CPW];
 #pragma unroll
     for (int cc = 0; cc < CPW; ++cc) wsh[cc] = wstream_h(BW(c, blk, DS_BW_CM0_H), 256, 256, (wave + NCW * cc) * 32);
     WRingH<PF> ring;
     wring_h<PF>(ring, wsh[0], 0);
-#if DS_EQUI_T2
     WRingH<PF> ringB;
-    wring_h<PF>(ringB, wsh[CPW - 1], 0);
-#endif
+    wring_h<PF>(ringB, wsh[1], 0);
     __syncthreads();
     DS_STAMP(0);
     int it = 0;
@@ -1387,8 +1369,7 @@ __global__ __launch_bounds__((NCW + NLW) * 64) void k_equi_pairs(Ctx c, int blk)
         o4.w = 0.0f;
         reinterpret_cast<float4*>(&part[buf][ch][lane][0])[0] = o4;
       };
-#if DS_EQUI_T2
-      if constexpr (CPW == 2) {   // both chunks of the wave against the same X fragments: half the LDS operand reads
+      {   // both chunks of the wave against the same X fragments: half the LDS operand reads
         f32x16 accA[2], loA[2], accB[2], loB[2];
         bias_init(wave, accA);
         bias_init(wave + NCW, accB);
@@ -1404,20 +1385,6 @@ __global__ __launch_bounds__((NCW + NLW) * 64) void k_equi_pairs(Ctx c, int blk)
         split_finish<2>(accB, loB);
         epilogue(wave + NCW, accB);
         DS_STAMP(11);
-      } else
-#endif
-      {
-#pragma unroll
-        for (int cc = 0; cc < CPW; ++cc) {
-          const int ch = wave + NCW * cc;
-          f32x16 acc1[2], acclo[2];
-          bias_init(ch, acc1);
-          acc_zero<2>(acclo);
-          wave_mma_h_deep<2, true, 16, PF>(&Xh[buf][0][0], 256, wsh[cc], ring, 0, acc1, acclo);
-          wring_h<PF>(ring, wsh[(cc + 1) % CPW], 0);   // the next chunk's (next tile's) first blocks fly under the epilogue and the barrier
-          split_finish<2>(acc1, acclo);
-          epilogue(ch, acc1);
-        }
       }
       if (wave == 0 && it > 0) tail(tile - stride, buf ^ 1, (it + 2) % 3);   // previous tile: its partial sums were complete one barrier ago
       DS_STAMP(1);
@@ -2280,30 +2247,32 @@ __global__ void k_layernorm_affine(const float* __restrict__ x, const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-bool make_ctx(Ctx& c, const ds_weights* w, const ds_layout* L, const ds_workspace* ws, hipStream_t s) {
-  if (!w || !L || !ws || !w->base) return false;
-  if (L->max_n > DS_MAX_ATOMS || L->B <= 0 || !w->off_dev) return false;
-  (void)s;
-  c.L = *L; c.ws = *ws; c.wbase = w->base;
-  c.woff = w->off_dev;
+bool make_ctx(Ctx& c, const ds_weights* w, const ds_layout* L, const ds_workspace* ws) {
+  if (!w || !L || !ws || !w->base || !w->off_dev) return false;
+  if (L->max_n > DS_MAX_ATOMS || L->B <= 0) return false;
+  c.L = *L; c.ws = *ws; c.wbase = w->base; c.woff = w->off_dev;
   c.edge_th = w->edge_th; c.cutoff = w->spatial_cut_off;
-  return c.woff != nullptr;
+  return true;
 }
 
-inline int launch_status() { return hipGetLastError() == hipSuccess ? DS_OK : DS_ERR_LAUNCH; }
+// What the entry points that take a bare layout require of it (their kernels stage <= 32 node indices of a molecule in LDS)
+inline bool layout_ok(const ds_layout* L) { return L && L->B > 0 && L->max_n <= DS_MAX_ATOMS && L->max_n <= L->N; }
+
+inline bool clear(void* p, size_t bytes, hipStream_t s) { return hipMemsetAsync(p, 0, bytes, s) == hipSuccess; }
+inline bool record(hipEvent_t ev, hipStream_t s) { return hipEventRecord(ev, s) == hipSuccess; }
+inline bool wait(hipStream_t s, hipEvent_t ev) { return hipStreamWaitEvent(s, ev, 0) == hipSuccess; }
+constexpr int MAX_DEVICES = 16;   // per-device host state (CU counts, side streams) is kept for devices below this index
 
 // Compute units of the current device (256 on a full MI355X; fewer in a partitioned mode): the persistent
-// k_equi_pairs launches exactly one workgroup per CU.
+// k_equi_pairs launches one workgroup per CU.  Remembered per device (256 if the query fails); two threads may both ask, which is harmless.
 inline int device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      cus = n;
-    else
-      cus = 256;
-  }
-  return cus;
+  static std::atomic<int> cus[MAX_DEVICES];
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return 256;
+  if ((n = cus[dev].load(std::memory_order_relaxed)) > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  cus[dev].store(n, std::memory_order_relaxed);
+  return n;
 }
 
 // Large plain GEMMs (the per-step adaLN table [B,1024] x [1024,19744] is 6 % of a denoising step): 128x128 output tile,
@@ -2385,26 +2354,13 @@ int gemm_dispatch(const GemmArgs& g, int act, hipStream_t s) {
   if (!g.A || !g.Wp || !g.C || g.M <= 0 || g.K <= 0 || g.N <= 0 || (g.cs && !g.csh)) return DS_ERR_ARG;
   const bool big = g.M >= 512 && g.a_grp_rows <= 0 && g.c_grp_rows <= 0 && g.K % 64 == 0 && g.lda % 4 == 0 &&
                    (reinterpret_cast<uintptr_t>(g.A) & 15) == 0;
-  if (big) {
-    dim3 gridb((g.M + 127) / 128, (g.Npad + 127) / 128);
-    switch (act) {
-      case 0: hipLaunchKernelGGL(k_gemm_big<0>, gridb, dim3(256), 0, s, g); break;
-      case 1: hipLaunchKernelGGL(k_gemm_big<1>, gridb, dim3(256), 0, s, g); break;
-      case 2: hipLaunchKernelGGL(k_gemm_big<2>, gridb, dim3(256), 0, s, g); break;
-      case 3: hipLaunchKernelGGL(k_gemm_big<3>, gridb, dim3(256), 0, s, g); break;
-      default: return DS_ERR_ARG;
-    }
-    return launch_status();
-  }
-  dim3 grid((g.M + 63) / 64, (g.Npad + 127) / 128);
-  switch (act) {
-    case 0: hipLaunchKernelGGL(k_gemm<0>, grid, dim3(256), 0, s, g); break;
-    case 1: hipLaunchKernelGGL(k_gemm<1>, grid, dim3(256), 0, s, g); break;
-    case 2: hipLaunchKernelGGL(k_gemm<2>, grid, dim3(256), 0, s, g); break;
-    case 3: hipLaunchKernelGGL(k_gemm<3>, grid, dim3(256), 0, s, g); break;
-    default: return DS_ERR_ARG;
-  }
-  return launch_status();
+  using Kernel = void (*)(GemmArgs);   // one instantiation per activation code: 128-row tiles when big, else 64-row tiles
+  static constexpr Kernel tile128[4] = {k_gemm_big<0>, k_gemm_big<1>, k_gemm_big<2>, k_gemm_big<3>};
+  static constexpr Kernel tile64[4] = {k_gemm<0>, k_gemm<1>, k_gemm<2>, k_gemm<3>};
+  if (act < 0 || act > 3) return DS_ERR_ARG;
+  const int rows = big ? 128 : 64;
+  hipLaunchKernelGGL(big ? tile128[act] : tile64[act], dim3((g.M + rows - 1) / rows, (g.Npad + 127) / 128), dim3(256), 0, s, g);
+  return DST_CHECK_LAUNCH();
 }
 
 int gemm_simple(const float* A, int64_t lda, const float* Wp, const float* bias, float* C, int64_t ldc, int M, int K, int N,
@@ -2416,8 +2372,9 @@ int gemm_simple(const float* A, int64_t lda, const float* Wp, const float* bias,
 }
 
 // ---- optional HIP-event timing of one block-stage kernel (bench.py's live roofline measurement) ----
+enum ProfSlot { PROF_EDGE_GEOM = 0, PROF_NODE_QKV = 1, PROF_ATTN = 2, PROF_NODE_UPDATE = 3, PROF_EDGE_UPDATE = 4, PROF_EQUI_PAIRS = 5 };   // the numbers are ABI (ds_profile_config)
 struct ProfState {
-  int kernel = -1;          // 0 edge_geom, 1 node_qkv, 2 attn_logits, 3 node_update, 4 edge_update, 5 equi_pairs, 6 attn_agg
+  int kernel = -1;          // a ProfSlot, or < 0: off
   int every = 1;
   long long seen = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
@@ -2438,6 +2395,39 @@ struct ProfScope {   // records start/stop events around one launch when samplin
     if (on) (void)hipEventRecord(g_prof.pool[g_prof.used++].second, s);
   }
 };
+
+// ---- the kernels of a block stage: the one launch site of each, which owns its grid, block size, profiling slot and - for the pair-row
+//      kernels - the "no pair rows, no launch" rule.  ds_stage_block and forward_blocks_two_streams are two orderings of these calls.
+void launch_edge_geom(const Ctx& c, int blk, hipStream_t s) {
+  if (c.L.Pp <= 0) return;
+  ProfScope ps(PROF_EDGE_GEOM, s);
+  hipLaunchKernelGGL(k_edge_geom, dim3((c.L.Pp + 63) / 64), dim3(256), 0, s, c, blk);
+}
+void launch_node_qkv(const Ctx& c, int blk, hipStream_t s) {
+  ProfScope ps(PROF_NODE_QKV, s);
+  hipLaunchKernelGGL(k_node_qkv<4>, dim3((c.L.Nn + 63) / 64, 2), dim3(256), 0, s, c, blk);
+}
+void launch_attn(const Ctx& c, int blk, hipStream_t s) {
+  ProfScope ps(PROF_ATTN, s);
+  hipLaunchKernelGGL(k_attn_fused, dim3(c.L.B), dim3(1024), 0, s, c, blk);
+}
+void launch_node_n2e(const Ctx& c, int blk, hipStream_t s) { hipLaunchKernelGGL(k_node_n2e, dim3((c.L.Nn + 63) / 64), dim3(256), 0, s, c, blk); }
+template <bool N2E>   // true: node2edge_lin inside the kernel; false: k_node_n2e has run
+void launch_node_update(const Ctx& c, int blk, hipStream_t s) {
+  ProfScope ps(PROF_NODE_UPDATE, s);
+  hipLaunchKernelGGL(k_node_update<N2E>, dim3((c.L.Nn + 31) / 32), dim3(256), 0, s, c, blk);
+}
+void launch_edge_update(const Ctx& c, int blk, hipStream_t s) {
+  if (c.L.Pp <= 0) return;
+  ProfScope ps(PROF_EDGE_UPDATE, s);
+  hipLaunchKernelGGL(k_edge_update, dim3((c.L.Pp + 127) / 128), dim3(256), 0, s, c, blk);
+}
+void launch_equi_pairs(const Ctx& c, int blk, hipStream_t s) {   // persistent: at most one workgroup per CU
+  if (c.L.Pp <= 0) return;
+  ProfScope ps(PROF_EQUI_PAIRS, s);
+  hipLaunchKernelGGL(k_equi_pairs, dim3(min((c.L.Pp + 31) / 32, device_cus())), dim3((EQUI_NCW + EQUI_NLW) * 64), 0, s, c, blk);
+}
+void launch_pos_update(const Ctx& c, int last, hipStream_t s) { hipLaunchKernelGGL(k_pos_update, dim3(c.L.B), dim3(64), 0, s, c, last); }
 
 }  // namespace
 
@@ -2467,14 +2457,14 @@ int ds_gemm_split(const void* A_split, const float* W_split, const float* bias, 
   if (!A_split || !W_split || !C || M <= 0 || K <= 0 || N <= 0 || K % 64 != 0 || N % 32 != 0 || ldc < N) return DS_ERR_ARG;
   hipLaunchKernelGGL(k_gemm_ada, dim3((M + 63) / 64, (N + 127) / 128), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const _Float16*>(A_split), W_split, bias, C, (int)ldc, M, K, N);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_stage_time(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* noise_level, const float* ctx_emb,
                   void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Ctx c;
-  if (!make_ctx(c, w, L, ws, s) || !noise_level) return DS_ERR_ARG;
+  if (!make_ctx(c, w, L, ws) || !noise_level) return DS_ERR_ARG;
   const int B = L->B;
   const int64_t* off = w->off + DS_NBLOCKS * DS_W_BLOCK_SLOTS;
   hipLaunchKernelGGL(k_time_feat, dim3((B + 63) / 64), dim3(64), 0, s, c, noise_level);
@@ -2488,49 +2478,45 @@ int ds_stage_time(const ds_weights* w, const ds_layout* L, ds_workspace* ws, con
   hipLaunchKernelGGL(k_temb_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, c, (const float*)tm3, B, ctx_emb);
   // every *time_mlp Linear of the model in one GEMM: [B,1024] x [1024, DS_ADA_COLS]
   static_assert(ADAC % 32 == 0, "adaLN table width");
-  hipLaunchKernelGGL(k_gemm_ada, dim3((B + 63) / 64, (ADAC + 127) / 128), dim3(256), 0, s, reinterpret_cast<const _Float16*>(ws->temb_silu),
-                     w->base + off[DS_GW_ADA_W], w->base + off[DS_GW_ADA_B], ws->ada, (int)ADAC, B, 1024, (int)ADAC);
-  return launch_status();
+  return ds_gemm_split(ws->temb_silu, w->base + off[DS_GW_ADA_W], w->base + off[DS_GW_ADA_B], ws->ada, ADAC, B, 1024, ADAC, stream);
 }
 
 int ds_stage_init(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* xh, const float* edge_x,
                   const float* cond_x, const float* cond_edge_x, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Ctx c;
-  if (!make_ctx(c, w, L, ws, s) || !xh || !edge_x || ((cond_x == nullptr) != (cond_edge_x == nullptr))) return DS_ERR_ARG;
-  if (hipMemsetAsync(ws->flags, 0, 8 * sizeof(int32_t), s) != hipSuccess) return DS_ERR_LAUNCH;
+  if (!make_ctx(c, w, L, ws) || !xh || !edge_x || ((cond_x == nullptr) != (cond_edge_x == nullptr))) return DS_ERR_ARG;
+  if (!clear(ws->flags, 8 * sizeof(int32_t), s)) return DS_ERR_LAUNCH;
   if (L->Pp > 0) hipLaunchKernelGGL(k_pair_flags, dim3((L->Pp + 1023) / 1024), dim3(1024), 0, s, c, cond_x, cond_edge_x);
   hipLaunchKernelGGL(k_node_init, dim3((L->Nn + 7) / 8), dim3(256), 0, s, c, xh, cond_x);
   if (L->Pp > 0) hipLaunchKernelGGL(k_pair_init, dim3((L->Pp + 63) / 64), dim3(256), 0, s, c, edge_x, cond_x, cond_edge_x);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_stage_block(const ds_weights* w, const ds_layout* L, ds_workspace* ws, int blk, int last, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Ctx c;
-  if (!make_ctx(c, w, L, ws, s) || blk < 0 || blk >= DS_NBLOCKS) return DS_ERR_ARG;
-  const int pt = (L->Pp + 63) / 64, nt = (L->Nn + 31) / 32;
-  if (pt > 0) { ProfScope ps(0, s); hipLaunchKernelGGL(k_edge_geom, dim3(pt), dim3(256), 0, s, c, blk); }
-  { ProfScope ps(1, s); hipLaunchKernelGGL(k_node_qkv<4>, dim3((L->Nn + 63) / 64, 2), dim3(256), 0, s, c, blk); }
-  { ProfScope ps(2, s); hipLaunchKernelGGL(k_attn_fused, dim3(L->B), dim3(1024), 0, s, c, blk); }
-  { ProfScope ps(3, s); hipLaunchKernelGGL(k_node_update<true>, dim3(nt), dim3(256), 0, s, c, blk); }
-  if (pt > 0) { ProfScope ps(4, s); hipLaunchKernelGGL(k_edge_update, dim3((L->Pp + 127) / 128), dim3(256), 0, s, c, blk); }
-  if (pt > 0) { ProfScope ps(5, s); { const int nt_ = (L->Pp + 31) / 32, cu_ = device_cus(); hipLaunchKernelGGL((k_equi_pairs<DS_EQUI_NCW, DS_EQUI_NLW>), dim3(nt_ < cu_ ? nt_ : cu_), dim3((DS_EQUI_NCW + DS_EQUI_NLW) * 64), 0, s, c, blk); } }
-  hipLaunchKernelGGL(k_pos_update, dim3(L->B), dim3(64), 0, s, c, last);
-  return launch_status();
+  if (!make_ctx(c, w, L, ws) || blk < 0 || blk >= DS_NBLOCKS) return DS_ERR_ARG;
+  launch_edge_geom(c, blk, s);
+  launch_node_qkv(c, blk, s);
+  launch_attn(c, blk, s);
+  launch_node_update<true>(c, blk, s);
+  launch_edge_update(c, blk, s);
+  launch_equi_pairs(c, blk, s);
+  launch_pos_update(c, last, s);
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_stage_readout(const ds_weights* w, const ds_layout* L, ds_workspace* ws, float* out_xh, float* out_edge, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Ctx c;
-  if (!make_ctx(c, w, L, ws, s) || !out_xh || !out_edge) return DS_ERR_ARG;
+  if (!make_ctx(c, w, L, ws) || !out_xh || !out_edge) return DS_ERR_ARG;
   const size_t nx = (size_t)L->B * L->N * 9, ne = (size_t)L->B * L->N * L->N * 2;
-  if (hipMemsetAsync(out_xh, 0, nx * sizeof(float), s) != hipSuccess) return DS_ERR_LAUNCH;
-  if (hipMemsetAsync(out_edge, 0, ne * sizeof(float), s) != hipSuccess) return DS_ERR_LAUNCH;
+  if (!clear(out_xh, nx * sizeof(float), s) || !clear(out_edge, ne * sizeof(float), s)) return DS_ERR_LAUNCH;
   hipLaunchKernelGGL(k_node_readout, dim3((L->Nn + 31) / 32), dim3(256), 0, s, c, out_xh);
   if (L->Pp > 0) hipLaunchKernelGGL(k_edge_readout, dim3((L->Pp + 127) / 128), dim3(256), 0, s, c, out_edge);
   hipLaunchKernelGGL(k_final_pos, dim3((L->B + 63) / 64), dim3(64), 0, s, c, out_xh);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 // The blocks of one forward over TWO streams (ds_forward).  A block's node rows after the attention - gated residual, FF, read-out
@@ -2546,54 +2532,50 @@ int ds_stage_readout(const ds_weights* w, const ds_layout* L, ds_workspace* ws, 
 struct SideStream {
   hipStream_t s = nullptr;
   hipEvent_t fork[DS_NBLOCKS + 1] = {}, join[DS_NBLOCKS + 1] = {};
-  bool ok = false, tried = false;
+  std::once_flag once;   // the first ds_forward on a device creates its side stream, whichever thread it comes from
+  bool ok = false;
 };
-static SideStream g_side[16];
+static SideStream g_side[MAX_DEVICES];
 static int g_two_stream = -1;   // -1: from the environment (DIFFSPECTRA_TWO_STREAM), else by batch size
 
 static SideStream* side_stream() {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return nullptr;
   SideStream& ss = g_side[dev];
-  if (!ss.tried) {
-    ss.tried = true;
+  std::call_once(ss.once, [&ss] {
     bool ok = hipStreamCreateWithFlags(&ss.s, hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; ok && i <= DS_NBLOCKS; ++i)
       ok = hipEventCreateWithFlags(&ss.fork[i], hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&ss.join[i], hipEventDisableTiming) == hipSuccess;
     ss.ok = ok;
-  }
+  });
   return ss.ok ? &ss : nullptr;
 }
 
 static int forward_blocks_two_streams(const ds_weights* w, const ds_layout* L, ds_workspace* ws, hipStream_t s, SideStream* ss) {
   Ctx c;
-  if (!make_ctx(c, w, L, ws, s)) return DS_ERR_ARG;
-  const int pt = (L->Pp + 63) / 64, nt = (L->Nn + 31) / 32;
+  if (!make_ctx(c, w, L, ws)) return DS_ERR_ARG;
   hipStream_t s2 = ss->s;
-#define DS_HIP_OK(x) do { if ((x) != hipSuccess) return DS_ERR_LAUNCH; } while (0)
+  const hipEvent_t fork0 = ss->fork[DS_NBLOCKS], join0 = ss->join[DS_NBLOCKS];
   // q|k|v of block 0 on the side stream, beside edge_geom(0)
-  DS_HIP_OK(hipEventRecord(ss->fork[DS_NBLOCKS], s));
-  DS_HIP_OK(hipStreamWaitEvent(s2, ss->fork[DS_NBLOCKS], 0));
-  { ProfScope ps(1, s2); hipLaunchKernelGGL(k_node_qkv<4>, dim3((L->Nn + 63) / 64, 2), dim3(256), 0, s2, c, 0); }
-  DS_HIP_OK(hipEventRecord(ss->join[DS_NBLOCKS], s2));
+  if (!record(fork0, s) || !wait(s2, fork0)) return DS_ERR_LAUNCH;
+  launch_node_qkv(c, 0, s2);
+  if (!record(join0, s2)) return DS_ERR_LAUNCH;
   for (int blk = 0; blk < DS_NBLOCKS; ++blk) {
-    if (pt > 0) { ProfScope ps(0, s); hipLaunchKernelGGL(k_edge_geom, dim3(pt), dim3(256), 0, s, c, blk); }
-    DS_HIP_OK(hipStreamWaitEvent(s, blk == 0 ? ss->join[DS_NBLOCKS] : ss->join[blk - 1], 0));     // q|k|v(blk)
-    { ProfScope ps(2, s); hipLaunchKernelGGL(k_attn_fused, dim3(L->B), dim3(1024), 0, s, c, blk); }
-    hipLaunchKernelGGL(k_node_n2e, dim3((L->Nn + 63) / 64), dim3(256), 0, s, c, blk);
-    DS_HIP_OK(hipEventRecord(ss->fork[blk], s));
-    DS_HIP_OK(hipStreamWaitEvent(s2, ss->fork[blk], 0));
-    { ProfScope ps(3, s2); hipLaunchKernelGGL(k_node_update<false>, dim3(nt), dim3(256), 0, s2, c, blk); }
-    if (blk + 1 < DS_NBLOCKS) { ProfScope ps(1, s2); hipLaunchKernelGGL(k_node_qkv<4>, dim3((L->Nn + 63) / 64, 2), dim3(256), 0, s2, c, blk + 1); }
-    DS_HIP_OK(hipEventRecord(ss->join[blk], s2));
-    if (pt > 0) { ProfScope ps(4, s); hipLaunchKernelGGL(k_edge_update, dim3((L->Pp + 127) / 128), dim3(256), 0, s, c, blk); }
-    DS_HIP_OK(hipStreamWaitEvent(s, ss->join[blk], 0));                                           // ac, h, atom_hids, q|k|v(blk + 1)
-    if (pt > 0) { ProfScope ps(5, s); { const int nt_ = (L->Pp + 31) / 32, cu_ = device_cus(); hipLaunchKernelGGL((k_equi_pairs<DS_EQUI_NCW, DS_EQUI_NLW>), dim3(nt_ < cu_ ? nt_ : cu_), dim3((DS_EQUI_NCW + DS_EQUI_NLW) * 64), 0, s, c, blk); } }
-    hipLaunchKernelGGL(k_pos_update, dim3(L->B), dim3(64), 0, s, c, blk == DS_NBLOCKS - 1 ? 1 : 0);
+    launch_edge_geom(c, blk, s);
+    if (!wait(s, blk == 0 ? join0 : ss->join[blk - 1])) return DS_ERR_LAUNCH;     // q|k|v(blk)
+    launch_attn(c, blk, s);
+    launch_node_n2e(c, blk, s);
+    if (!record(ss->fork[blk], s) || !wait(s2, ss->fork[blk])) return DS_ERR_LAUNCH;
+    launch_node_update<false>(c, blk, s2);
+    if (blk + 1 < DS_NBLOCKS) launch_node_qkv(c, blk + 1, s2);
+    if (!record(ss->join[blk], s2)) return DS_ERR_LAUNCH;
+    launch_edge_update(c, blk, s);
+    if (!wait(s, ss->join[blk])) return DS_ERR_LAUNCH;                            // ac, h, atom_hids, q|k|v(blk + 1)
+    launch_equi_pairs(c, blk, s);
+    launch_pos_update(c, blk == DS_NBLOCKS - 1 ? 1 : 0, s);
   }
-#undef DS_HIP_OK
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_set_two_stream(int on) {   // -1: follow DIFFSPECTRA_TWO_STREAM (default on); 0 / 1: force.  Returns the previous setting.
@@ -2631,75 +2613,67 @@ int ds_forward(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const 
 int ds_sampler_step(const ds_layout* L, float c_x, float c_pred, float sigma, float temperature, float* x, float* edge_x,
                      const float* pred, const float* edge_pred, const float* raw_pos, const float* raw_feat,
                      const float* raw_edge, float* x_mean, float* edge_mean, void* stream) {
-  if (!L || !x || !edge_x || !pred || !edge_pred || !raw_pos || !raw_feat || !raw_edge || !x_mean || !edge_mean) return DS_ERR_ARG;
-  if (L->B <= 0 || L->max_n > DS_MAX_ATOMS || L->max_n > L->N) return DS_ERR_ARG;   // k_sampler_step stages <= 32 node indices in LDS
+  if (!layout_ok(L) || !x || !edge_x || !pred || !edge_pred || !raw_pos || !raw_feat || !raw_edge || !x_mean || !edge_mean) return DS_ERR_ARG;
   hipLaunchKernelGGL(k_sampler_step, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, c_x, c_pred, sigma, temperature, x,
                      edge_x, pred, edge_pred, raw_pos, raw_feat, raw_edge, x_mean, edge_mean);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_initial_noise(const ds_layout* L, uint64_t seed, const int64_t* mol_id, float* x, float* edge_x, void* stream) {
-  if (!L || !mol_id || !x || !edge_x) return DS_ERR_ARG;
-  if (L->B <= 0 || L->max_n > DS_MAX_ATOMS || L->max_n > L->N) return DS_ERR_ARG;
+  if (!layout_ok(L) || !mol_id || !x || !edge_x) return DS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const size_t nb = (size_t)L->B * L->N;
-  if (hipMemsetAsync(x, 0, nb * 9 * sizeof(float), s) != hipSuccess) return DS_ERR_LAUNCH;
-  if (hipMemsetAsync(edge_x, 0, nb * L->N * 2 * sizeof(float), s) != hipSuccess) return DS_ERR_LAUNCH;
+  if (!clear(x, nb * 9 * sizeof(float), s) || !clear(edge_x, nb * L->N * 2 * sizeof(float), s)) return DS_ERR_LAUNCH;
   hipLaunchKernelGGL(k_noise_step<0>, dim3(L->B), dim3(256), 0, s, *L, 0.0f, 0.0f, 0.0f, 0.0f, (unsigned long long)seed, 0u, mol_id,
                      x, edge_x, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr,
                      (const float*)nullptr, (const int32_t*)nullptr);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_sampler_step_philox(const ds_layout* L, float c_x, float c_pred, float sigma, float temperature, uint64_t seed, int32_t step,
                            const int64_t* mol_id, float* x, float* edge_x, const float* pred, const float* edge_pred,
                            float* x_mean, float* edge_mean, void* stream) {
-  if (!L || !mol_id || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean || step < 0) return DS_ERR_ARG;
-  if (L->B <= 0 || L->max_n > DS_MAX_ATOMS || L->max_n > L->N) return DS_ERR_ARG;
+  if (!layout_ok(L) || !mol_id || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean || step < 0) return DS_ERR_ARG;
   hipLaunchKernelGGL(k_noise_step<1>, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, c_x, c_pred, sigma, temperature,
                      (unsigned long long)seed, (unsigned int)step + 1u, mol_id, x, edge_x, pred, edge_pred, x_mean, edge_mean,
                      (const float*)nullptr, (const int32_t*)nullptr);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_step_begin(const float* table, int32_t n_steps, int32_t* step, int32_t B, float* noise_level, void* stream) {
   if (!table || !step || !noise_level || B <= 0 || n_steps <= 0) return DS_ERR_ARG;
   hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(256), 0, (hipStream_t)stream, table, n_steps, step, B, noise_level);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_sampler_step_philox_dev(const ds_layout* L, const float* table, const int32_t* step, float temperature, uint64_t seed,
                                const int64_t* mol_id, float* x, float* edge_x, const float* pred, const float* edge_pred,
                                float* x_mean, float* edge_mean, void* stream) {
-  if (!L || !table || !step || !mol_id || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean) return DS_ERR_ARG;
-  if (L->B <= 0 || L->max_n > DS_MAX_ATOMS || L->max_n > L->N) return DS_ERR_ARG;
+  if (!layout_ok(L) || !table || !step || !mol_id || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean) return DS_ERR_ARG;
   hipLaunchKernelGGL(k_noise_step<2>, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, 0.0f, 0.0f, 0.0f, temperature,
                      (unsigned long long)seed, 0u, mol_id, x, edge_x, pred, edge_pred, x_mean, edge_mean, table, step);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_post_process(const ds_layout* L, const float* xh, const float* edge_x, float* pos_out, int32_t* atom_type, int32_t* fc,
                     float* edge_type, void* stream) {
-  if (!L || !xh || !edge_x || !pos_out || !atom_type || !fc || !edge_type) return DS_ERR_ARG;
-  if (L->B <= 0 || L->max_n > DS_MAX_ATOMS || L->max_n > L->N) return DS_ERR_ARG;
+  if (!layout_ok(L) || !xh || !edge_x || !pos_out || !atom_type || !fc || !edge_type) return DS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const size_t nb = (size_t)L->B * L->N;
-  if (hipMemsetAsync(pos_out, 0, nb * 3 * sizeof(float), s) != hipSuccess) return DS_ERR_LAUNCH;
-  if (hipMemsetAsync(atom_type, 0, nb * sizeof(int32_t), s) != hipSuccess) return DS_ERR_LAUNCH;
-  if (hipMemsetAsync(fc, 0, nb * sizeof(int32_t), s) != hipSuccess) return DS_ERR_LAUNCH;
-  if (hipMemsetAsync(edge_type, 0, nb * L->N * sizeof(float), s) != hipSuccess) return DS_ERR_LAUNCH;
+  if (!clear(pos_out, nb * 3 * sizeof(float), s) || !clear(atom_type, nb * sizeof(int32_t), s) || !clear(fc, nb * sizeof(int32_t), s) ||
+      !clear(edge_type, nb * L->N * sizeof(float), s))
+    return DS_ERR_LAUNCH;
   hipLaunchKernelGGL(k_post_process, dim3(L->B), dim3(128), 0, s, *L, xh, edge_x, pos_out, atom_type, fc, edge_type);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_check_stability(const ds_layout* L, const float* pos, const int32_t* atom_type, int32_t* bond_order, int32_t* nr_stable,
                        int32_t* mol_stable, void* stream) {
-  if (!L || !pos || !atom_type || !nr_stable || !mol_stable) return DS_ERR_ARG;
-  if (L->B <= 0 || L->max_n > DS_MAX_ATOMS || L->max_n > L->N) return DS_ERR_ARG;
+  if (!layout_ok(L) || !pos || !atom_type || !nr_stable || !mol_stable) return DS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  if (bond_order && hipMemsetAsync(bond_order, 0, (size_t)L->B * L->N * L->N * sizeof(int32_t), s) != hipSuccess) return DS_ERR_LAUNCH;
+  if (bond_order && !clear(bond_order, (size_t)L->B * L->N * L->N * sizeof(int32_t), s)) return DS_ERR_LAUNCH;
   hipLaunchKernelGGL(k_check_stability, dim3(L->B), dim3(64), 0, s, *L, pos, atom_type, bond_order, nr_stable, mol_stable);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_spec_attention(const float* qkv, float* scores, float* out, int B, int L, int heads, int dk, float scale, int has_prev,
@@ -2709,7 +2683,7 @@ int ds_spec_attention(const float* qkv, float* scores, float* out, int B, int L,
   dim3 grid((L + threads - 1) / threads, heads, B);
   hipLaunchKernelGGL(k_spec_attention, grid, dim3(threads), (size_t)L * 8 * 2 * sizeof(float), (hipStream_t)stream, qkv, scores, out, B,
                      L, heads, scale, has_prev);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 int ds_profile_config(int kernel, int every, int max_samples) {
@@ -2743,7 +2717,7 @@ int ds_layernorm_affine(const float* x, const float* gamma, const float* beta, f
                         void* stream) {
   if (!x || !gamma || !beta || !y || rows <= 0 || cols <= 0) return DS_ERR_ARG;
   hipLaunchKernelGGL(k_layernorm_affine, dim3(rows), dim3(64), 0, (hipStream_t)stream, x, gamma, beta, y, rows, cols, eps);
-  return launch_status();
+  return DST_CHECK_LAUNCH();
 }
 
 }  // extern "C"

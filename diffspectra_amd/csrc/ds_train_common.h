@@ -1,4 +1,5 @@
-// diffspectra_amd - small helpers shared by the training sources (ds_train*.hip): device math, and the host side of a launch.
+// diffspectra_amd - small helpers shared by the training sources (ds_train*.hip): device math, and the host side of a launch
+// (DST_CHECK_LAUNCH is the whole library's launch-status rule: ds_kernels.hip includes this header for it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -10,85 +10,32 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import re
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_PKG)
-LIB_PATH = os.environ.get("DIFFSPECTRA_HIP_LIB", os.path.join(_PKG, "libdiffspectra_hip.so"))
-HEADER_PATH = os.path.join(_ROOT, "include", "diffspectra_hip.h")
+from . import abi
 
-_c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
+LIB_PATH = os.environ.get("DIFFSPECTRA_HIP_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdiffspectra_hip.so"))
 
-
-def _parse_header():
-    txt = open(HEADER_PATH).read()
-    txt_nc = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-
-    def enum_names(name):
-        body = re.search(r"enum\s+%s\s*\{(.*?)\}" % name, txt_nc, flags=re.S).group(1)
-        return [t.split("=")[0].strip() for t in body.split(",") if t.strip()]
-
-    defs = {}
-    for m in re.finditer(r"#define\s+(DS_\w+)\s+(\(?[-\w\s\*\+\(\)]+?\)?)\s*$", txt_nc, flags=re.M):
-        defs[m.group(1)] = m.group(2)
-    consts: Dict[str, int] = {}
-    for _ in range(4):  # resolve nested defines
-        for k, v in defs.items():
-            if k in consts:
-                continue
-            try:
-                consts[k] = int(eval(v, {"__builtins__": {}}, consts))
-            except Exception:
-                pass
-    blk = enum_names("ds_block_slot")
-    glb = enum_names("ds_global_slot")
-    exports = re.findall(r"^\s*(?:int|void)\s+(ds_\w+)\s*\(", txt_nc, flags=re.M)
-    return consts, blk, glb, exports
-
-
-CONSTS, BLOCK_SLOTS, GLOBAL_SLOTS, EXPORTS = _parse_header()
+# constants, weight slots, entry points and argument structs as include/diffspectra_hip.h declares them (abi.py reads it)
+_HDR = abi.SAMPLING
+HEADER_PATH = _HDR.path
+CONSTS = _HDR.consts
+BLOCK_SLOTS, GLOBAL_SLOTS = _HDR.enums["ds_block_slot"], _HDR.enums["ds_global_slot"]      # the last enumerator of each is its count
+EXPORTS = _HDR.exports("ds_")
 NB = CONSTS["DS_NBLOCKS"]
-W_BLOCK_SLOTS = len(BLOCK_SLOTS) - 1      # last enumerator is the count
-W_GLOBAL_SLOTS = len(GLOBAL_SLOTS) - 1
-W_NUM_SLOTS = NB * W_BLOCK_SLOTS + W_GLOBAL_SLOTS
+W_BLOCK_SLOTS, W_GLOBAL_SLOTS, W_NUM_SLOTS = CONSTS["DS_W_BLOCK_SLOTS"], CONSTS["DS_W_GLOBAL_SLOTS"], CONSTS["DS_W_NUM_SLOTS"]
 ADA_COLS = CONSTS["DS_ADA_COLS"]
 ADA_STRIDE = CONSTS["DS_ADA_BLOCK_STRIDE"]
 MAX_ATOMS = CONSTS["DS_MAX_ATOMS"]
 
-
-class DsWeights(C.Structure):
-    _fields_ = [("base", C.c_void_p), ("off_dev", C.c_void_p), ("off", C.c_int64 * W_NUM_SLOTS),
-                ("edge_th", C.c_float), ("spatial_cut_off", C.c_float)]
-
-
-class DsLayout(C.Structure):
-    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("Nn", C.c_int32), ("Pp", C.c_int32),
-                ("max_n", C.c_int32), ("_pad", C.c_int32),
-                ("node_off", C.c_void_p), ("pair_off", C.c_void_p), ("node_dense", C.c_void_p),
-                ("node_mol", C.c_void_p), ("pair_a", C.c_void_p), ("pair_b", C.c_void_p), ("pair_mol", C.c_void_p),
-                ("mol_by_size", C.c_void_p)]
-
-
-_WS_FIELDS = ["pos", "h", "e", "atom_hids", "edge_hids", "tfeat", "tmid", "temb_silu", "ada", "qkv", "ye",
-              "dist", "attn", "u", "ac", "ed", "lg", "tr", "adj", "flags"]
-
-
-class DsWorkspace(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in _WS_FIELDS]
-
-
-class DsGemmArgs(C.Structure):
-    _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("a_grp_rows", C.c_int32), ("_p0", C.c_int32),
-                ("a_grp_stride", C.c_int64), ("Wp", C.c_void_p), ("bias", C.c_void_p),
-                ("C", C.c_void_p), ("ldc", C.c_int64), ("c_grp_rows", C.c_int32), ("_p1", C.c_int32),
-                ("c_grp_stride", C.c_int64), ("M", C.c_int32), ("K", C.c_int32), ("N", C.c_int32), ("act", C.c_int32),
-                ("R", C.c_void_p), ("ldr", C.c_int64), ("r_grp_rows", C.c_int32), ("a_silu", C.c_int32),
-                ("col_scale", C.c_void_p), ("col_shift", C.c_void_p)]
-
+DsWeights = _HDR.ctypes_struct("ds_weights")
+DsLayout = _HDR.ctypes_struct("ds_layout")
+DsWorkspace = _HDR.ctypes_struct("ds_workspace")
+DsGemmArgs = _HDR.ctypes_struct("ds_gemm_args")
+_WS_FIELDS = [f for f, _ in _HDR.structs["ds_workspace"]]
 
 _lib = None
 
@@ -104,7 +51,7 @@ def load_library() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
-    mine = [C.sizeof(DsWeights), C.sizeof(DsLayout), C.sizeof(DsWorkspace), C.sizeof(DsGemmArgs)]
+    mine = [C.sizeof(t) for t in (DsWeights, DsLayout, DsWorkspace, DsGemmArgs)]
     if list(sizes) != mine:
         raise RuntimeError(f"C-ABI struct layout mismatch: library {list(sizes)} vs binding {mine}")
     for name in EXPORTS:
@@ -426,7 +373,9 @@ class Workspace:
                       ed=f(Pp, 256), lg=f(Pp, 32), tr=f(Pp, 8),
                       adj=torch.zeros(Pp, dtype=torch.int32, device=device),
                       flags=torch.zeros(64, dtype=torch.int32, device=device))
-        self.c = DsWorkspace(**{k: self.t[k].data_ptr() for k in _WS_FIELDS})
+        # a buffer is added in the header AND here: one without the other fails now instead of leaving a NULL pointer in the struct
+        assert list(self.t) == _WS_FIELDS, (list(self.t), _WS_FIELDS)
+        self.c = DsWorkspace(**{k: v.data_ptr() for k, v in self.t.items()})
 
 
 # ----------------------------------------------------------------------------------------- engine

@@ -16,16 +16,13 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-import re
-import struct as _struct
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import engine as E
+from . import abi, engine as E
 
-TRAIN_HEADER = os.path.join(E._ROOT, "include", "diffspectra_train.h")
 ADA, ADA_STRIDE, ADA_TOP = E.ADA_COLS, E.ADA_STRIDE, E.CONSTS["DS_ADA_TOP"]
 NODE_OFF, EDGE_OFF, EQUI_OFF, DIST_OFF = (E.CONSTS[k] for k in ("DS_ADA_NODE", "DS_ADA_EDGE", "DS_ADA_EQUI", "DS_ADA_DIST"))
 NB = E.NB
@@ -34,48 +31,24 @@ ADDREF = 4                 # dst_gemm `dact` code: the epilogue adds ref (a resi
 DW_STREAMS = 2             # weight-gradient streams (1: 19.2 ms per step, 2: 17.9, 3: 18.2; profiles/r05_train_ab_final.txt)
 
 
-# ---- the argument structs of the C-ABI, read from include/diffspectra_train.h (the one description of their layouts; the library reports
-#      its sizes, load_train_library compares)
-_FIELD_CODES = {"int64_t": "q", "int32_t": "i", "uint32_t": "I", "uint64_t": "Q", "float": "f"}
-_CTYPES = {"P": C.c_void_p, "q": C.c_int64, "i": C.c_int32, "I": C.c_uint32, "Q": C.c_uint64, "f": C.c_float}
+# ---- the argument structs of the C-ABI, read from include/diffspectra_train.h by abi.py (the one description of their layouts; the library
+#      reports its sizes, load_train_library compares)
 # the order in which dst_struct_sizes reports them
 STRUCT_NAMES = ("dst_gemm_args", "dst_layout", "dst_piece", "dst_pair_chain_args", "dst_pair_front_args", "dst_dir_chain_args",
                 "dst_node_chain_args", "dst_dir_bwd_args", "dst_pair_bwd_args", "dst_node_bwd_args")
 
 
-def _header_text() -> str:
-    """The training header without its comments."""
-    with open(TRAIN_HEADER) as f:
-        return re.sub(r"/\*.*?\*/|//[^\n]*", "", f.read(), flags=re.S)
-
-
 def train_exports() -> List[str]:
-    return re.findall(r"^\s*int\s+(dst_\w+)\s*\(", _header_text(), flags=re.M)
+    return abi.TRAINING.exports("dst_")
 
 
 def header_structs() -> Dict[str, List[Tuple[str, str]]]:
-    """``{struct name: [(field, struct code)]}`` of every ``typedef struct dst_* { ... }`` of the header: any pointer is ``P``, scalars map
-    through ``_FIELD_CODES``; a declaration may list several fields (``int32_t a, b;``, ``float *x, *y;``)."""
-    txt = _header_text()
-    out = {}
-    for name, body in re.findall(r"typedef\s+struct\s+(dst_\w+)\s*\{(.*?)\}", txt, flags=re.S):
-        fields = []
-        for decl in filter(None, (d.strip() for d in body.split(";"))):
-            typ, rest = re.fullmatch(r"(?:const\s+)?(\w+)\s*(.*)", decl, flags=re.S).groups()
-            for f_ in rest.split(","):
-                f_ = f_.strip()
-                fields.append((f_.lstrip("* "), "P" if f_.startswith("*") else _FIELD_CODES[typ]))
-        out[name] = fields
-    return out
+    """``{struct name: [(field, struct code)]}`` of every ``typedef struct dst_* { ... }`` of the header."""
+    return abi.TRAINING.structs
 
 
-def _native_format(fields) -> str:
-    return "@" + "".join(code for _, code in fields)          # native alignment: the C compiler's layout
-
-
-_FIELDS = header_structs()
 # Call sites pack positionally: keyword packing or a ctypes Structure built field by field costs ~10 us per call, and a step makes ~600 products
-STRUCTS = {n: _struct.Struct(_native_format(fl)) for n, fl in _FIELDS.items()}
+STRUCTS = {n: abi.TRAINING.packer(n) for n in header_structs()}
 _GEMM_PACK = STRUCTS["dst_gemm_args"].pack
 _CHAIN_PACK = STRUCTS["dst_pair_chain_args"].pack
 _FRONT_PACK = STRUCTS["dst_pair_front_args"].pack
@@ -86,12 +59,8 @@ _PAIRB_PACK = STRUCTS["dst_pair_bwd_args"].pack
 _NODEB_PACK = STRUCTS["dst_node_bwd_args"].pack
 
 
-def _ctypes_struct(name: str):
-    return type(name, (C.Structure,), {"_fields_": [(f_, _CTYPES[code]) for f_, code in _FIELDS[name]]})
-
-
-DstPiece = _ctypes_struct("dst_piece")
-DstLayout = _ctypes_struct("dst_layout")
+DstPiece = abi.TRAINING.ctypes_struct("dst_piece")
+DstLayout = abi.TRAINING.ctypes_struct("dst_layout")
 
 
 def copy_pieces(lib, dev, dst: List[torch.Tensor], src: List[torch.Tensor], cache: dict, key: str, stream=None):

@@ -5,8 +5,10 @@
  * convention of SURVEY §8b.  This library is what a binding for that path attaches to: plain device
  * pointers + sizes + a hipStream_t, no torch types, int status returns (0 = ok, <0 = error; the
  * Python mirror turns them into RuntimeError).  All buffers are caller-owned device memory
- * (PyTorch-ROCm allocations in the shipped host code).  No hidden global state: weights are a
- * caller-owned packed buffer described by ds_weights.
+ * (PyTorch-ROCm allocations in the shipped host code); weights are a caller-owned packed buffer
+ * described by ds_weights.  The library's own state is process-global and never changes a result:
+ * the stream-mode switch (ds_set_two_stream), one side stream with its events per device
+ * (ds_forward), the compute-unit count per device, and the timing hook (ds_profile_config).
  *
  * Reference interfaces replaced (file:line in /root/reference):
  *   ds_forward            DMT.forward                         models/dmt.py:306-412
@@ -186,7 +188,9 @@ int ds_gemm_split(const void* A_split, const float* W_split, const float* bias, 
 
 /* One DMT evaluation (dmt.py:306-412).  xh [B,N,9], edge_x [B,N,N,2] dense; cond_x/cond_edge_x may be NULL
  * (first step, dmt.py:332-335); noise_level [B]; ctx_emb [B,1024] = cond_lin(SpecFormer(context)) (dmt.py:348-350),
- * NULL means zero context embedding.  out_xh [B,N,9], out_edge [B,N,N,2] are fully written (masked entries 0). */
+ * NULL means zero context embedding.  out_xh [B,N,9], out_edge [B,N,N,2] are fully written (masked entries 0).
+ * The side stream of the two-stream mode (ds_set_two_stream) and its events exist once per device, whatever `stream` is: any number of
+ * host threads may run ds_forward on different devices, two must not run it on the same device at the same time. */
 int ds_forward(const ds_weights* w, const ds_layout* L, ds_workspace* ws,
                const float* xh, const float* edge_x, const float* cond_x, const float* cond_edge_x,
                const float* noise_level, const float* ctx_emb,

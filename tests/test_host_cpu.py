@@ -53,6 +53,33 @@ def test_training_structs_parsed_from_the_header():
     assert ctypes.sizeof(T.DstLayout) == T.STRUCTS["dst_layout"].size and ctypes.sizeof(T.DstPiece) == T.STRUCTS["dst_piece"].size
 
 
+def test_sampling_structs_parsed_from_the_header():
+    """The sampling C-ABI's four argument structs are built from include/diffspectra_hip.h: pinned, field by field, to the layouts the
+    kernels were validated with - a reordered header keeps every sizeof and would swap buffers silently."""
+    from diffspectra_amd import abi
+    assert (E.W_BLOCK_SLOTS, E.W_GLOBAL_SLOTS, E.W_NUM_SLOTS, E.NB) == (43, 38, 382, 8)
+    assert len(E.BLOCK_SLOTS) == 44 and E.BLOCK_SLOTS[0] == "DS_BW_EDGE_EMB_W" and E.BLOCK_SLOTS[-2:] == ["DS_BW_EDGE_EMB_H", "DS_W_BLOCK_SLOTS"]
+    assert len(E.GLOBAL_SLOTS) == 39 and E.GLOBAL_SLOTS[0] == "DS_GW_SIN_W" and E.GLOBAL_SLOTS[-2:] == ["DS_GW_ET2_C", "DS_W_GLOBAL_SLOTS"]
+    expected = {
+        "ds_weights": "@PP 382q ff",
+        "ds_layout": "@iiiiii PPPPPPPP",
+        "ds_workspace": "@" + 20 * "P",
+        "ds_gemm_args": "@Pqiiq PP Pqiiq iiii Pqii PP",
+    }
+    assert {n: abi.SAMPLING.packer(n).format for n in abi.SAMPLING.structs} == {n: f.replace(" ", "") for n, f in expected.items()}
+    names = lambda t: [f[0] for f in t._fields_]
+    assert names(E.DsWeights) == ["base", "off_dev", "off", "edge_th", "spatial_cut_off"]
+    assert names(E.DsLayout) == ["B", "N", "Nn", "Pp", "max_n", "_pad", "node_off", "pair_off", "node_dense", "node_mol", "pair_a", "pair_b",
+                                 "pair_mol", "mol_by_size"]
+    assert names(E.DsWorkspace) == E._WS_FIELDS == ["pos", "h", "e", "atom_hids", "edge_hids", "tfeat", "tmid", "temb_silu", "ada", "qkv", "ye",
+                                                    "dist", "attn", "u", "ac", "ed", "lg", "tr", "adj", "flags"]
+    assert names(E.DsGemmArgs) == ["A", "lda", "a_grp_rows", "_p0", "a_grp_stride", "Wp", "bias", "C", "ldc", "c_grp_rows", "_p1", "c_grp_stride",
+                                   "M", "K", "N", "act", "R", "ldr", "r_grp_rows", "a_silu", "col_scale", "col_shift"]
+    for t, n in ((E.DsWeights, "ds_weights"), (E.DsLayout, "ds_layout"), (E.DsWorkspace, "ds_workspace"), (E.DsGemmArgs, "ds_gemm_args")):
+        assert ctypes.sizeof(t) == abi.SAMPLING.packer(n).size
+    assert E.DsWeights.off.size == 382 * 8 and E.DsLayout.node_off.offset == 24
+
+
 def test_training_surface_refuses_cpu():
     """Row N1 has no CPU path either: optimizer, loss function and graphs raise off the GPU."""
     from diffspectra_amd import losses as Lh, train_engine as T

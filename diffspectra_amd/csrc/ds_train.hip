@@ -69,16 +69,11 @@ __global__ __launch_bounds__(256) void k_sumsq_partial(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------------------------ elementwise
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+using dst::sigmoidf_;
 __global__ void k_act_fwd(const float* __restrict__ x, float* __restrict__ y, int64_t n, int kind) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float v = x[i];
-  float r;
-  if (kind == 1) r = v * sigmoidf_(v);
-  else if (kind == 2) r = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-  else r = tanhf(v);
-  y[i] = r;
+  y[i] = dst::act_apply(x[i], kind);
 }
 __global__ void k_act_bwd(const float* __restrict__ dy, const float* __restrict__ ref, float* __restrict__ dx, int64_t n, int kind) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -150,11 +145,7 @@ __global__ __launch_bounds__(256) void k_pack_bf16_pieces(const dst_piece* __res
 // nn.Dropout(p) in training mode (dmt.py:114-120): y = x * keep / (1 - p) with keep ~ Bernoulli(1 - p) from a counter-based Philox4x32-10
 // stream keyed on (seed, stream id): the mask of element i is a pure function of (seed, stream, i), so the backward pass re-creates it
 // instead of storing it.  (The reference's masks come from torch's generator; only the distribution can agree.)
-__device__ __forceinline__ void philox_round(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
-  const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned int)p1, n2 = (unsigned int)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned int)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
+using dst::philox_round;
 __global__ void k_dropout(const float* __restrict__ x, float* __restrict__ y, int64_t n, float p, float scale, unsigned long long seed,
                           unsigned int stream_id) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;        // one Philox block = 4 elements

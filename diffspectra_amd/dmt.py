@@ -137,7 +137,7 @@ class DMT(nn.Module):
         tr.ops.bf16 = getattr(self.config.training, "precision", "fp32") == "bf16"      # (before graphs(): the per-step weight copies depend on it)
         named, dmt, spec = tr.graphs()
         f32 = lambda v: v.detach().to(dev, torch.float32)
-        TL = tr.layout(f32(node_mask).reshape(node_mask.shape[0], -1))
+        TL = tr.layout(f32(node_mask).reshape(node_mask.shape[0], -1), ident=node_mask)
         TL.L.check_edge_mask(edge_mask)
         TL.L.check_edge_symmetry(edge_x, "edge_x")
         z, ez = TL.pack_nodes(f32(xh)), TL.pack_pairs(f32(edge_x))
@@ -225,4 +225,8 @@ class _DmtGraph(torch.autograd.Function):
             g.update(spec.backward(g.pop("@ctx_emb")))
         finally:
             tr.ops.end()
-        return (None,) * 8 + deliver(tr, named, g, flat, offs, None)
+        target, grads = deliver(tr, named, g, flat, offs)
+        if target is not None:
+            target.add_(flat)
+            grads = [None] * len(named)
+        return (None,) * 8 + tuple(grads)

@@ -26,6 +26,7 @@ import torch.distributed as dist
 from . import engine as E
 from .ema import ExponentialMovingAverage
 from .scalers import _factors, get_self_cond_fn
+from .spec_train import SpecTrainGraph
 from .train_engine import DmtTrainGraph, Ops, TrainLayout, load_train_library
 
 
@@ -381,28 +382,19 @@ class _HipLossFlat(torch.autograd.Function):
         return (None,) * len(ctx.needs_input_grad)
 
 
-def _deliver_grads(tr, named, g, flat, offs, scale):
-    """Parameter gradients of a finished backward (``flat`` = the stage they were written into) for an autograd node's return tuple:
-    when every ``p.grad`` is a view of one flat buffer laid out like the stage, ONE kernel adds the stage into it and the node
-    returns None s; otherwise per-parameter clones (autograd accumulates them)."""
+def _deliver_grads(tr, named, g, flat, offs):
+    """The hand-over of a finished backward (``g``: its gradients, views of the stage ``flat``) to autograd, as ``(target, grads)``.  When
+    every ``p.grad`` is a view of one flat buffer laid out like the stage, ``target`` is that buffer - the caller adds the stage (frozen
+    slices cleared here) into it with ONE kernel and its autograd node returns None s - and ``grads`` is None; otherwise ``target`` is None
+    and ``grads`` holds per-parameter clones (the stage is overwritten by the next call; None for a frozen parameter)."""
     missing = [n for n, p in named.items() if p.requires_grad and n not in g]
     if missing:
         raise RuntimeError(f"no gradient was produced for {missing[:5]}")
     target = tr.flat_grad_target(named, offs)
     if target is not None:
         zero_frozen(flat, named, offs)
-        if scale is None:
-            target.add_(flat)
-        else:
-            target.addcmul_(flat, scale.to(flat.dtype))
-        return (None,) * len(named)
-    out = []
-    for n, p in named.items():
-        if not p.requires_grad:
-            out.append(None)
-        else:
-            out.append(g[n].clone() if scale is None else g[n] * scale)
-    return tuple(out)
+        return target, None
+    return None, [g[n].clone() if p.requires_grad else None for n, p in named.items()]
 
 
 def zero_frozen(flat, named, offs):
@@ -424,7 +416,12 @@ class HipTrainer:
             raise RuntimeError("training runs on an MI355X only (move the model to a 'cuda' device); there is no CPU path")
         self.ops = Ops(self.dev)
         self.lib = self.ops.lib
+        self.dmt = DmtTrainGraph({}, config, self.dev, self.ops)      # bound to the parameters' current storage by graphs()
+        self.spec = SpecTrainGraph({}, {}, config, self.ops)
+        self._registry = None           # (module identity, named parameters, named buffers): the module tree is walked once
         self._layouts: Dict[bytes, TrainLayout] = {}
+        self._layout_seen = None        # (mask tensor, its version, key into _layouts) of the last layout() call
+        self._flat_ok = None            # (key, base, target) of the last flat gradient buffer flat_grad_target() accepted
         self._stage = None
         self.stage_generation = 0       # bumped whenever the shared gradient stage is rewritten (checked by _HipLossFlat.backward)
 
@@ -457,7 +454,7 @@ class HipTrainer:
         if base is None or base.dim() != 1 or not base.is_contiguous() or base.dtype != torch.float32:
             return None
         key = (base.data_ptr(), tuple(int(p.grad.data_ptr()) if (p.requires_grad and p.grad is not None) else -1 for p in params[::37]))
-        cached = getattr(self, "_flat_ok", None)
+        cached = self._flat_ok
         if cached is not None and cached[0] == key and cached[1] is base:
             return cached[2]
         b0 = base.data_ptr()
@@ -474,16 +471,18 @@ class HipTrainer:
         self._flat_ok = (key, base, target)
         return target
 
-    def layout(self, atom_mask) -> TrainLayout:
+    def layout(self, atom_mask, ident=None) -> TrainLayout:
         # The packed layout is a function of the mask's CONTENT: reading it is a device -> host copy, i.e. the host waits for everything the
-        # stream still holds (the previous step's tail) - the one synchronisation of a step.  A mask tensor that was seen before (same
-        # storage, same version counter: an epoch over pre-uploaded batches, bench.py) is recognised without reading it.
-        ident = (atom_mask.data_ptr(), atom_mask._version, tuple(atom_mask.shape), atom_mask.dtype)
-        seen = getattr(self, "_layout_ident", None)
-        if seen is not None and seen[0] == ident and seen[1] in self._layouts:
-            return self._layouts[seen[1]]
+        # stream still holds (the previous step's tail) - the one synchronisation of a step.  A mask tensor that was seen in the last call
+        # (the same object - held here, so its address cannot be given to another tensor - at the same version counter: an epoch over
+        # pre-uploaded batches, bench.py) is recognised without reading it.  ``ident``: the caller's own tensor to recognise the mask by,
+        # when ``atom_mask`` is a temporary made from it.
+        ident = atom_mask if ident is None else ident
+        seen = self._layout_seen
+        if seen is not None and seen[0] is ident and seen[1] == ident._version and seen[2] in self._layouts:
+            return self._layouts[seen[2]]
         key = (atom_mask != 0).to("cpu").numpy().tobytes() + bytes(atom_mask.shape[1])
-        self._layout_ident = (ident, key)
+        self._layout_seen = (ident, ident._version, key)
         if key not in self._layouts:
             if len(self._layouts) >= 8:
                 self._layouts.pop(next(iter(self._layouts)))
@@ -491,21 +490,18 @@ class HipTrainer:
         return self._layouts[key]
 
     def graphs(self):
-        from .spec_train import SpecTrainGraph
         # (the module tree is walked once: named_parameters() / named_buffers() of ~400 modules cost 2 ms of host time per step)
-        reg = getattr(self, "_registry", None)
+        reg = self._registry
         if reg is None or reg[0] != (id(self.module), len(self.module._modules)):          # (set tr._registry = None after surgery on the module tree)
             reg = ((id(self.module), len(self.module._modules)), dict(self.module.named_parameters()), {k: v for k, v in self.module.named_buffers()})
             self._registry = reg
         named, bufs = reg[1], reg[2]
         pd = {k: v.data for k, v in named.items()}
-        dmt = DmtTrainGraph.__new__(DmtTrainGraph)
-        dmt.p, dmt.cfg, dmt.dev, dmt.ops, dmt.lib = pd, self.cfg, self.dev, self.ops, self.lib
-        dmt.edge_th, dmt.cutoff = float(self.cfg.model.edge_quan_th), float(self.cfg.model.spatial_cut_off)
-        spec = SpecTrainGraph(pd, bufs, self.cfg, self.ops)
-        dmt.gbuf = spec.gbuf = self.stage(named)[1]
-        self.cat_cache = dmt.prepare_weights(getattr(self, "cat_cache", None))     # concatenated weights of this call's parameters (one multi-tensor copy)
-        return named, dmt, spec
+        gbuf = self.stage(named)[1]
+        self.dmt.bind(pd, gbuf)
+        self.spec.bind(pd, gbuf, bufs)
+        self.dmt.prepare_weights()                  # concatenated weights of this call's parameters (one multi-tensor copy)
+        return named, self.dmt, self.spec
 
 
 def _trainer(model) -> HipTrainer:
@@ -605,16 +601,10 @@ def get_sde_graph_loss_fn(noise_scheduler, train, scaler, config, prop_norm=None
         flat, _, offs = tr.stage_begin(named)                           # zeroed: gradients that a branch does not produce (first-step dist_layer) stay zero
         g = dmt.backward(dpos, dfeat, dedge)
         g.update(spec.backward(g.pop("@ctx_emb")))
-        params = [p for p in named.values()]
-        missing = [n for n, p in named.items() if p.requires_grad and n not in g]
-        if missing:
-            raise RuntimeError(f"no gradient was produced for {missing[:5]}")
-        target = tr.flat_grad_target(named, offs)
+        target, grads = _deliver_grads(tr, named, g, flat, offs)
         if target is not None:                                          # the fused optimizer's flat gradient buffer: one accumulation kernel
-            zero_frozen(flat, named, offs)
-            return _HipLossFlat.apply(loss, flat, target, tr, tr.stage_generation, *params)
-        grads = [g.get(n).clone() if p.requires_grad else None for n, p in named.items()]      # the stage is overwritten by the next call
-        return _HipLoss.apply(loss, grads, *params)
+            return _HipLossFlat.apply(loss, flat, target, tr, tr.stage_generation, *named.values())
+        return _HipLoss.apply(loss, grads, *named.values())
 
     return loss_fn
 

@@ -10,8 +10,7 @@ encoder are 0 in the reference's constructor defaults.  No PyTorch arithmetic: G
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -26,7 +25,10 @@ class SpecTrainGraph:
     def __init__(self, params: Dict[str, torch.Tensor], buffers: Dict[str, torch.Tensor], config, ops: Ops):
         """``params``: reference-named trainable tensors (``cond_encoder.*``, ``cond_lin.*``); ``buffers``: the BatchNorm running
         statistics (updated in place by ``forward``)."""
-        self.p, self.buf, self.cfg, self.ops = params, buffers, config, ops
+        self.cfg, self.ops = config, ops
+        self.p, self.buf, self.gbuf = params, buffers, None      # bind()
+        self.t = None                                             # the tape of the last forward(save=True), consumed by backward
+        self._bn_last = []                                        # (name, batch statistics) of the BatchNorms of the last forward
         self.lib, self.dev = ops.lib, ops.dev
         self.version = config.data.spectra_version
         self.used = used_spectra(self.version)
@@ -35,6 +37,13 @@ class SpecTrainGraph:
         self.L = sum(pn for _, _, pn in self.patch)
         self.pos_names = (["W_pos_uv", "W_pos_ir", "W_pos_raman"] if self.version == "allspectra" else ["W_pos"])
         self.flash = None      # None: the score-free flash attention in bf16 mode, the materialised fp32 kernels otherwise; True / False force one
+
+    def bind(self, params: Dict[str, torch.Tensor], gbuf: Optional[Dict[str, torch.Tensor]] = None, buffers: Optional[Dict[str, torch.Tensor]] = None):
+        """This call's parameter storage, the views of the gradient stage its backward writes into (None: fresh tensors) and - if given - the
+        BatchNorm buffers.  A forward keeps its binding in its tape and ``backward`` returns to it (see ``DmtTrainGraph.bind``)."""
+        self.p, self.gbuf, self.t = params, gbuf, None
+        if buffers is not None:
+            self.buf = buffers
 
     def f(self, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=self.dev)
@@ -61,7 +70,7 @@ class SpecTrainGraph:
     def _bn_bwd(self, dy, x, stats, name, dx, g):
         o = self.ops
         R, Cc = x.shape
-        gb = getattr(self, "gbuf", None)
+        gb = self.gbuf
         g[name + ".weight"], g[name + ".bias"] = (gb[name + ".weight"], gb[name + ".bias"]) if gb is not None else (self.f(Cc), self.f(Cc))
         E._check(self.lib.dst_bn_bwd(E._ptr(dy), E._ptr(x), E._ptr(stats), C.c_int32(R), C.c_int32(Cc), E._ptr(self.p[name + ".weight"]), E._ptr(dx),
                                      E._ptr(g[name + ".weight"]), E._ptr(g[name + ".bias"]), E._ptr(o.scratch), C.c_int64(o.scratch.numel()), self.ops._s()),
@@ -75,7 +84,7 @@ class SpecTrainGraph:
         specs = list(context) if self.version == "allspectra" else [context]
         B = specs[0].shape[0]
         L = self.L
-        t: Dict[str, object] = dict(B=B)
+        t: Dict[str, object] = dict(B=B, bound=(self.p, self.gbuf, self.buf))
         self._bn_last = []
         toks, Xs = [], []
         for slot, ((pl, stv, pn), spec) in enumerate(zip(self.patch, specs)):
@@ -140,14 +149,13 @@ class SpecTrainGraph:
 
     # ------------------------------------------------------------------ backward
     def backward(self, dctx: torch.Tensor) -> Dict[str, torch.Tensor]:
-        o, p, t = self.ops, self.p, self.t
+        t = self.t
+        self.bind(*t["bound"])                                         # the parameters and the stage of the forward that wrote this tape
+        o, p, gbuf = self.ops, self.p, self.gbuf
         pre = "cond_encoder."
         B, L = t["B"], self.L
         g: Dict[str, torch.Tensor] = {}
-        o.async_dw = bool(int(os.environ.get("DIFFSPECTRA_ASYNC_DW", "1")))     # weight gradients on the side stream (train_engine.Ops.lin_bwd_w)
-        two_streams = bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and o.main_stream is not None
-
-        gbuf = getattr(self, "gbuf", None)
+        two_streams, o.async_dw = o.stream_modes()                     # weight gradients on the side streams (train_engine.Ops.lin_bwd_w)
 
         def gw(name):
             g[name] = gbuf[name] if gbuf is not None else torch.empty_like(p[name])

@@ -16,6 +16,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -63,45 +64,42 @@ DstPiece = abi.TRAINING.ctypes_struct("dst_piece")
 DstLayout = abi.TRAINING.ctypes_struct("dst_layout")
 
 
-def copy_pieces(lib, dev, dst: List[torch.Tensor], src: List[torch.Tensor], cache: dict, key: str, stream=None):
-    """``dst[i].copy_(src[i])`` for many small (<= 2-D, last dimension contiguous) fp32 pieces in ONE ``dst_copy_pieces`` launch.  The device
-    table is rebuilt only when a pointer changed (parameters live in the optimizer's flat buffer, the concatenated buffers are persistent)."""
+def _piece_table(dev, dst: List[torch.Tensor], src: List[torch.Tensor], cache: dict, key: str, row):
+    """(device pointer, length) of the ``dst_piece`` table with the rows ``row(i, dst[i], src[i])``.  The table is rebuilt only when a pointer
+    changed (parameters live in the optimizer's flat buffer, the concatenated buffers are persistent)."""
     sig = tuple(t.data_ptr() for t in dst) + tuple(t.data_ptr() for t in src)
     ent = cache.get(key)
     if ent is None or ent[0] != sig:
-        arr = (DstPiece * len(dst))()
-        for i, (d, s_) in enumerate(zip(dst, src)):
-            assert d.shape == s_.shape and d.dtype == torch.float32 and s_.dtype == torch.float32 and d.dim() <= 2
-            rows, cols = (1, d.numel()) if d.dim() < 2 else (d.shape[0], d.shape[1])
-            assert rows * cols < 2 ** 31                              # the kernel's index arithmetic is 32-bit
-            ld = lambda t: (t.stride(0) if t.dim() == 2 and t.shape[0] > 1 else cols)
-            assert (d.dim() < 2 or d.stride(-1) == 1 or cols == 1) and (s_.dim() < 2 or s_.stride(-1) == 1 or cols == 1)
-            assert d.dim() >= 1 and (d.dim() == 2 or d.is_contiguous()) and (s_.dim() == 2 or s_.is_contiguous())
-            arr[i] = DstPiece(src=s_.data_ptr(), dst=d.data_ptr(), rows=rows, cols=cols, src_ld=ld(s_), dst_ld=ld(d))
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        ent = (sig, raw, len(dst))
-        cache[key] = ent
-    E._check(lib.dst_copy_pieces(C.c_void_p(ent[1].data_ptr()), C.c_int32(ent[2]), stream if stream is not None else E._stream()), "dst_copy_pieces")
+        arr = (DstPiece * len(dst))(*(row(i, d, s_) for i, (d, s_) in enumerate(zip(dst, src))))
+        ent = cache[key] = (sig, torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), len(dst))
+    return C.c_void_p(ent[1].data_ptr()), C.c_int32(ent[2])
+
+
+def copy_pieces(lib, dev, dst: List[torch.Tensor], src: List[torch.Tensor], cache: dict, key: str, stream=None):
+    """``dst[i].copy_(src[i])`` for many small (<= 2-D, last dimension contiguous) fp32 pieces in ONE ``dst_copy_pieces`` launch."""
+    def row(i, d, s_):
+        assert d.shape == s_.shape and d.dtype == torch.float32 and s_.dtype == torch.float32 and d.dim() <= 2
+        rows, cols = (1, d.numel()) if d.dim() < 2 else (d.shape[0], d.shape[1])
+        assert rows * cols < 2 ** 31                              # the kernel's index arithmetic is 32-bit
+        ld = lambda t: (t.stride(0) if t.dim() == 2 and t.shape[0] > 1 else cols)
+        assert (d.dim() < 2 or d.stride(-1) == 1 or cols == 1) and (s_.dim() < 2 or s_.stride(-1) == 1 or cols == 1)
+        assert d.dim() >= 1 and (d.dim() == 2 or d.is_contiguous()) and (s_.dim() == 2 or s_.is_contiguous())
+        return DstPiece(src=s_.data_ptr(), dst=d.data_ptr(), rows=rows, cols=cols, src_ld=ld(s_), dst_ld=ld(d))
+    table, n = _piece_table(dev, dst, src, cache, key, row)
+    E._check(lib.dst_copy_pieces(table, n, stream if stream is not None else E._stream()), "dst_copy_pieces")
 
 
 def pack_bf16_pieces(lib, dev, dst: List[torch.Tensor], src: List[torch.Tensor], cache: dict, key: str, stream=None, key_t=None):
     """``dst[i].copy_(src[i])`` with ``dst`` in bfloat16 (round to nearest even) for many small 2-D pieces in ONE ``dst_pack_bf16_pieces`` launch:
-    the weights of the fused row chains, once per step.  ``key_t``: the indices of the pieces that are stored TRANSPOSED.  The device table is
-    rebuilt only when a pointer changed."""
-    sig = tuple(t.data_ptr() for t in dst) + tuple(t.data_ptr() for t in src)
-    ent = cache.get(key)
-    if ent is None or ent[0] != sig:
-        arr = (DstPiece * len(dst))()
-        for i, (d, s_) in enumerate(zip(dst, src)):
-            assert d.dtype == torch.bfloat16 and s_.dtype == torch.float32 and d.dim() == 2 and d.stride(1) == 1 and s_.stride(1) == 1 and d.numel() < 2 ** 31
-            transposed = key_t is not None and i in key_t           # dst = src^T (dst_ld < 0 in the table)
-            assert tuple(d.shape) == (tuple(s_.shape)[::-1] if transposed else tuple(s_.shape))
-            arr[i] = DstPiece(src=s_.data_ptr(), dst=d.data_ptr(), rows=s_.shape[0], cols=s_.shape[1], src_ld=s_.stride(0),
-                              dst_ld=-d.stride(0) if transposed else d.stride(0))
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        ent = (sig, raw, len(dst))
-        cache[key] = ent
-    E._check(lib.dst_pack_bf16_pieces(C.c_void_p(ent[1].data_ptr()), C.c_int32(ent[2]), stream if stream is not None else E._stream()), "dst_pack_bf16_pieces")
+    the weights of the fused row chains, once per step.  ``key_t``: the indices of the pieces that are stored TRANSPOSED."""
+    def row(i, d, s_):
+        assert d.dtype == torch.bfloat16 and s_.dtype == torch.float32 and d.dim() == 2 and d.stride(1) == 1 and s_.stride(1) == 1 and d.numel() < 2 ** 31
+        transposed = key_t is not None and i in key_t           # dst = src^T (dst_ld < 0 in the table)
+        assert tuple(d.shape) == (tuple(s_.shape)[::-1] if transposed else tuple(s_.shape))
+        return DstPiece(src=s_.data_ptr(), dst=d.data_ptr(), rows=s_.shape[0], cols=s_.shape[1], src_ld=s_.stride(0),
+                        dst_ld=-d.stride(0) if transposed else d.stride(0))
+    table, n = _piece_table(dev, dst, src, cache, key, row)
+    E._check(lib.dst_pack_bf16_pieces(table, n, stream if stream is not None else E._stream()), "dst_pack_bf16_pieces")
 
 
 _lib = None
@@ -155,6 +153,16 @@ def mv(t: torch.Tensor, c0: Optional[int] = None, c1: Optional[int] = None, r0: 
     return MV(t, r1 - r0, c1 - c0, t2c, r0 * t2c + c0)
 
 
+def ptr(t) -> int:
+    """Data pointer of a tensor, 0 for None (an output the fused chain kernels need not write)."""
+    return 0 if t is None else t.data_ptr()
+
+
+def _need_bf16(*weights):
+    """The fused row chains stream their weights as bf16 (dst_pack_bf16_pieces / .to(torch.bfloat16): nearest even)."""
+    assert all(w_.dtype == torch.bfloat16 for w_ in weights)
+
+
 class Ops:
     """ctypes wrappers over the dst_* entry points, issued on torch's current stream."""
 
@@ -163,7 +171,7 @@ class Ops:
         self.dev = torch.device(device)
         self.scratch = torch.empty(48 * 1024 * 1024, dtype=torch.float32, device=self.dev)     # split-K partials / column sums
         self.bf16 = False      # config.training.precision == 'bf16': every GEMM rounds its operands to bf16 (fp32 accumulate, fp32 storage)
-        # Weight-gradient products on a SIDE stream (DmtTrainGraph.backward switches it on): nothing downstream of a backward pass reads
+        # Weight-gradient products on a SIDE stream (a backward pass switches it on, stream_modes()): nothing downstream of a backward pass reads
         # dW, so the ~200 split-K products of a step need not sit in the dependent chain of input-gradient kernels - they fill the CUs the
         # small kernels of that chain leave idle.  The side stream has its own split-K scratch; operands are kept alive until join_dw().
         self.async_dw = False
@@ -190,6 +198,12 @@ class Ops:
         self.stream_ptr = None
         self.main_stream = None
         self.cur_stream = None
+
+    def stream_modes(self) -> Tuple[bool, bool]:
+        """(node stream, weight-gradient streams) as the environment asks for them NOW: every forward / backward reads them, so a caller
+        may flip them between two steps.  The node stream needs the stream handle of ``begin``."""
+        return (bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and self.main_stream is not None,
+                bool(int(os.environ.get("DIFFSPECTRA_ASYNC_DW", "1"))))
 
     def gemm(self, A: MV, Bm: MV, Cm: MV, ta: bool, tb: bool, bias: Optional[torch.Tensor] = None, acc: bool = False,
              rowsum: Optional[torch.Tensor] = None, act: int = 0, dact: int = 0, ref: Optional[MV] = None, out2: Optional[MV] = None,
@@ -326,30 +340,27 @@ class Ops:
 
     def pair_chain_fwd(self, TL, u, n2e_bias, e_in, feat, ld_feat, ada, g1, sh, sc, g2, W3, b3, W4, b4, Wed, ld_wed, bed, Wro, bro, drop, out):
         """The pair rows of a block behind the attention as one kernel (``dst_pair_chain_fwd``, bf16 products).  ``drop = (p, seed, stream3,
-        stream4)``; ``out``: dict with e_out, ed, ro and - when the tape is kept - he, xe1, st, ye1, f3, s3, f4, X2."""
-        ptr = lambda t: 0 if t is None else t.data_ptr()
-        assert all(w_.dtype == torch.bfloat16 for w_ in (W3, W4, Wed, Wro))          # (dst_pack_bf16_pieces / .to(torch.bfloat16): nearest even)
+        stream4)``; ``out``: the block's tape, holding e_out, ed, re_ and - when the tape is kept - he, xe1, st_e2, ye1, f3, s3, f4, X2."""
+        _need_bf16(W3, W4, Wed, Wro)
         args = _CHAIN_PACK(*TL.pair_tables, ptr(u), ptr(n2e_bias), ptr(e_in), ptr(feat), ld_feat, ptr(ada), ADA, g1, sh, sc, g2, ptr(W3), ptr(b3), ptr(W4), ptr(b4),
                            ptr(Wed), ld_wed, ptr(bed), ptr(Wro), ptr(bro), float(drop[0]), int(drop[2]), int(drop[3]), 0, int(drop[1]),
-                           *(ptr(out.get(k)) for k in ("he", "xe1", "st", "ye1", "f3", "s3", "f4", "e_out", "X2", "ed", "ro")))
+                           *(ptr(out.get(k)) for k in ("he", "xe1", "st_e2", "ye1", "f3", "s3", "f4", "e_out", "X2", "ed", "re_")))
         E._check(self.lib.dst_pair_chain_fwd(C.byref(TL.c), args, self._s()), "dst_pair_chain_fwd")
 
     def node_chain_fwd(self, TL, h_in, attn, ada, g1, sh, sc, g2, W1, b1, W2, b2, Wac, Wn, bn, drop, out):
         """The node rows of a block behind the attention as one kernel (``dst_node_chain_fwd``, bf16 products).  ``drop = (p, seed, stream1,
-        stream2)``; ``out``: dict with h_out, ac, rn and - when the tape is kept - x1, st, y1, f1, s1, f2."""
-        ptr = lambda t: 0 if t is None else t.data_ptr()
-        assert all(w_.dtype == torch.bfloat16 for w_ in (W1, W2, Wac, Wn))
+        stream2)``; ``out``: the block's tape, holding h_out, ac, rn and - when the tape is kept - x1, st_n2, y1, f1, s1, f2."""
+        _need_bf16(W1, W2, Wac, Wn)
         args = _NODE_PACK(TL.node_mol_ptr, ptr(h_in), ptr(attn), ptr(ada), ADA, g1, sh, sc, g2, ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(Wac), ptr(Wn), ptr(bn),
                           float(drop[0]), int(drop[2]), int(drop[3]), 0, int(drop[1]),
-                          *(ptr(out.get(k)) for k in ("x1", "st", "y1", "f1", "s1", "f2", "h_out", "ac", "rn")))
+                          *(ptr(out.get(k)) for k in ("x1", "st_n2", "y1", "f1", "s1", "f2", "h_out", "ac", "rn")))
         E._check(self.lib.dst_node_chain_fwd(C.byref(TL.c), args, self._s()), "dst_node_chain_fwd")
 
     def dir_chain_fwd(self, TL, ac, ed, ada, sh, sc, W0, b0, W2, out):
-        """The directed rows of a block as one kernel (``dst_dir_chain_fwd``, bf16 products).  ``out``: dict with c2 and - when the tape is kept -
-        zz, st, zn, c0, sc0."""
-        ptr = lambda t: 0 if t is None else t.data_ptr()
-        assert W0.dtype == torch.bfloat16 and W2.dtype == torch.bfloat16
-        args = _DIR_PACK(*TL.pair_tables, ptr(ac), ptr(ed), ptr(ada), ADA, sh, sc, ptr(W0), ptr(b0), ptr(W2), *(ptr(out.get(k)) for k in ("zz", "st", "zn", "c0", "sc0", "c2")))
+        """The directed rows of a block as one kernel (``dst_dir_chain_fwd``, bf16 products).  ``out``: the block's tape, holding c2 and - when the tape is
+        kept - zz, st_z, zn, c0, sc0."""
+        _need_bf16(W0, W2)
+        args = _DIR_PACK(*TL.pair_tables, ptr(ac), ptr(ed), ptr(ada), ADA, sh, sc, ptr(W0), ptr(b0), ptr(W2), *(ptr(out.get(k)) for k in ("zz", "st_z", "zn", "c0", "sc0", "c2")))
         E._check(self.lib.dst_dir_chain_fwd(C.byref(TL.c), args, self._s()), "dst_dir_chain_fwd")
 
     def _part(self, kernel: str, n: int) -> int:
@@ -364,41 +375,48 @@ class Ops:
         """Backward of the pair rows of a block behind the attention as one kernel + its finishing kernel (``dst_pair_chain_bwd``).  ``dro``: a
         data pointer (the read-out slice's gradient is a column window of a wider tensor) with row stride ``ld_dro``; ``drop = (p, seed, stream3,
         stream4)``."""
-        assert all(w_.dtype == torch.bfloat16 for w_ in (WedT, WroT, W4T, W3T))
+        _need_bf16(WedT, WroT, W4T, W3T)
         tt = TL.pair_tiles
-        dp_ = lambda t: t.data_ptr()
-        args = _PAIRB_PACK(tt[0], tt[1], tt[2], tt[3], tt[4], dp_(de), int(dro), ld_dro, dp_(ded), dp_(f4), dp_(f3), dp_(xe1), dp_(st), dp_(he), dp_(ada), dp_(d_ada), ADA,
-                           g1, sh, sc, g2, dp_(WedT), dp_(WroT), dp_(W4T), dp_(W3T), float(drop[0]), int(drop[2]), int(drop[3]), 0, int(drop[1]),
-                           dp_(dfeat), dp_(df4), dp_(df3), dp_(de_in), dp_(dhe), self._part("pair", tt[4] * 256))
+        args = _PAIRB_PACK(tt[0], tt[1], tt[2], tt[3], tt[4], ptr(de), int(dro), ld_dro, ptr(ded), ptr(f4), ptr(f3), ptr(xe1), ptr(st), ptr(he), ptr(ada), ptr(d_ada), ADA,
+                           g1, sh, sc, g2, ptr(WedT), ptr(WroT), ptr(W4T), ptr(W3T), float(drop[0]), int(drop[2]), int(drop[3]), 0, int(drop[1]),
+                           ptr(dfeat), ptr(df4), ptr(df3), ptr(de_in), ptr(dhe), self._part("pair", tt[4] * 256))
         E._check(self.lib.dst_pair_chain_bwd(C.byref(TL.c), args, self._s()), "dst_pair_chain_bwd")
 
     def node_chain_bwd(self, TL, dh, drn, ld_drn, dac, f2, f1, x1, st, attn, ada, d_ada, g1, sh, sc, g2, WacT, WnT, W2T, W1T, drop, df2, df1, dh_in, dattn):
         """Backward of the node rows of a block behind the attention as one kernel + its finishing kernel (``dst_node_chain_bwd``).  ``drn``: a data
         pointer with row stride ``ld_drn``; ``drop = (p, seed, stream1, stream2)``."""
-        assert all(w_.dtype == torch.bfloat16 for w_ in (WacT, WnT, W2T, W1T))
+        _need_bf16(WacT, WnT, W2T, W1T)
         tt = TL.node_tiles
-        dp_ = lambda t: t.data_ptr()
-        args = _NODEB_PACK(tt[0], tt[1], tt[2], tt[3], tt[4], dp_(dh), int(drn), ld_drn, dp_(dac), dp_(f2), dp_(f1), dp_(x1), dp_(st), dp_(attn), dp_(ada), dp_(d_ada), ADA,
-                           g1, sh, sc, g2, dp_(WacT), dp_(WnT), dp_(W2T), dp_(W1T), float(drop[0]), int(drop[2]), int(drop[3]), 0, int(drop[1]),
-                           dp_(df2), dp_(df1), dp_(dh_in), dp_(dattn), self._part("node", tt[4] * 1024))
+        args = _NODEB_PACK(tt[0], tt[1], tt[2], tt[3], tt[4], ptr(dh), int(drn), ld_drn, ptr(dac), ptr(f2), ptr(f1), ptr(x1), ptr(st), ptr(attn), ptr(ada), ptr(d_ada), ADA,
+                           g1, sh, sc, g2, ptr(WacT), ptr(WnT), ptr(W2T), ptr(W1T), float(drop[0]), int(drop[2]), int(drop[3]), 0, int(drop[1]),
+                           ptr(df2), ptr(df1), ptr(dh_in), ptr(dattn), self._part("node", tt[4] * 1024))
         E._check(self.lib.dst_node_chain_bwd(C.byref(TL.c), args, self._s()), "dst_node_chain_bwd")
 
     def dir_chain_bwd(self, TL, dc2, c0, zz, st, ada, d_ada, sh, sc, W2, W0T, dc0, dz):
         """Backward of the directed rows of a block as one kernel + its finishing kernel (``dst_dir_chain_bwd``)."""
-        assert W0T.dtype == torch.bfloat16 and W2.dtype == torch.float32
+        _need_bf16(W0T)
+        assert W2.dtype == torch.float32
         tt = TL.dir_tiles
         args = _DIRB_PACK(tt[0], tt[1], tt[2], tt[3], tt[4], dc2.data_ptr(), c0.data_ptr(), zz.data_ptr(), st.data_ptr(), ada.data_ptr(), d_ada.data_ptr(), ADA, sh, sc,
                           W2.data_ptr(), W0T.data_ptr(), dc0.data_ptr(), dz.data_ptr(), self._part("dir", tt[4] * 512))
         E._check(self.lib.dst_dir_chain_bwd(C.byref(TL.c), args, self._s()), "dst_dir_chain_bwd")
 
     def pair_front_fwd(self, TL, pos, ada, dist_off, sh, sc, means, stds, e_in, Wee, bee, Wte, out):
-        """The pair rows of a block in front of the attention as one kernel (``dst_pair_front_fwd``, bf16 products).  ``out``: dict with X1, te and -
-        when the tape is kept - xs, d2, e1, st, en."""
-        ptr = lambda t: 0 if t is None else t.data_ptr()
-        assert Wee.dtype == torch.bfloat16 and Wte.dtype == torch.bfloat16
+        """The pair rows of a block in front of the attention as one kernel (``dst_pair_front_fwd``, bf16 products).  ``out``: the block's tape, holding X1, te
+        and - when the tape is kept - xs, d2, e1, st_e1, en."""
+        _need_bf16(Wee, Wte)
         args = _FRONT_PACK(*TL.pair_tables, ptr(pos), ptr(ada), ADA, dist_off, sh, sc, 0, ptr(means), ptr(stds), ptr(e_in), ptr(Wee), ptr(bee), ptr(Wte),
-                           *(ptr(out.get(k)) for k in ("X1", "xs", "d2", "e1", "st", "en", "te")))
+                           *(ptr(out.get(k)) for k in ("X1", "xs", "d2", "e1", "st_e1", "en", "te")))
         E._check(self.lib.dst_pair_front_fwd(C.byref(TL.c), args, self._s()), "dst_pair_front_fwd")
+
+    def geom_fwd(self, TL, pos, ada, dist_off, means, stds, X, ldx, col0, xs, d2s):
+        E._check(self.lib.dst_geom_fwd(C.byref(TL.c), E._ptr(pos), E._ptr(ada), C.c_int64(ADA), C.c_int32(dist_off), E._ptr(means), E._ptr(stds),
+                                       C.c_void_p(X.data_ptr() + 4 * col0), C.c_int64(ldx), E._ptr(xs), E._ptr(d2s), self._s()), "dst_geom_fwd")
+
+    def geom_bwd(self, TL, pos, ada, d_ada, dist_off, means, stds, xs, d2s, g1, g2, dms, dd2, dpos):
+        E._check(self.lib.dst_geom_bwd(C.byref(TL.c), E._ptr(pos), E._ptr(ada), E._ptr(d_ada), C.c_int64(ADA), C.c_int32(dist_off), E._ptr(means),
+                                       E._ptr(stds), E._ptr(xs), E._ptr(d2s), E._ptr(g1), C.c_int64(g1.shape[1]), E._ptr(g2),
+                                       C.c_int64(0 if g2 is None else g2.shape[1]), E._ptr(dms), E._ptr(dd2), E._ptr(dpos), self._s()), "dst_geom_bwd")
 
     def gate_add_bwd(self, dout, z, Cc, seg, mul, B, ada, d_ada, g, dr, acc_r, dz, drop=None):
         """``drop = (p, seed, stream_id)``: ``z`` was a dropout's output; ``dz`` is then the gradient in FRONT of that dropout."""
@@ -484,26 +502,85 @@ class TrainLayout:
 ADA_PARTS = (("node_time_mlp.1", NODE_OFF, 1536), ("edge_time_mlp.1", EDGE_OFF, 384), ("equi_update.time_mlp.1", EQUI_OFF, 512),
              ("dist_layer.time_mlp.1", DIST_OFF, 2))
 
+DROP_ROW = (512, 256, 128, 64)     # row length of a block's four dropout masks: behind ff_linear1, ff_linear2 (node rows), ff_linear3, ff_linear4 (pair rows)
+
+
+def _row_slots(base: int, width: int) -> SimpleNamespace:
+    """adaLN columns of the node or the pair rows of a block: ``ln1 = (shift, scale)`` in front of the attention and ``gate1`` behind it,
+    ``ln2`` / ``gate2`` around the FF; ``width`` columns each, in the order the *time_mlp produces them."""
+    return SimpleNamespace(ln1=(base, base + width), gate1=base + 2 * width, ln2=(base + 3 * width, base + 4 * width), gate2=base + 5 * width)
+
+
+class BlockSlots:
+    """What block ``i`` is called by: its parameter prefix, its columns of the adaLN table and its Philox dropout streams."""
+    __slots__ = ("i", "bp", "node", "edge", "equi_ln", "dist")
+
+    def __init__(self, i: int):
+        a0 = i * ADA_STRIDE
+        self.i, self.bp = i, f"e_block_{i}."
+        self.node, self.edge = _row_slots(a0 + NODE_OFF, 256), _row_slots(a0 + EDGE_OFF, 64)
+        self.equi_ln = (a0 + EQUI_OFF, a0 + EQUI_OFF + 256)        # (shift, scale) of the directed rows
+        self.dist = a0 + DIST_OFF                                  # (scale, shift) pair of the distance features
+
+    def drop(self, k: int) -> Tuple[int, int]:
+        """(stream id, row length) of dropout ``k`` of the block (``DROP_ROW``)."""
+        return 4 * self.i + k, DROP_ROW[k]
+
+
+BLOCKS = tuple(BlockSlots(i) for i in range(NB))
+
+# bf16 copies of a block's weights for the fused row chains (leading dimension NB): (name, shape, source, transposed).  Source: a parameter
+# name ({i} = block), (parameter name, first column, end column), or "cat.X" = block i of the concatenated buffer X.  The transposed copies
+# ([in][out]) are the B operands of the input-gradient products of the fused backward kernels.  The order is the order of the device table.
+_BP = "e_block_{i}."
+BF16_WEIGHTS = (
+    ("W3", (128, 64), _BP + "ff_linear3.weight", False), ("W4", (64, 128), _BP + "ff_linear4.weight", False),
+    ("Wed", (256, 128), (_BP + "equi_update.input_lin.weight", 512, 640), False), ("Wro", (16, 64), "edge_{i}.weight", False),
+    ("Wee", (64, 128), _BP + "edge_emb.weight", False), ("Wte", (512, 64), "cat.Wte", False),
+    ("W0", (256, 256), _BP + "equi_update.coord_mlp.0.weight", False), ("W2", (3, 256), _BP + "equi_update.coord_mlp.2.weight", False),
+    ("F1", (512, 256), _BP + "ff_linear1.weight", False), ("F2", (256, 512), _BP + "ff_linear2.weight", False),
+    ("Wac", (512, 256), "cat.Wac", False), ("Wn", (64, 256), "node_{i}.weight", False),
+    ("W0T", (256, 256), _BP + "equi_update.coord_mlp.0.weight", True), ("WedT", (128, 256), (_BP + "equi_update.input_lin.weight", 512, 640), True),
+    ("WroT", (64, 16), "edge_{i}.weight", True), ("W4T", (128, 64), _BP + "ff_linear4.weight", True),
+    ("W3T", (64, 128), _BP + "ff_linear3.weight", True), ("WacT", (256, 512), "cat.Wac", True), ("WnT", (256, 64), "node_{i}.weight", True),
+    ("F2T", (512, 256), _BP + "ff_linear2.weight", True), ("F1T", (256, 512), _BP + "ff_linear1.weight", True))
+
+
+def _bf16_source(src, i: int, p, cat) -> torch.Tensor:
+    if isinstance(src, tuple):
+        return p[src[0].format(i=i)][:, src[1]:src[2]]
+    return cat[src[4:]][i] if src.startswith("cat.") else p[src.format(i=i)]
+
 
 class DmtTrainGraph:
     """Forward tape and backward of one DMT evaluation (conditioning embedding given) on packed tensors.
 
-    ``params``: name -> fp32 device tensor (reference names, no ``module.`` prefix).  ``grads`` (same names) receives the gradients."""
+    ``params``: name -> fp32 device tensor (reference names, no ``module.`` prefix).  ``backward`` returns the gradients under the same
+    names: views of the gradient stage given to ``bind``, or - stand-alone - fresh tensors.  ``ops``: the caller's ``Ops`` (a trainer shares
+    one between its graphs); None makes one."""
 
-    def __init__(self, params: Dict[str, torch.Tensor], config, device):
-        self.p = params
+    def __init__(self, params: Dict[str, torch.Tensor], config, device, ops: Optional[Ops] = None):
         self.cfg = config
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
             raise RuntimeError("the training graph runs on an MI355X only; diffspectra_amd has no CPU path")
-        self.ops = Ops(self.dev)
+        self.ops = ops if ops is not None else Ops(self.dev)
         self.lib = self.ops.lib
         self.edge_th = float(config.model.edge_quan_th)
         self.cutoff = float(config.model.spatial_cut_off)
+        self.p, self.gbuf = params, None       # bind()
+        self.cat = self.dcat = self.wb = None  # prepare_weights(): concatenated weights, their gradients, the bf16 copies of the fused chains
+        self._cat_cache: dict = {}             # those buffers and the device tables of their piece copies, kept over the calls
+        self.t = None                          # the tape of the last forward(save=True), consumed by backward
+        # FF dropout of the training forward (dmt.py:114-120): probability and the seed of this evaluation's Philox streams; 0 = identity
+        self.dropout_p = 0.0
+        self.dropout_seed = 0
 
-    # FF dropout of the training forward (dmt.py:114-120): probability and the seed of this evaluation's Philox streams; 0 = identity
-    dropout_p = 0.0
-    dropout_seed = 0
+    def bind(self, params: Dict[str, torch.Tensor], gbuf: Optional[Dict[str, torch.Tensor]] = None):
+        """This call's parameter storage and the views of the gradient stage its backward writes into (None: fresh tensors).  A forward
+        keeps its binding in its tape and ``backward`` returns to it, so a backward may follow a later forward of the same graph (whoever
+        wants that keeps the tape: a new binding drops it)."""
+        self.p, self.gbuf, self.t = params, gbuf, None
 
     # ------------------------------------------------------------------ helpers
     def f(self, *shape):
@@ -515,7 +592,8 @@ class DmtTrainGraph:
     # ---- concatenated weights: Linears that read the same input are evaluated as ONE product (q | k | v; lin_edge0 | lin_edge1; the row | col
     #      parts of input_lin; every *time_mlp as the adaLN table) from per-step copies of the parameters in one buffer each.  The copies are
     #      two multi-tensor launches per step (torch._foreach_copy_), the gradients of the concatenated buffers are scattered back the same way.
-    def cat_plan(self):
+    @staticmethod
+    def cat_plan():
         """[(buffer name, shape)], [(buffer name, index expression, parameter name)] - where every parameter piece lives in its buffer."""
         bufs = [("Wada", (ADA, 1024)), ("bada", (ADA,)), ("Wqkv", (NB, 768, 256)), ("bqkv", (NB, 768)), ("Wte", (NB, 512, 64)), ("Wac", (NB, 512, 256))]
         pieces = []
@@ -549,68 +627,38 @@ class DmtTrainGraph:
                 src.append(tensors[pname])
         return dst, src
 
-    def prepare_weights(self, cache: Optional[dict] = None):
+    def prepare_weights(self):
         """Fill the concatenated weight buffers from the current parameters (once per step: both forwards of a step share them)."""
-        if cache is None:
-            cache = {}
+        cache = self._cat_cache
         if "bufs" not in cache:
             shapes, _ = self.cat_plan()
             cache["bufs"] = {n: self.z(*shape) for n, shape in shapes}          # padding rows (252..255 of q / k / lin_edge0) stay zero
             cache["grads"] = {n: self.z(*shape) for n, shape in shapes}
         dst, src = self._piece_views(cache["bufs"], self.p)
         copy_pieces(self.lib, self.dev, dst, src, cache, "table_fwd", self.ops._s())
-        self.cat, self.dcat, self._cat_cache = cache["bufs"], cache["grads"], cache
+        self.cat, self.dcat = cache["bufs"], cache["grads"]
         if self.ops.bf16:
             # the fused row chains take their weights as bf16 (csrc/ds_train_chain.hip: the per-tile weight stream from L2 bounds them)
             if "wb" not in cache:
-                shapes = dict(W3=(128, 64), W4=(64, 128), Wed=(256, 128), Wro=(16, 64), Wee=(64, 128), Wte=(512, 64), W0=(256, 256), W2=(3, 256),
-                              F1=(512, 256), F2=(256, 512), Wac=(512, 256), Wn=(64, 256), W0T=(256, 256),
-                              WedT=(128, 256), WroT=(64, 16), W4T=(128, 64), W3T=(64, 128), WacT=(256, 512), WnT=(256, 64), F2T=(512, 256), F1T=(256, 512))
-                cache["wb"] = {n: torch.zeros(NB, *sh, dtype=torch.bfloat16, device=self.dev) for n, sh in shapes.items()}
-            wb, p = cache["wb"], self.p
-            dst, src, tset = [], [], set()
-            for i in range(NB):
-                bp = f"e_block_{i}."
-                for n, t in (("W3", p[bp + "ff_linear3.weight"]), ("W4", p[bp + "ff_linear4.weight"]), ("Wed", p[bp + "equi_update.input_lin.weight"][:, 512:640]),
-                             ("Wro", p[f"edge_{i}.weight"]), ("Wee", p[bp + "edge_emb.weight"]), ("Wte", cache["bufs"]["Wte"][i]),
-                             ("W0", p[bp + "equi_update.coord_mlp.0.weight"]), ("W2", p[bp + "equi_update.coord_mlp.2.weight"]),
-                             ("F1", p[bp + "ff_linear1.weight"]), ("F2", p[bp + "ff_linear2.weight"]), ("Wac", cache["bufs"]["Wac"][i]),
-                             ("Wn", p[f"node_{i}.weight"])):
-                    dst.append(wb[n][i])
-                    src.append(t)
-                # transposed copies ([in][out]): the B operands of the input-gradient products of the fused backward kernels
-                for n, t in (("W0T", p[bp + "equi_update.coord_mlp.0.weight"]), ("WedT", p[bp + "equi_update.input_lin.weight"][:, 512:640]),
-                             ("WroT", p[f"edge_{i}.weight"]), ("W4T", p[bp + "ff_linear4.weight"]), ("W3T", p[bp + "ff_linear3.weight"]),
-                             ("WacT", cache["bufs"]["Wac"][i]), ("WnT", p[f"node_{i}.weight"]), ("F2T", p[bp + "ff_linear2.weight"]),
-                             ("F1T", p[bp + "ff_linear1.weight"])):
-                    tset.add(len(dst))
-                    dst.append(wb[n][i])
-                    src.append(t)
+                cache["wb"] = {n: torch.zeros(NB, *sh, dtype=torch.bfloat16, device=self.dev) for n, sh, _, _ in BF16_WEIGHTS}
+            wb = cache["wb"]
+            dst = [wb[n][i] for i in range(NB) for n, _, _, _ in BF16_WEIGHTS]
+            src = [_bf16_source(s_, i, self.p, cache["bufs"]) for i in range(NB) for _, _, s_, _ in BF16_WEIGHTS]
+            tset = {j for j in range(len(dst)) if BF16_WEIGHTS[j % len(BF16_WEIGHTS)][3]}
             pack_bf16_pieces(self.lib, self.dev, dst, src, cache, "table_bf16", self.ops._s(), key_t=tset)
             self.wb = wb
-        return cache
 
-    def scatter_cat_grads(self, gw):
-        """Gradients of the concatenated buffers -> the parameters' gradient buffers (input_lin's edge part and bias are written directly)."""
+    def scatter_cat_grads(self, g, gw):
+        """Gradients of the concatenated buffers -> the parameters' gradient buffers (input_lin's edge part and bias are written directly).
+        ``g``: the gradients the backward has handed out so far, ``gw``: its way to the buffer of one it has not."""
         _, pieces = self.cat_plan()
         tgt = {}
         for _, _, pname in pieces:
             name = pname[0] if isinstance(pname, tuple) else pname
             if name not in tgt:
-                tgt[name] = gw(name) if name not in self._gw_done else self._gw_done[name]
+                tgt[name] = g[name] if name in g else gw(name)
         src, dst = self._piece_views(self.dcat, tgt)
         copy_pieces(self.lib, self.dev, dst, src, self._cat_cache, "table_bwd", self.ops._s())
-
-    def _geom_fwd(self, TL, pos, ada, dist_off, prefix, X, ldx, col0, xs, d2s):
-        E._check(self.lib.dst_geom_fwd(C.byref(TL.c), E._ptr(pos), E._ptr(ada), C.c_int64(ADA), C.c_int32(dist_off),
-                                       E._ptr(self.p[prefix + "means.weight"]), E._ptr(self.p[prefix + "stds.weight"]),
-                                       C.c_void_p(X.data_ptr() + 4 * col0), C.c_int64(ldx), E._ptr(xs), E._ptr(d2s), self.ops._s()), "dst_geom_fwd")
-
-    def _geom_bwd(self, TL, pos, ada, d_ada, dist_off, prefix, xs, d2s, g1, g2, dms, dd2, dpos):
-        E._check(self.lib.dst_geom_bwd(C.byref(TL.c), E._ptr(pos), E._ptr(ada), E._ptr(d_ada), C.c_int64(ADA), C.c_int32(dist_off),
-                                       E._ptr(self.p[prefix + "means.weight"]), E._ptr(self.p[prefix + "stds.weight"]), E._ptr(xs), E._ptr(d2s),
-                                       E._ptr(g1), C.c_int64(g1.shape[1]), E._ptr(g2), C.c_int64(0 if g2 is None else g2.shape[1]), E._ptr(dms),
-                                       E._ptr(dd2), E._ptr(dpos), self.ops._s()), "dst_geom_bwd")
 
     # ------------------------------------------------------------------ forward
     def forward(self, TL: TrainLayout, xn, ex, noise_level, ctx_emb, cond_n=None, cond_e=None, save: bool = True):
@@ -619,9 +667,7 @@ class DmtTrainGraph:
         edge_pred [Pp,2]) and keeps the tape in ``self.t`` when ``save``."""
         o, p, lib = self.ops, self.p, self.lib
         B, Nn, Pp = TL.B, TL.Nn, TL.Pp
-        D = 2 * Pp
-        t: Dict[str, object] = dict(TL=TL, first=cond_n is None, drop=(self.dropout_p, self.dropout_seed))
-        dp, dseed = self.dropout_p, self.dropout_seed
+        t: Dict[str, object] = dict(TL=TL, first=cond_n is None, drop=(self.dropout_p, self.dropout_seed), bound=(self.p, self.gbuf))
         s = self.ops._s
         # ---- time embedding + adaLN table (dmt.py:249-257,353-357; every *time_mlp)
         tf = self.f(B, 17)
@@ -631,7 +677,7 @@ class DmtTrainGraph:
         o.lin_fwd(mv(tg), mv(p["time_mlp.3.weight"]), p["time_mlp.3.bias"], mv(temb))
         o.axpy(1.0, ctx_emb, temb)                                                       # time_emb = time_mlp(noise_level) + context
         o.act_fwd(temb, st, SILU)
-        if getattr(self, "cat", None) is None:
+        if self.cat is None:
             self.prepare_weights()
         cat = self.cat
         ada = self.f(B, ADA)
@@ -649,7 +695,7 @@ class DmtTrainGraph:
             X0p[:, 2:4] = cond_e
             cpos = cond_n[:, 0:3].contiguous()
             xs0, d2c = self.f(Pp), self.f(Pp)
-            self._geom_fwd(TL, cpos, ada, ADA_TOP, "dist_layer.", X0p, 68, 4, xs0, d2c)
+            o.geom_fwd(TL, cpos, ada, ADA_TOP, p["dist_layer.means.weight"], p["dist_layer.stds.weight"], X0p, 68, 4, xs0, d2c)
             adj = torch.empty(Pp, dtype=torch.int32, device=self.dev)
             E._check(lib.dst_adj_bits(E._ptr(cond_e), C.c_int64(cond_e.shape[1]), E._ptr(d2c), C.c_float(self.edge_th), C.c_float(self.cutoff), C.c_int32(Pp),
                                       E._ptr(adj), s()), "dst_adj_bits")
@@ -661,147 +707,19 @@ class DmtTrainGraph:
         t.update(X0n=X0n, X0p=X0p, xs0=xs0, d2c=d2c, adj=adj, h0=h, e0=e)
         node_hids, edge_hids = [h], [e]
         blocks = []
-        ns = bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and o.main_stream is not None
-        sec = o.node_section if ns else contextlib.nullcontext
+        ns, _ = o.stream_modes()
         # fused row chains: bf16 mode only (their products are bf16 MFMAs; the fp32 mode keeps the per-operation kernels golden G13 / G17 pin)
         fused_chain = bool(o.bf16) and Pp > 0 and os.environ.get("DIFFSPECTRA_FUSED_CHAIN", "1") != "0"
         t.update(node_stream=ns, fused_chain=fused_chain)        # the backward walks this tape with the same choices
-        for i in range(NB):
-            bp = f"e_block_{i}."
-            a0 = i * ADA_STRIDE
+        for k in BLOCKS:
+            # (the tape of a block is kept in every mode: with the node stream nothing a block touched may be freed - and handed out
+            # again - before the join below)
             bt: Dict[str, object] = dict(pos_in=pos, h_in=h, e_in=e)
-            ap = bp + "attn_mpnn."
-            # node rows, in front of the attention (dmt.py:148; layers.py:131-140): adaLN modulate, q | k | v as one product (the padding
-            # columns come out as exact zeros) - on the node stream, beside the pair rows' geometry and embedding
-            with sec():
-                hn, st_n1 = self.f(Nn, 256), self.f(Nn, 2)
-                o.lnmod_fwd(h, 256, TL.node_off, 1, B, ada, a0 + NODE_OFF + 0, a0 + NODE_OFF + 256, hn, st_n1)
-                qkv = self.f(Nn, 768)
-                o.lin_fwd(mv(hn), mv(cat["Wqkv"][i]), cat["bqkv"][i], mv(qkv))
-            # distances + CondGaussian features, edge embedding (dmt.py:136-139)
-            if fused_chain:
-                # dmt.py:136-139,145-149 + both lin_edge projections as ONE kernel (csrc/ds_train_chain.hip)
-                X1, te = self.f(Pp, 128), self.f(Pp, 512)
-                outs = dict(X1=X1, te=te)
-                if save:
-                    outs.update(xs=self.f(Pp), d2=self.f(Pp), e1=self.f(Pp, 64), st=self.f(Pp, 2), en=self.f(Pp, 64))
-                o.pair_front_fwd(TL, pos, ada, a0 + DIST_OFF, a0 + EDGE_OFF + 0, a0 + EDGE_OFF + 64, p[bp + "dist_layer.means.weight"],
-                                 p[bp + "dist_layer.stds.weight"], e, self.wb["Wee"][i], p[bp + "edge_emb.bias"], self.wb["Wte"][i], outs)
-                xs, d2, e1, st_e1, en = (outs.get(k) for k in ("xs", "d2", "e1", "st", "en"))
-            else:
-                X1, xs, d2 = self.f(Pp, 128), self.f(Pp), self.f(Pp)
-                self._geom_fwd(TL, pos, ada, a0 + DIST_OFF, bp + "dist_layer.", X1, 128, 0, xs, d2)
-                X1[:, 64:128] = e
-                e1 = self.f(Pp, 64)
-                o.lin_fwd(mv(X1), mv(p[bp + "edge_emb.weight"]), p[bp + "edge_emb.bias"], mv(e1))
-                en, st_e1 = self.f(Pp, 64), self.f(Pp, 2)
-                o.lnmod_fwd(e1, 64, TL.pair_off, 1, B, ada, a0 + EDGE_OFF + 0, a0 + EDGE_OFF + 64, en, st_e1)
-                te = self.f(Pp, 512)                                     # tanh(lin_edge0 e) | tanh(lin_edge1 e) as one product; columns 252..255 = tanh(0)
-                o.lin_fwd(mv(en), mv(cat["Wte"][i]), None, mv(te), act=TANH)
-            te0, te1 = te[:, 0:256], te[:, 256:512]
-            # attention (layers.py:131-186)
-            if ns:
-                o.main_wait()                                        # q | k | v
-            attn, alpha = self.f(Nn, 256), self.f(max(D, 1), 16)
-            E._check(lib.dst_attn_fwd(C.byref(TL.c), E._ptr(qkv), E._ptr(te0), E._ptr(te1), C.c_int64(512), E._ptr(adj), E._ptr(attn), E._ptr(alpha), s()),
-                     "dst_attn_fwd")
-            # node stream (dmt.py:156-163): node2edge per node first (the pair rows wait for it), then the gated residual and the FF, the
-            # node parts of input_lin and the read-out slice
-            with sec():
-                u = self.f(Nn, 64)
-                o.lin_fwd(mv(attn), mv(p[bp + "node2edge_lin.weight"]), None, mv(u))
-                ev_u = o.node_event() if ns else None
-                if fused_chain:
-                    # dmt.py:113-116,158-163,387 + the node parts of input_lin as ONE kernel (csrc/ds_train_chain.hip): the directed rows wait
-                    # for `ac` at the end of this chain
-                    h_out, ac, rn = self.f(Nn, 256), self.f(Nn, 512), self.f(Nn, 64)
-                    outs = dict(h_out=h_out, ac=ac, rn=rn)
-                    if save:
-                        outs.update(x1=self.f(Nn, 256), st=self.f(Nn, 2), y1=self.f(Nn, 256), f1=self.f(Nn, 512), s1=self.f(Nn, 512), f2=self.f(Nn, 256))
-                    o.node_chain_fwd(TL, h, attn, ada, a0 + NODE_OFF + 512, a0 + NODE_OFF + 768, a0 + NODE_OFF + 1024, a0 + NODE_OFF + 1280,
-                                     self.wb["F1"][i], p[bp + "ff_linear1.bias"], self.wb["F2"][i], p[bp + "ff_linear2.bias"], self.wb["Wac"][i],
-                                     self.wb["Wn"][i], p[f"node_{i}.bias"], (dp, dseed, 4 * i + 0, 4 * i + 1), outs)
-                    x1, st_n2, y1, f1, s1, f2 = (outs.get(k) for k in ("x1", "st", "y1", "f1", "s1", "f2"))
-                    ev_ac = o.node_event() if ns else None
-                else:
-                    x1, y1, st_n2 = self.f(Nn, 256), self.f(Nn, 256), self.f(Nn, 2)
-                    o.gate_add_fwd(h, attn, 256, TL.node_off, 1, B, ada, a0 + NODE_OFF + 512, x1)
-                    o.lnmod_fwd(x1, 256, TL.node_off, 1, B, ada, a0 + NODE_OFF + 768, a0 + NODE_OFF + 1024, y1, st_n2)
-                    f1, s1, f2, h_out = self.f(Nn, 512), self.f(Nn, 512), self.f(Nn, 256), self.f(Nn, 256)
-                    # dmt.py:114-116: dropout(act(ff_linear1)) and dropout(ff_linear2) where the GEMMs produce them (f1 = pre-activation, kept)
-                    o.lin_fwd(mv(y1), mv(p[bp + "ff_linear1.weight"]), p[bp + "ff_linear1.bias"], mv(f1), act=SILU, out2=mv(s1), drop=(dp, dseed, 4 * i + 0, 512))
-                    o.lin_fwd(mv(s1), mv(p[bp + "ff_linear2.weight"]), p[bp + "ff_linear2.bias"], mv(f2), drop=(dp, dseed, 4 * i + 1, 256))
-                    o.gate_add_fwd(y1, f2, 256, TL.node_off, 1, B, ada, a0 + NODE_OFF + 1280, h_out)
-                    ac = self.f(Nn, 512)                                 # h_row | h_col parts of input_lin as one product
-                    o.lin_fwd(mv(h_out), mv(cat["Wac"][i]), None, mv(ac))
-                    ev_ac = o.node_event() if ns else None
-                    rn = self.f(Nn, 64)                                  # per-block read-out features (dmt.py:387)
-                    o.lin_fwd(mv(h_out), mv(p[f"node_{i}.weight"]), p[f"node_{i}.bias"], mv(rn))
-            # edge stream (dmt.py:156-157,165-169)
-            if ns:
-                o.main_wait(ev_u)
-            Win = p[bp + "equi_update.input_lin.weight"]                       # [256, 640] = [h_row | h_col | e | dist]
-            if fused_chain:
-                # dmt.py:156-157,165-169,388 + the edge part of input_lin as ONE kernel (csrc/ds_train_chain.hip); a forward without a tape
-                # (the self-conditioning pass) writes only what the rest of the forward reads
-                e_out, ed, re_ = self.f(Pp, 64), self.f(Pp, 256), self.f(Pp, 16)
-                outs = dict(e_out=e_out, ed=ed, ro=re_)
-                if save:
-                    outs.update(he=self.f(Pp, 64), xe1=self.f(Pp, 64), st=self.f(Pp, 2), ye1=self.f(Pp, 64), f3=self.f(Pp, 128), s3=self.f(Pp, 128),
-                                f4=self.f(Pp, 64), X2=self.f(Pp, 128))
-                o.pair_chain_fwd(TL, u, p[bp + "node2edge_lin.bias"], e, X1, 128, ada, a0 + EDGE_OFF + 128, a0 + EDGE_OFF + 192, a0 + EDGE_OFF + 256,
-                                 a0 + EDGE_OFF + 320, self.wb["W3"][i], p[bp + "ff_linear3.bias"], self.wb["W4"][i],
-                                 p[bp + "ff_linear4.bias"], self.wb["Wed"][i], 128, p[bp + "equi_update.input_lin.bias"], self.wb["Wro"][i],
-                                 p[f"edge_{i}.bias"], (dp, dseed, 4 * i + 2, 4 * i + 3), outs)
-                he, xe1, st_e2, ye1, f3, s3, f4, X2 = (outs.get(k) for k in ("he", "xe1", "st", "ye1", "f3", "s3", "f4", "X2"))
-            else:
-                he = self.f(Pp, 64)
-                E._check(lib.dst_pair_sum_fwd(C.byref(TL.c), E._ptr(u), C.c_int32(64), E._ptr(p[bp + "node2edge_lin.bias"]), E._ptr(he), s()), "dst_pair_sum_fwd")
-                xe1, ye1, st_e2 = self.f(Pp, 64), self.f(Pp, 64), self.f(Pp, 2)
-                o.gate_add_fwd(e, he, 64, TL.pair_off, 1, B, ada, a0 + EDGE_OFF + 128, xe1)
-                o.lnmod_fwd(xe1, 64, TL.pair_off, 1, B, ada, a0 + EDGE_OFF + 192, a0 + EDGE_OFF + 256, ye1, st_e2)
-                f3, s3, f4, e_out = self.f(Pp, 128), self.f(Pp, 128), self.f(Pp, 64), self.f(Pp, 64)
-                o.lin_fwd(mv(ye1), mv(p[bp + "ff_linear3.weight"]), p[bp + "ff_linear3.bias"], mv(f3), act=SILU, out2=mv(s3), drop=(dp, dseed, 4 * i + 2, 128))
-                o.lin_fwd(mv(s3), mv(p[bp + "ff_linear4.weight"]), p[bp + "ff_linear4.bias"], mv(f4), drop=(dp, dseed, 4 * i + 3, 64))
-                o.gate_add_fwd(ye1, f4, 64, TL.pair_off, 1, B, ada, a0 + EDGE_OFF + 320, e_out)
-                # equivariant update (dmt.py:37-60) + CoM removal (:385-386)
-                X2 = self.f(Pp, 128)
-                X2[:, 0:64] = e_out
-                X2[:, 64:128] = X1[:, 0:64]
-                ed = self.f(Pp, 256)
-                o.lin_fwd(mv(X2), mv(Win, 512, 640), p[bp + "equi_update.input_lin.bias"], mv(ed))
-                re_ = self.f(Pp, 16)                                     # per-block read-out features (dmt.py:388)
-                o.lin_fwd(mv(e_out), mv(p[f"edge_{i}.weight"]), p[f"edge_{i}.bias"], mv(re_))
-            if ns:
-                o.main_wait(ev_ac)
-            if fused_chain:
-                # dmt.py:37-48: z of both directions, LayerNorm + modulate, coord_mlp as ONE kernel (csrc/ds_train_chain.hip)
-                c2 = self.f(max(D, 1), 3)
-                outs = dict(c2=c2)
-                if save:
-                    outs.update(zz=self.f(D, 256), st=self.f(D, 2), zn=self.f(D, 256), c0=self.f(D, 256), sc0=self.f(D, 256))
-                o.dir_chain_fwd(TL, ac, ed, ada, a0 + EQUI_OFF + 0, a0 + EQUI_OFF + 256, self.wb["W0"][i],
-                                p[bp + "equi_update.coord_mlp.0.bias"], self.wb["W2"][i], outs)
-                zz, st_z, zn, c0, sc0 = (outs.get(k) for k in ("zz", "st", "zn", "c0", "sc0"))
-            else:
-                zz, zn, st_z = self.f(max(D, 1), 256), self.f(max(D, 1), 256), self.f(max(D, 1), 2)
-                E._check(lib.dst_zbuild_fwd(C.byref(TL.c), E._ptr(ac), E._ptr(ed), E._ptr(zz), s()), "dst_zbuild_fwd")
-                o.lnmod_fwd(zz, 256, TL.pair_off, 2, B, ada, a0 + EQUI_OFF + 0, a0 + EQUI_OFF + 256, zn, st_z)
-                c0, sc0, c2 = self.f(max(D, 1), 256), self.f(max(D, 1), 256), self.f(max(D, 1), 3)
-                o.lin_fwd(mv(zn, r1=D), mv(p[bp + "equi_update.coord_mlp.0.weight"]), p[bp + "equi_update.coord_mlp.0.bias"], mv(c0, r1=D), act=SILU,
-                          out2=mv(sc0, r1=D))
-                o.lin_fwd(mv(sc0, r1=D), mv(p[bp + "equi_update.coord_mlp.2.weight"]), None, mv(c2, r1=D))
-            pos_out = self.f(Nn, 3)
-            E._check(lib.dst_coord_fwd(C.byref(TL.c), E._ptr(pos), E._ptr(c2), E._ptr(adj), E._ptr(p[bp + "equi_update.coord_norm.scale"]),
-                                       E._ptr(pos_out), s()), "dst_coord_fwd")
-            node_hids.append(rn)
-            edge_hids.append(re_)
-            # (kept in every mode: with the node stream nothing a block touched may be freed - and handed out again - before the join below)
-            bt.update(X1=X1, xs=xs, d2=d2, e1=e1, hn=hn, st_n1=st_n1, en=en, st_e1=st_e1, qkv=qkv, te=te, attn=attn, alpha=alpha,
-                      u=u, he=he, x1=x1, y1=y1, st_n2=st_n2, f1=f1, s1=s1, f2=f2, h_out=h_out, xe1=xe1, ye1=ye1, st_e2=st_e2, f3=f3, s3=s3,
-                      f4=f4, e_out=e_out, X2=X2, zz=zz, zn=zn, st_z=st_z, c0=c0, sc0=sc0, c2=c2, ac=ac, ed=ed, rn=rn, re_=re_)
+            pos = self._block_fwd(t, k, bt, save)
+            h, e = bt["h_out"], bt["e_out"]
+            node_hids.append(bt["rn"])
+            edge_hids.append(bt["re_"])
             blocks.append(bt)
-            pos, h, e = pos_out, h_out, e_out
         if ns:
             o.main_wait()                                            # join: the last block's node rows and read-out slices
         # ---- read-out MLPs (dmt.py:391-394)
@@ -824,28 +742,189 @@ class DmtTrainGraph:
             self.t = t
         return pos, atom_pred, edge_pred
 
+    # ---- one block, forward.  ``t``: the pass so far (layout, adaLN table, adjacency bits, stream and chain choices), ``k``: the block's slots,
+    #      ``bt``: its tape, holding pos_in / h_in / e_in on entry and every tensor the block made on return.  The stream choreography is here
+    #      and only here; the row chains it orders follow in their two forms - ``_fused``: one dst_*_chain_* launch (csrc/ds_train_chain.hip),
+    #      ``_ops``: the per-operation kernels - which read and write the same entries of ``bt``.  A fused chain without ``save`` (the
+    #      self-conditioning pass) writes only what the rest of the forward reads; the tape-only entries are then absent.
+    def _block_fwd(self, t, k: BlockSlots, bt, save: bool):
+        o, p, lib, s = self.ops, self.p, self.lib, self.ops._s
+        TL, ada, adj, ns, drop = t["TL"], t["ada"], t["adj"], t["node_stream"], t["drop"]
+        Nn, D = TL.Nn, 2 * TL.Pp
+        sec = o.node_section if ns else contextlib.nullcontext
+        pair_front, node_rear, pair_rear, dir_rows = ((self._pair_front_fwd_fused, self._node_rear_fwd_fused, self._pair_rear_fwd_fused, self._dir_fwd_fused)
+                                                      if t["fused_chain"] else
+                                                      (self._pair_front_fwd_ops, self._node_rear_fwd_ops, self._pair_rear_fwd_ops, self._dir_fwd_ops))
+        # node rows in front of the attention on the node stream, beside the pair rows' geometry and embedding
+        with sec():
+            self._node_front_fwd(TL, ada, k, bt)
+        pair_front(TL, ada, k, bt, save)
+        te = bt["te"]
+        # attention (layers.py:131-186)
+        if ns:
+            o.main_wait()                                        # q | k | v
+        attn, alpha = self.f(Nn, 256), self.f(max(D, 1), 16)
+        E._check(lib.dst_attn_fwd(C.byref(TL.c), E._ptr(bt["qkv"]), E._ptr(te[:, 0:256]), E._ptr(te[:, 256:512]), C.c_int64(512), E._ptr(adj), E._ptr(attn),
+                                  E._ptr(alpha), s()), "dst_attn_fwd")
+        bt.update(attn=attn, alpha=alpha)
+        # node stream (dmt.py:156-163): node2edge per node first (the pair rows wait for it), then the node rows behind the attention (the
+        # directed rows wait for their `ac`, not for the read-out slice behind it)
+        with sec():
+            u = bt["u"] = self.f(Nn, 64)
+            o.lin_fwd(mv(attn), mv(p[k.bp + "node2edge_lin.weight"]), None, mv(u))
+            ev_u = o.node_event() if ns else None
+            ev_ac = node_rear(TL, ada, k, bt, drop, save, o.node_event if ns else (lambda: None))
+        # edge stream (dmt.py:156-157,165-169)
+        if ns:
+            o.main_wait(ev_u)
+        pair_rear(TL, ada, k, bt, drop, save)
+        if ns:
+            o.main_wait(ev_ac)
+        dir_rows(TL, ada, k, bt, save)
+        pos_out = self.f(Nn, 3)
+        E._check(lib.dst_coord_fwd(C.byref(TL.c), E._ptr(bt["pos_in"]), E._ptr(bt["c2"]), E._ptr(adj), E._ptr(p[k.bp + "equi_update.coord_norm.scale"]),
+                                   E._ptr(pos_out), s()), "dst_coord_fwd")
+        return pos_out
+
+    def _node_front_fwd(self, TL, ada, k, bt):
+        """Node rows in front of the attention (dmt.py:148; layers.py:131-140): adaLN modulate, q | k | v as one product (the padding columns
+        come out as exact zeros).  Tape: hn, st_n1, qkv."""
+        o, cat, i = self.ops, self.cat, k.i
+        hn, st_n1 = self.f(TL.Nn, 256), self.f(TL.Nn, 2)
+        o.lnmod_fwd(bt["h_in"], 256, TL.node_off, 1, TL.B, ada, *k.node.ln1, hn, st_n1)
+        qkv = self.f(TL.Nn, 768)
+        o.lin_fwd(mv(hn), mv(cat["Wqkv"][i]), cat["bqkv"][i], mv(qkv))
+        bt.update(hn=hn, st_n1=st_n1, qkv=qkv)
+
+    # pair rows in front of the attention: distances + CondGaussian features, edge embedding, adaLN modulate, both lin_edge projections
+    # (dmt.py:136-139,145-149).  Tape: X1, te and xs, d2, e1, st_e1, en.
+    def _pair_front_fwd_fused(self, TL, ada, k, bt, save):
+        p, bp, i, Pp = self.p, k.bp, k.i, TL.Pp
+        bt.update(X1=self.f(Pp, 128), te=self.f(Pp, 512))
+        if save:
+            bt.update(xs=self.f(Pp), d2=self.f(Pp), e1=self.f(Pp, 64), st_e1=self.f(Pp, 2), en=self.f(Pp, 64))
+        self.ops.pair_front_fwd(TL, bt["pos_in"], ada, k.dist, *k.edge.ln1, p[bp + "dist_layer.means.weight"], p[bp + "dist_layer.stds.weight"], bt["e_in"],
+                                self.wb["Wee"][i], p[bp + "edge_emb.bias"], self.wb["Wte"][i], bt)
+
+    def _pair_front_fwd_ops(self, TL, ada, k, bt, save):
+        o, p, bp, Pp = self.ops, self.p, k.bp, TL.Pp
+        X1, xs, d2 = self.f(Pp, 128), self.f(Pp), self.f(Pp)
+        o.geom_fwd(TL, bt["pos_in"], ada, k.dist, p[bp + "dist_layer.means.weight"], p[bp + "dist_layer.stds.weight"], X1, 128, 0, xs, d2)
+        X1[:, 64:128] = bt["e_in"]
+        e1 = self.f(Pp, 64)
+        o.lin_fwd(mv(X1), mv(p[bp + "edge_emb.weight"]), p[bp + "edge_emb.bias"], mv(e1))
+        en, st_e1 = self.f(Pp, 64), self.f(Pp, 2)
+        o.lnmod_fwd(e1, 64, TL.pair_off, 1, TL.B, ada, *k.edge.ln1, en, st_e1)
+        te = self.f(Pp, 512)                                     # tanh(lin_edge0 e) | tanh(lin_edge1 e) as one product; columns 252..255 = tanh(0)
+        o.lin_fwd(mv(en), mv(self.cat["Wte"][k.i]), None, mv(te), act=TANH)
+        bt.update(X1=X1, te=te, xs=xs, d2=d2, e1=e1, st_e1=st_e1, en=en)
+
+    # node rows behind the attention: gated residual, LayerNorm + modulate, the FF with its two dropouts, gated residual, the node parts of
+    # input_lin and the read-out slice (dmt.py:113-116,158-163,387).  ``drop = (p, seed)``; returns ``ac_ready()``, called once `ac` is in the
+    # stream (the node stream's event for it).  Tape: h_out, ac, rn and x1, st_n2, y1, f1, s1, f2.
+    def _node_rear_fwd_fused(self, TL, ada, k, bt, drop, save, ac_ready):
+        p, wb, bp, i, Nn = self.p, self.wb, k.bp, k.i, TL.Nn
+        bt.update(h_out=self.f(Nn, 256), ac=self.f(Nn, 512), rn=self.f(Nn, 64))
+        if save:
+            bt.update(x1=self.f(Nn, 256), st_n2=self.f(Nn, 2), y1=self.f(Nn, 256), f1=self.f(Nn, 512), s1=self.f(Nn, 512), f2=self.f(Nn, 256))
+        self.ops.node_chain_fwd(TL, bt["h_in"], bt["attn"], ada, k.node.gate1, *k.node.ln2, k.node.gate2, wb["F1"][i], p[bp + "ff_linear1.bias"],
+                                wb["F2"][i], p[bp + "ff_linear2.bias"], wb["Wac"][i], wb["Wn"][i], p[f"node_{i}.bias"],
+                                (*drop, k.drop(0)[0], k.drop(1)[0]), bt)
+        return ac_ready()
+
+    def _node_rear_fwd_ops(self, TL, ada, k, bt, drop, save, ac_ready):
+        o, p, bp, i, B, Nn = self.ops, self.p, k.bp, k.i, TL.B, TL.Nn
+        x1, y1, st_n2 = self.f(Nn, 256), self.f(Nn, 256), self.f(Nn, 2)
+        o.gate_add_fwd(bt["h_in"], bt["attn"], 256, TL.node_off, 1, B, ada, k.node.gate1, x1)
+        o.lnmod_fwd(x1, 256, TL.node_off, 1, B, ada, *k.node.ln2, y1, st_n2)
+        f1, s1, f2, h_out = self.f(Nn, 512), self.f(Nn, 512), self.f(Nn, 256), self.f(Nn, 256)
+        # dmt.py:114-116: dropout(act(ff_linear1)) and dropout(ff_linear2) where the GEMMs produce them (f1 = pre-activation, kept)
+        o.lin_fwd(mv(y1), mv(p[bp + "ff_linear1.weight"]), p[bp + "ff_linear1.bias"], mv(f1), act=SILU, out2=mv(s1), drop=(*drop, *k.drop(0)))
+        o.lin_fwd(mv(s1), mv(p[bp + "ff_linear2.weight"]), p[bp + "ff_linear2.bias"], mv(f2), drop=(*drop, *k.drop(1)))
+        o.gate_add_fwd(y1, f2, 256, TL.node_off, 1, B, ada, k.node.gate2, h_out)
+        ac = self.f(Nn, 512)                                 # h_row | h_col parts of input_lin as one product
+        o.lin_fwd(mv(h_out), mv(self.cat["Wac"][i]), None, mv(ac))
+        ev_ac = ac_ready()
+        rn = self.f(Nn, 64)                                  # per-block read-out features (dmt.py:387)
+        o.lin_fwd(mv(h_out), mv(p[f"node_{i}.weight"]), p[f"node_{i}.bias"], mv(rn))
+        bt.update(h_out=h_out, ac=ac, rn=rn, x1=x1, st_n2=st_n2, y1=y1, f1=f1, s1=s1, f2=f2)
+        return ev_ac
+
+    # pair rows behind the attention: node2edge sum, gated residual, LayerNorm + modulate, the FF with its two dropouts, gated residual, the
+    # edge part of input_lin and the read-out slice (dmt.py:156-157,165-169,388).  Tape: e_out, ed, re_ and he, xe1, st_e2, ye1, f3, s3, f4, X2.
+    def _pair_rear_fwd_fused(self, TL, ada, k, bt, drop, save):
+        p, wb, bp, i, Pp = self.p, self.wb, k.bp, k.i, TL.Pp
+        bt.update(e_out=self.f(Pp, 64), ed=self.f(Pp, 256), re_=self.f(Pp, 16))
+        if save:
+            bt.update(he=self.f(Pp, 64), xe1=self.f(Pp, 64), st_e2=self.f(Pp, 2), ye1=self.f(Pp, 64), f3=self.f(Pp, 128), s3=self.f(Pp, 128),
+                      f4=self.f(Pp, 64), X2=self.f(Pp, 128))
+        self.ops.pair_chain_fwd(TL, bt["u"], p[bp + "node2edge_lin.bias"], bt["e_in"], bt["X1"], 128, ada, k.edge.gate1, *k.edge.ln2, k.edge.gate2,
+                                wb["W3"][i], p[bp + "ff_linear3.bias"], wb["W4"][i], p[bp + "ff_linear4.bias"], wb["Wed"][i], 128,
+                                p[bp + "equi_update.input_lin.bias"], wb["Wro"][i], p[f"edge_{i}.bias"], (*drop, k.drop(2)[0], k.drop(3)[0]), bt)
+
+    def _pair_rear_fwd_ops(self, TL, ada, k, bt, drop, save):
+        o, p, bp, i, B, Pp = self.ops, self.p, k.bp, k.i, TL.B, TL.Pp
+        he = self.f(Pp, 64)
+        E._check(self.lib.dst_pair_sum_fwd(C.byref(TL.c), E._ptr(bt["u"]), C.c_int32(64), E._ptr(p[bp + "node2edge_lin.bias"]), E._ptr(he), o._s()),
+                 "dst_pair_sum_fwd")
+        xe1, ye1, st_e2 = self.f(Pp, 64), self.f(Pp, 64), self.f(Pp, 2)
+        o.gate_add_fwd(bt["e_in"], he, 64, TL.pair_off, 1, B, ada, k.edge.gate1, xe1)
+        o.lnmod_fwd(xe1, 64, TL.pair_off, 1, B, ada, *k.edge.ln2, ye1, st_e2)
+        f3, s3, f4, e_out = self.f(Pp, 128), self.f(Pp, 128), self.f(Pp, 64), self.f(Pp, 64)
+        o.lin_fwd(mv(ye1), mv(p[bp + "ff_linear3.weight"]), p[bp + "ff_linear3.bias"], mv(f3), act=SILU, out2=mv(s3), drop=(*drop, *k.drop(2)))
+        o.lin_fwd(mv(s3), mv(p[bp + "ff_linear4.weight"]), p[bp + "ff_linear4.bias"], mv(f4), drop=(*drop, *k.drop(3)))
+        o.gate_add_fwd(ye1, f4, 64, TL.pair_off, 1, B, ada, k.edge.gate2, e_out)
+        # the input of the equivariant update (dmt.py:37-60): e_out | distance features
+        X2 = self.f(Pp, 128)
+        X2[:, 0:64] = e_out
+        X2[:, 64:128] = bt["X1"][:, 0:64]
+        ed = self.f(Pp, 256)
+        Win = p[bp + "equi_update.input_lin.weight"]                       # [256, 640] = [h_row | h_col | e | dist]
+        o.lin_fwd(mv(X2), mv(Win, 512, 640), p[bp + "equi_update.input_lin.bias"], mv(ed))
+        re_ = self.f(Pp, 16)                                     # per-block read-out features (dmt.py:388)
+        o.lin_fwd(mv(e_out), mv(p[f"edge_{i}.weight"]), p[f"edge_{i}.bias"], mv(re_))
+        bt.update(e_out=e_out, ed=ed, re_=re_, he=he, xe1=xe1, st_e2=st_e2, ye1=ye1, f3=f3, s3=s3, f4=f4, X2=X2)
+
+    # directed rows (dmt.py:37-48): z of both directions, LayerNorm + modulate, coord_mlp.  Tape: c2 and zz, st_z, zn, c0, sc0.
+    def _dir_fwd_fused(self, TL, ada, k, bt, save):
+        D = 2 * TL.Pp
+        bt["c2"] = self.f(max(D, 1), 3)
+        if save:
+            bt.update(zz=self.f(D, 256), st_z=self.f(D, 2), zn=self.f(D, 256), c0=self.f(D, 256), sc0=self.f(D, 256))
+        self.ops.dir_chain_fwd(TL, bt["ac"], bt["ed"], ada, *k.equi_ln, self.wb["W0"][k.i], self.p[k.bp + "equi_update.coord_mlp.0.bias"],
+                               self.wb["W2"][k.i], bt)
+
+    def _dir_fwd_ops(self, TL, ada, k, bt, save):
+        o, p, bp = self.ops, self.p, k.bp
+        D = 2 * TL.Pp
+        zz, zn, st_z = self.f(max(D, 1), 256), self.f(max(D, 1), 256), self.f(max(D, 1), 2)
+        E._check(self.lib.dst_zbuild_fwd(C.byref(TL.c), E._ptr(bt["ac"]), E._ptr(bt["ed"]), E._ptr(zz), o._s()), "dst_zbuild_fwd")
+        o.lnmod_fwd(zz, 256, TL.pair_off, 2, TL.B, ada, *k.equi_ln, zn, st_z)
+        c0, sc0, c2 = self.f(max(D, 1), 256), self.f(max(D, 1), 256), self.f(max(D, 1), 3)
+        o.lin_fwd(mv(zn, r1=D), mv(p[bp + "equi_update.coord_mlp.0.weight"]), p[bp + "equi_update.coord_mlp.0.bias"], mv(c0, r1=D), act=SILU,
+                  out2=mv(sc0, r1=D))
+        o.lin_fwd(mv(sc0, r1=D), mv(p[bp + "equi_update.coord_mlp.2.weight"]), None, mv(c2, r1=D))
+        bt.update(c2=c2, zz=zz, st_z=st_z, zn=zn, c0=c0, sc0=sc0)
+
     # ------------------------------------------------------------------ backward
     def backward(self, dpos, datom, dedge) -> Dict[str, torch.Tensor]:
         """Gradients of every DMT parameter (and ``ctx_emb`` under the key ``'@ctx_emb'``) given the gradients of the three outputs."""
-        o, p, lib, t = self.ops, self.p, self.lib, self.t
+        t = self.t
+        self.bind(*t["bound"])                              # the parameters and the stage of the forward that wrote this tape
+        o, p, lib, gbuf = self.ops, self.p, self.lib, self.gbuf
         TL: TrainLayout = t["TL"]
         B, Nn, Pp = TL.B, TL.Nn, TL.Pp
-        D = 2 * Pp
         s = self.ops._s
         ada = t["ada"]
-        dp, dseed = t["drop"]
         g: Dict[str, torch.Tensor] = {}
-
-        gbuf = getattr(self, "gbuf", None)
         cat, dcat = self.cat, self.dcat
-        self._gw_done = g
 
         def gw(name):                                       # gradient buffer of a parameter: a view of the trainer's flat stage (zeroed once
             g[name] = gbuf[name] if gbuf is not None else torch.zeros_like(p[name])   # per backward) or, stand-alone, a fresh zero tensor
             return g[name]
 
         d_ada = self.z(B, ADA)
-        o.async_dw = bool(int(os.environ.get("DIFFSPECTRA_ASYNC_DW", "1")))
+        _, o.async_dw = o.stream_modes()
         # ---- read-out MLPs
         dAH, dEH = self.f(Nn, 768), self.f(Pp, 192)
 
@@ -866,138 +945,9 @@ class DmtTrainGraph:
         # ---- blocks, last to first
         dh = self.z(Nn, 256)             # gradient of the block output h (later: block input of the next one)
         de = self.z(Pp, 64)
-        dpos_out = dpos
         dd2_buf = self.f(max(Pp, 1))
-        ns = t["node_stream"]
-        sec = o.node_section if ns else contextlib.nullcontext
-        # the fused forward's tape feeds the fused backward kernels (the pair- and directed-row kernels take a CU's LDS alone,
-        # csrc/ds_train_chain.hip CHAIN_BWD_LDS: sharing a CU with a weight-gradient product they were not bit-reproducible)
-        fused_chain = t["fused_chain"]
-        for i in reversed(range(NB)):
-            bt = t["blocks"][i]
-            bp = f"e_block_{i}."
-            a0 = i * ADA_STRIDE
-            ap = bp + "attn_mpnn."
-            # read-out features of this block (node rows on the node stream, here and below: see forward)
-            drn, dre = mv(dAH, 256 + 64 * i, 256 + 64 * (i + 1)), mv(dEH, 64 + 16 * i, 64 + 16 * (i + 1))
-            with sec():
-                o.lin_bwd_w(drn, mv(bt["h_out"]), mv(gw(f"node_{i}.weight")), gw(f"node_{i}.bias"))
-                if not fused_chain:                               # (fused: inside dst_node_chain_bwd)
-                    o.lin_bwd_x(drn, mv(p[f"node_{i}.weight"]), mv(dh), acc=True)
-            o.lin_bwd_w(dre, mv(bt["e_out"]), mv(gw(f"edge_{i}.weight")), gw(f"edge_{i}.bias"))
-            if not fused_chain:                                  # (fused: inside dst_pair_chain_bwd)
-                o.lin_bwd_x(dre, mv(p[f"edge_{i}.weight"]), mv(de), acc=True)
-            # equivariant update
-            dpos_in, dc2 = self.f(Nn, 3), self.f(max(D, 1), 3)
-            dsp, dms_buf = self.f(B), self.f(B, 128)          # per block: their column sums (parameter gradients) run on the side stream
-            E._check(lib.dst_coord_bwd(C.byref(TL.c), E._ptr(bt["pos_in"]), E._ptr(bt["c2"]), E._ptr(t["adj"]), E._ptr(p[bp + "equi_update.coord_norm.scale"]),
-                                       E._ptr(dpos_out), E._ptr(dpos_in), E._ptr(dc2), E._ptr(dsp), s()), "dst_coord_bwd")
-            o.colsum(mv(dsp.view(B, 1)), gw(bp + "equi_update.coord_norm.scale"), param_grad=True)
-            Win = p[bp + "equi_update.input_lin.weight"]
-            dWin = gw(bp + "equi_update.input_lin.weight")
-            o.lin_bwd_w(mv(dc2, r1=D), mv(bt["sc0"], r1=D), mv(gw(bp + "equi_update.coord_mlp.2.weight")))
-            dc0 = self.f(max(D, 1), 256)
-            dz = self.f(max(D, 1), 256)                      # (not dc0: the coord_mlp.0 weight gradient may still be reading it on the side stream)
-            if fused_chain:
-                # coord_mlp.2's and coord_mlp.0's input gradients and the LayerNorm backward as ONE kernel (csrc/ds_train_chain.hip)
-                o.dir_chain_bwd(TL, dc2, bt["c0"], bt["zz"], bt["st_z"], ada, d_ada, a0 + EQUI_OFF + 0, a0 + EQUI_OFF + 256,
-                                p[bp + "equi_update.coord_mlp.2.weight"], self.wb["W0T"][i], dc0, dz)
-                o.lin_bwd_w(mv(dc0, r1=D), mv(bt["zn"], r1=D), mv(gw(bp + "equi_update.coord_mlp.0.weight")), gw(bp + "equi_update.coord_mlp.0.bias"))
-            else:
-                o.lin_bwd_x(mv(dc2, r1=D), mv(p[bp + "equi_update.coord_mlp.2.weight"]), mv(dc0, r1=D), dact=SILU, ref=mv(bt["c0"], r1=D))
-                o.lin_bwd_w(mv(dc0, r1=D), mv(bt["zn"], r1=D), mv(gw(bp + "equi_update.coord_mlp.0.weight")), gw(bp + "equi_update.coord_mlp.0.bias"))
-                dzn = self.f(max(D, 1), 256)
-                o.lin_bwd_x(mv(dc0, r1=D), mv(p[bp + "equi_update.coord_mlp.0.weight"]), mv(dzn, r1=D))
-                o.lnmod_bwd(dzn, bt["zz"], bt["st_z"], 256, TL.pair_off, 2, B, ada, d_ada, a0 + EQUI_OFF + 0, a0 + EQUI_OFF + 256, dz, False)
-            dac, ded = self.f(Nn, 512), self.f(Pp, 256)
-            E._check(lib.dst_zbuild_bwd(C.byref(TL.c), E._ptr(dz), E._ptr(dac), E._ptr(ded), s()), "dst_zbuild_bwd")
-            # node stream (the section waits for dac)
-            with sec():
-                o.lin_bwd_w(mv(dac), mv(bt["h_out"]), mv(dcat["Wac"][i]))           # both node parts at once; scattered into dWin[:, 0:512] at the end
-                if fused_chain:
-                    # the five input gradients, both gated residuals and the LayerNorm backward of the node chain as ONE kernel (csrc/ds_train_chain.hip)
-                    df2, df1, dh_in, dattn = self.f(Nn, 256), self.f(Nn, 512), self.f(Nn, 256), self.f(Nn, 256)
-                    o.node_chain_bwd(TL, dh, dAH.data_ptr() + 4 * (256 + 64 * i), 768, dac, bt["f2"], bt["f1"], bt["x1"], bt["st_n2"], bt["attn"], ada, d_ada,
-                                     a0 + NODE_OFF + 512, a0 + NODE_OFF + 768, a0 + NODE_OFF + 1024, a0 + NODE_OFF + 1280, self.wb["WacT"][i], self.wb["WnT"][i],
-                                     self.wb["F2T"][i], self.wb["F1T"][i], (dp, dseed, 4 * i + 0, 4 * i + 1), df2, df1, dh_in, dattn)
-                    o.lin_bwd_w(mv(df2), mv(bt["s1"]), mv(gw(bp + "ff_linear2.weight")), gw(bp + "ff_linear2.bias"))
-                    o.lin_bwd_w(mv(df1), mv(bt["y1"]), mv(gw(bp + "ff_linear1.weight")), gw(bp + "ff_linear1.bias"))
-                else:
-                    o.lin_bwd_x(mv(dac), mv(cat["Wac"][i]), mv(dh), acc=True)
-                    dy1, df2 = self.f(Nn, 256), self.f(Nn, 256)
-                    o.gate_add_bwd(dh, bt["f2"], 256, TL.node_off, 1, B, ada, d_ada, a0 + NODE_OFF + 1280, dy1, False, df2, drop=(dp, dseed, 4 * i + 1))
-                    o.lin_bwd_w(mv(df2), mv(bt["s1"]), mv(gw(bp + "ff_linear2.weight")), gw(bp + "ff_linear2.bias"))
-                    df1 = self.f(Nn, 512)
-                    o.lin_bwd_x(mv(df2), mv(p[bp + "ff_linear2.weight"]), mv(df1), dact=SILU, ref=mv(bt["f1"]), drop=(dp, dseed, 4 * i + 0, 512))
-                    o.lin_bwd_w(mv(df1), mv(bt["y1"]), mv(gw(bp + "ff_linear1.weight")), gw(bp + "ff_linear1.bias"))
-                    o.lin_bwd_x(mv(df1), mv(p[bp + "ff_linear1.weight"]), mv(dy1), acc=True)
-                    dx1 = self.f(Nn, 256)
-                    o.lnmod_bwd(dy1, bt["x1"], bt["st_n2"], 256, TL.node_off, 1, B, ada, d_ada, a0 + NODE_OFF + 768, a0 + NODE_OFF + 1024, dx1, False)
-                    dh_in, dattn = self.f(Nn, 256), self.f(Nn, 256)
-                    o.gate_add_bwd(dx1, bt["attn"], 256, TL.node_off, 1, B, ada, d_ada, a0 + NODE_OFF + 512, dh_in, False, dattn)
-            # edge stream
-            o.lin_bwd_w(mv(ded), mv(bt["X2"]), mv(dWin, 512, 640), gw(bp + "equi_update.input_lin.bias"))
-            if fused_chain:
-                # the five input gradients, both gated residuals and the LayerNorm backward of the rear chain as ONE kernel (csrc/ds_train_chain.hip)
-                dfeat2, df4, df3, de_in, dhe = self.f(Pp, 64), self.f(Pp, 64), self.f(Pp, 128), self.f(Pp, 64), self.f(Pp, 64)
-                o.pair_chain_bwd(TL, de, dEH.data_ptr() + 4 * (64 + 16 * i), 192, ded, bt["f4"], bt["f3"], bt["xe1"], bt["st_e2"], bt["he"], ada, d_ada,
-                                 a0 + EDGE_OFF + 128, a0 + EDGE_OFF + 192, a0 + EDGE_OFF + 256, a0 + EDGE_OFF + 320, self.wb["WedT"][i], self.wb["WroT"][i],
-                                 self.wb["W4T"][i], self.wb["W3T"][i], (dp, dseed, 4 * i + 2, 4 * i + 3), dfeat2, df4, df3, de_in, dhe)
-                o.lin_bwd_w(mv(df4), mv(bt["s3"]), mv(gw(bp + "ff_linear4.weight")), gw(bp + "ff_linear4.bias"))
-                o.lin_bwd_w(mv(df3), mv(bt["ye1"]), mv(gw(bp + "ff_linear3.weight")), gw(bp + "ff_linear3.bias"))
-            else:
-                o.lin_bwd_x(mv(ded), mv(Win, 512, 576), mv(de), acc=True)
-                dfeat2 = self.f(Pp, 64)
-                o.lin_bwd_x(mv(ded), mv(Win, 576, 640), mv(dfeat2))
-                dye1, df4 = self.f(Pp, 64), self.f(Pp, 64)
-                o.gate_add_bwd(de, bt["f4"], 64, TL.pair_off, 1, B, ada, d_ada, a0 + EDGE_OFF + 320, dye1, False, df4, drop=(dp, dseed, 4 * i + 3))
-                o.lin_bwd_w(mv(df4), mv(bt["s3"]), mv(gw(bp + "ff_linear4.weight")), gw(bp + "ff_linear4.bias"))
-                df3 = self.f(Pp, 128)
-                o.lin_bwd_x(mv(df4), mv(p[bp + "ff_linear4.weight"]), mv(df3), dact=SILU, ref=mv(bt["f3"]), drop=(dp, dseed, 4 * i + 2, 128))
-                o.lin_bwd_w(mv(df3), mv(bt["ye1"]), mv(gw(bp + "ff_linear3.weight")), gw(bp + "ff_linear3.bias"))
-                o.lin_bwd_x(mv(df3), mv(p[bp + "ff_linear3.weight"]), mv(dye1), acc=True)
-                dxe1 = self.f(Pp, 64)
-                o.lnmod_bwd(dye1, bt["xe1"], bt["st_e2"], 64, TL.pair_off, 1, B, ada, d_ada, a0 + EDGE_OFF + 192, a0 + EDGE_OFF + 256, dxe1, False)
-                de_in, dhe = self.f(Pp, 64), self.f(Pp, 64)
-                o.gate_add_bwd(dxe1, bt["he"], 64, TL.pair_off, 1, B, ada, d_ada, a0 + EDGE_OFF + 128, de_in, False, dhe)
-            # node2edge
-            du = self.f(Nn, 64)
-            E._check(lib.dst_pair_sum_bwd(C.byref(TL.c), E._ptr(dhe), C.c_int32(64), E._ptr(du), C.c_int32(0), s()), "dst_pair_sum_bwd")
-            o.colsum(mv(dhe), gw(bp + "node2edge_lin.bias"), param_grad=True)
-            with sec():                                                              # (waits for du)
-                o.lin_bwd_w(mv(du), mv(bt["attn"]), mv(gw(bp + "node2edge_lin.weight")))
-                o.lin_bwd_x(mv(du), mv(p[bp + "node2edge_lin.weight"]), mv(dattn), acc=True)
-            if ns:
-                o.main_wait()                                                        # dattn
-            # attention
-            dqkv, dte = self.f(Nn, 768), self.f(Pp, 512)
-            te = bt["te"]
-            E._check(lib.dst_attn_bwd(C.byref(TL.c), E._ptr(bt["qkv"]), E._ptr(te[:, 0:256]), E._ptr(te[:, 256:512]), C.c_int64(512), E._ptr(bt["alpha"]),
-                                      E._ptr(dattn), E._ptr(dqkv), E._ptr(dte[:, 0:256]), E._ptr(dte[:, 256:512]), C.c_int32(1), E._ptr(o.scratch),
-                                      C.c_int64(o.scratch.numel()), s()), "dst_attn_bwd")
-            with sec():                                                              # (waits for dqkv) q | k | v and the adaLN modulate of the block input
-                dhn = self.f(Nn, 256)
-                o.lin_bwd_w(mv(dqkv), mv(bt["hn"]), mv(dcat["Wqkv"][i]), dcat["bqkv"][i])
-                o.lin_bwd_x(mv(dqkv), mv(cat["Wqkv"][i]), mv(dhn))
-                o.lnmod_bwd(dhn, bt["h_in"], bt["st_n1"], 256, TL.node_off, 1, B, ada, d_ada, a0 + NODE_OFF + 0, a0 + NODE_OFF + 256, dh_in, True)
-            o.lin_bwd_w(mv(dte), mv(bt["en"]), mv(dcat["Wte"][i]))                  # lin_edge0 | lin_edge1; dte is already in front of the tanh (te_is_tanh)
-            den = self.f(Pp, 64)
-            o.lin_bwd_x(mv(dte), mv(cat["Wte"][i]), mv(den))
-            de1 = self.f(Pp, 64)
-            o.lnmod_bwd(den, bt["e1"], bt["st_e1"], 64, TL.pair_off, 1, B, ada, d_ada, a0 + EDGE_OFF + 0, a0 + EDGE_OFF + 64, de1, False)
-            # edge embedding + distance features
-            o.lin_bwd_w(mv(de1), mv(bt["X1"]), mv(gw(bp + "edge_emb.weight")), gw(bp + "edge_emb.bias"))
-            dfeat1 = self.f(Pp, 64)
-            Wee = p[bp + "edge_emb.weight"]
-            o.lin_bwd_x(mv(de1), mv(Wee, 0, 64), mv(dfeat1))
-            o.lin_bwd_x(mv(de1), mv(Wee, 64, 128), mv(de_in), acc=True)
-            self._geom_bwd(TL, bt["pos_in"], ada, d_ada, a0 + DIST_OFF, bp + "dist_layer.", bt["xs"], bt["d2"], dfeat1, dfeat2, dms_buf, dd2_buf, dpos_in)
-            o.colsum(mv(dms_buf, 1, 64), gw(bp + "dist_layer.means.weight").view(-1), param_grad=True)      # lane k of the kernel = feature k = Gaussian k - 1
-            o.colsum(mv(dms_buf, 65, 128), gw(bp + "dist_layer.stds.weight").view(-1), param_grad=True)
-            if ns:
-                o.main_wait()           # end of the block: everything the node stream was given precedes what the main stream does next, so this
-                                        # block's temporaries may be released (and handed out again) when the next block rebinds their names
-            dh, de, dpos_out = dh_in, de_in, dpos_in
+        for k in reversed(BLOCKS):
+            dh, de, dpos = self._block_bwd(t, k, gw, d_ada, dAH, dEH, dd2_buf, dh, de, dpos)
         # ---- input embeddings
         o.lin_bwd_w(mv(dh), mv(t["X0n"]), mv(gw("node_emb.weight")), gw("node_emb.bias"))
         o.lin_bwd_w(mv(dAH, 0, 256), mv(t["X0n"]), mv(g["node_emb.weight"]), g["node_emb.bias"], acc=True)
@@ -1010,7 +960,8 @@ class DmtTrainGraph:
             o.lin_bwd_x(mv(de), mv(p["edge_emb.weight"], 4, 68), mv(dfeat0))
             o.lin_bwd_x(mv(dEH, 0, 64), mv(p["edge_emb.weight"], 4, 68), mv(dfeat0), acc=True)
             dms_top = self.f(B, 128)                         # (block 0's buffer may still be feeding its column sums on the side stream)
-            self._geom_bwd(TL, t["cpos"], ada, d_ada, ADA_TOP, "dist_layer.", t["xs0"], t["d2c"], dfeat0, None, dms_top, dd2_buf, None)
+            o.geom_bwd(TL, t["cpos"], ada, d_ada, ADA_TOP, p["dist_layer.means.weight"], p["dist_layer.stds.weight"], t["xs0"], t["d2c"], dfeat0, None,
+                       dms_top, dd2_buf, None)
             o.colsum(mv(dms_top, 1, 64), g["dist_layer.means.weight"].view(-1))
             o.colsum(mv(dms_top, 65, 128), g["dist_layer.stds.weight"].view(-1))
         # ---- adaLN table + time embedding
@@ -1028,9 +979,181 @@ class DmtTrainGraph:
                                        E._ptr(gw("time_mlp.0.weights")), s()), "dst_time_feat_bwd")
         o.join_dw()                                          # the concatenated gradients are read right here, on the main stream
         o.async_dw = False
-        self.scatter_cat_grads(gw)
+        self.scatter_cat_grads(g, gw)
         self.t = None
         return g
+
+    # ---- one block, backward: (dh, de, dpos_out) of its outputs -> the gradients of its inputs; ``dAH`` / ``dEH`` hold the gradients of its
+    #      read-out slices.  As in the forward, the streams are ordered here and the row chains follow in their two forms; the fused
+    #      forward's tape feeds the fused backward kernels (the pair- and directed-row kernels take a CU's LDS alone, csrc/ds_train_chain.hip
+    #      CHAIN_BWD_LDS: sharing a CU with a weight-gradient product they were not bit-reproducible).  Node rows run on the node stream.
+    def _block_bwd(self, t, k: BlockSlots, gw, d_ada, dAH, dEH, dd2_buf, dh, de, dpos_out):
+        o, p, lib, s = self.ops, self.p, self.lib, self.ops._s
+        cat, dcat, bp, i = self.cat, self.dcat, k.bp, k.i
+        TL, ada, ns, fused, drop, bt = t["TL"], t["ada"], t["node_stream"], t["fused_chain"], t["drop"], t["blocks"][k.i]
+        B, Nn, Pp = TL.B, TL.Nn, TL.Pp
+        D = 2 * Pp
+        sec = o.node_section if ns else contextlib.nullcontext
+        keep: list = []                                  # what only a node section touched: not freed before the closing wait of the block
+        dir_rows, node_rear, pair_rear = ((self._dir_bwd_fused, self._node_rear_bwd_fused, self._pair_rear_bwd_fused) if fused else
+                                          (self._dir_bwd_ops, self._node_rear_bwd_ops, self._pair_rear_bwd_ops))
+        # read-out features of this block: their weight gradients here; their input gradients are part of the fused chains, the
+        # per-operation chains find them added to dh / de
+        drn, dre = mv(dAH, 256 + 64 * i, 256 + 64 * (i + 1)), mv(dEH, 64 + 16 * i, 64 + 16 * (i + 1))
+        with sec():
+            o.lin_bwd_w(drn, mv(bt["h_out"]), mv(gw(f"node_{i}.weight")), gw(f"node_{i}.bias"))
+            if not fused:
+                o.lin_bwd_x(drn, mv(p[f"node_{i}.weight"]), mv(dh), acc=True)
+        o.lin_bwd_w(dre, mv(bt["e_out"]), mv(gw(f"edge_{i}.weight")), gw(f"edge_{i}.bias"))
+        if not fused:
+            o.lin_bwd_x(dre, mv(p[f"edge_{i}.weight"]), mv(de), acc=True)
+        # equivariant update
+        dpos_in, dc2 = self.f(Nn, 3), self.f(max(D, 1), 3)
+        dsp, dms_buf = self.f(B), self.f(B, 128)          # per block: their column sums (parameter gradients) run on the side stream
+        E._check(lib.dst_coord_bwd(C.byref(TL.c), E._ptr(bt["pos_in"]), E._ptr(bt["c2"]), E._ptr(t["adj"]), E._ptr(p[bp + "equi_update.coord_norm.scale"]),
+                                   E._ptr(dpos_out), E._ptr(dpos_in), E._ptr(dc2), E._ptr(dsp), s()), "dst_coord_bwd")
+        o.colsum(mv(dsp.view(B, 1)), gw(bp + "equi_update.coord_norm.scale"), param_grad=True)
+        dWin = gw(bp + "equi_update.input_lin.weight")
+        o.lin_bwd_w(mv(dc2, r1=D), mv(bt["sc0"], r1=D), mv(gw(bp + "equi_update.coord_mlp.2.weight")))
+        dz = dir_rows(TL, ada, d_ada, k, bt, gw, dc2)
+        dac, ded = self.f(Nn, 512), self.f(Pp, 256)
+        E._check(lib.dst_zbuild_bwd(C.byref(TL.c), E._ptr(dz), E._ptr(dac), E._ptr(ded), s()), "dst_zbuild_bwd")
+        # node stream (the section waits for dac)
+        with sec():
+            o.lin_bwd_w(mv(dac), mv(bt["h_out"]), mv(dcat["Wac"][i]))           # both node parts at once; scattered into dWin[:, 0:512] at the end
+            dh_in, dattn = node_rear(TL, ada, d_ada, k, bt, gw, drop, dh, dAH.data_ptr() + 4 * (256 + 64 * i), dac, keep)
+        # edge stream
+        o.lin_bwd_w(mv(ded), mv(bt["X2"]), mv(dWin, 512, 640), gw(bp + "equi_update.input_lin.bias"))
+        dfeat2, de_in, dhe = pair_rear(TL, ada, d_ada, k, bt, gw, drop, de, dEH.data_ptr() + 4 * (64 + 16 * i), ded)
+        # node2edge
+        du = self.f(Nn, 64)
+        E._check(lib.dst_pair_sum_bwd(C.byref(TL.c), E._ptr(dhe), C.c_int32(64), E._ptr(du), C.c_int32(0), s()), "dst_pair_sum_bwd")
+        o.colsum(mv(dhe), gw(bp + "node2edge_lin.bias"), param_grad=True)
+        with sec():                                                              # (waits for du)
+            o.lin_bwd_w(mv(du), mv(bt["attn"]), mv(gw(bp + "node2edge_lin.weight")))
+            o.lin_bwd_x(mv(du), mv(p[bp + "node2edge_lin.weight"]), mv(dattn), acc=True)
+        if ns:
+            o.main_wait()                                                        # dattn
+        # attention
+        dqkv, dte = self.f(Nn, 768), self.f(Pp, 512)
+        te = bt["te"]
+        E._check(lib.dst_attn_bwd(C.byref(TL.c), E._ptr(bt["qkv"]), E._ptr(te[:, 0:256]), E._ptr(te[:, 256:512]), C.c_int64(512), E._ptr(bt["alpha"]),
+                                  E._ptr(dattn), E._ptr(dqkv), E._ptr(dte[:, 0:256]), E._ptr(dte[:, 256:512]), C.c_int32(1), E._ptr(o.scratch),
+                                  C.c_int64(o.scratch.numel()), s()), "dst_attn_bwd")
+        with sec():                                                              # (waits for dqkv) q | k | v and the adaLN modulate of the block input
+            dhn = self.f(Nn, 256)
+            o.lin_bwd_w(mv(dqkv), mv(bt["hn"]), mv(dcat["Wqkv"][i]), dcat["bqkv"][i])
+            o.lin_bwd_x(mv(dqkv), mv(cat["Wqkv"][i]), mv(dhn))
+            o.lnmod_bwd(dhn, bt["h_in"], bt["st_n1"], 256, TL.node_off, 1, B, ada, d_ada, *k.node.ln1, dh_in, True)
+        self._pair_front_bwd(TL, ada, d_ada, k, bt, gw, dte, dfeat2, de_in, dms_buf, dd2_buf, dpos_in)
+        if ns:
+            o.main_wait()           # end of the block: everything the node stream was given precedes what the main stream does next, so this
+                                    # block's temporaries (the locals here, ``keep``) may be released - and handed out again - on return
+        return dh_in, de_in, dpos_in
+
+    def _pair_front_bwd(self, TL, ada, d_ada, k, bt, gw, dte, dfeat2, de_in, dms_buf, dd2_buf, dpos_in):
+        """Pair rows in front of the attention (one form: both forwards leave the same tape): lin_edge0 | lin_edge1, adaLN modulate, edge
+        embedding (its e part adds to ``de_in``), distance features (``dfeat2``: the gradient of the copy the equivariant update read;
+        adds to ``dpos_in``)."""
+        o, p, bp, Pp = self.ops, self.p, k.bp, TL.Pp
+        o.lin_bwd_w(mv(dte), mv(bt["en"]), mv(self.dcat["Wte"][k.i]))          # lin_edge0 | lin_edge1; dte is already in front of the tanh (te_is_tanh)
+        den = self.f(Pp, 64)
+        o.lin_bwd_x(mv(dte), mv(self.cat["Wte"][k.i]), mv(den))
+        de1 = self.f(Pp, 64)
+        o.lnmod_bwd(den, bt["e1"], bt["st_e1"], 64, TL.pair_off, 1, TL.B, ada, d_ada, *k.edge.ln1, de1, False)
+        # edge embedding + distance features
+        o.lin_bwd_w(mv(de1), mv(bt["X1"]), mv(gw(bp + "edge_emb.weight")), gw(bp + "edge_emb.bias"))
+        dfeat1 = self.f(Pp, 64)
+        Wee = p[bp + "edge_emb.weight"]
+        o.lin_bwd_x(mv(de1), mv(Wee, 0, 64), mv(dfeat1))
+        o.lin_bwd_x(mv(de1), mv(Wee, 64, 128), mv(de_in), acc=True)
+        o.geom_bwd(TL, bt["pos_in"], ada, d_ada, k.dist, p[bp + "dist_layer.means.weight"], p[bp + "dist_layer.stds.weight"], bt["xs"], bt["d2"], dfeat1,
+                   dfeat2, dms_buf, dd2_buf, dpos_in)
+        o.colsum(mv(dms_buf, 1, 64), gw(bp + "dist_layer.means.weight").view(-1), param_grad=True)      # lane k of the kernel = feature k = Gaussian k - 1
+        o.colsum(mv(dms_buf, 65, 128), gw(bp + "dist_layer.stds.weight").view(-1), param_grad=True)
+
+    # directed rows: ``dc2`` -> dz, the gradient of z of both directions; coord_mlp.0's weight gradient
+    def _dir_bwd_fused(self, TL, ada, d_ada, k, bt, gw, dc2):
+        o, bp, D = self.ops, k.bp, 2 * TL.Pp
+        dc0 = self.f(max(D, 1), 256)
+        dz = self.f(max(D, 1), 256)                      # (not dc0: the coord_mlp.0 weight gradient may still be reading it on the side stream)
+        # coord_mlp.2's and coord_mlp.0's input gradients and the LayerNorm backward as ONE kernel
+        o.dir_chain_bwd(TL, dc2, bt["c0"], bt["zz"], bt["st_z"], ada, d_ada, *k.equi_ln, self.p[bp + "equi_update.coord_mlp.2.weight"],
+                        self.wb["W0T"][k.i], dc0, dz)
+        o.lin_bwd_w(mv(dc0, r1=D), mv(bt["zn"], r1=D), mv(gw(bp + "equi_update.coord_mlp.0.weight")), gw(bp + "equi_update.coord_mlp.0.bias"))
+        return dz
+
+    def _dir_bwd_ops(self, TL, ada, d_ada, k, bt, gw, dc2):
+        o, p, bp, D = self.ops, self.p, k.bp, 2 * TL.Pp
+        dc0 = self.f(max(D, 1), 256)
+        dz = self.f(max(D, 1), 256)                      # (not dc0: the coord_mlp.0 weight gradient may still be reading it on the side stream)
+        o.lin_bwd_x(mv(dc2, r1=D), mv(p[bp + "equi_update.coord_mlp.2.weight"]), mv(dc0, r1=D), dact=SILU, ref=mv(bt["c0"], r1=D))
+        o.lin_bwd_w(mv(dc0, r1=D), mv(bt["zn"], r1=D), mv(gw(bp + "equi_update.coord_mlp.0.weight")), gw(bp + "equi_update.coord_mlp.0.bias"))
+        dzn = self.f(max(D, 1), 256)
+        o.lin_bwd_x(mv(dc0, r1=D), mv(p[bp + "equi_update.coord_mlp.0.weight"]), mv(dzn, r1=D))
+        o.lnmod_bwd(dzn, bt["zz"], bt["st_z"], 256, TL.pair_off, 2, TL.B, ada, d_ada, *k.equi_ln, dz, False)
+        return dz
+
+    # node rows behind the attention: ``dh`` (block output), ``drn`` (data pointer of the read-out slice's gradient, row stride 768) and
+    # ``dac`` (node parts of input_lin) -> (dh_in, dattn); the FF weight gradients.  Runs on the node stream: its temporaries go to ``keep``
+    def _node_rear_bwd_fused(self, TL, ada, d_ada, k, bt, gw, drop, dh, drn, dac, keep):
+        o, wb, bp, i, Nn = self.ops, self.wb, k.bp, k.i, TL.Nn
+        # the five input gradients, both gated residuals and the LayerNorm backward of the node chain as ONE kernel
+        df2, df1, dh_in, dattn = self.f(Nn, 256), self.f(Nn, 512), self.f(Nn, 256), self.f(Nn, 256)
+        o.node_chain_bwd(TL, dh, drn, 768, dac, bt["f2"], bt["f1"], bt["x1"], bt["st_n2"], bt["attn"], ada, d_ada, k.node.gate1, *k.node.ln2, k.node.gate2,
+                         wb["WacT"][i], wb["WnT"][i], wb["F2T"][i], wb["F1T"][i], (*drop, k.drop(0)[0], k.drop(1)[0]), df2, df1, dh_in, dattn)
+        o.lin_bwd_w(mv(df2), mv(bt["s1"]), mv(gw(bp + "ff_linear2.weight")), gw(bp + "ff_linear2.bias"))
+        o.lin_bwd_w(mv(df1), mv(bt["y1"]), mv(gw(bp + "ff_linear1.weight")), gw(bp + "ff_linear1.bias"))
+        keep += (df2, df1)
+        return dh_in, dattn
+
+    def _node_rear_bwd_ops(self, TL, ada, d_ada, k, bt, gw, drop, dh, drn, dac, keep):
+        o, p, bp, B, Nn = self.ops, self.p, k.bp, TL.B, TL.Nn                  # (drn: the block has added its input gradient to dh)
+        o.lin_bwd_x(mv(dac), mv(self.cat["Wac"][k.i]), mv(dh), acc=True)
+        dy1, df2 = self.f(Nn, 256), self.f(Nn, 256)
+        o.gate_add_bwd(dh, bt["f2"], 256, TL.node_off, 1, B, ada, d_ada, k.node.gate2, dy1, False, df2, drop=(*drop, k.drop(1)[0]))
+        o.lin_bwd_w(mv(df2), mv(bt["s1"]), mv(gw(bp + "ff_linear2.weight")), gw(bp + "ff_linear2.bias"))
+        df1 = self.f(Nn, 512)
+        o.lin_bwd_x(mv(df2), mv(p[bp + "ff_linear2.weight"]), mv(df1), dact=SILU, ref=mv(bt["f1"]), drop=(*drop, *k.drop(0)))
+        o.lin_bwd_w(mv(df1), mv(bt["y1"]), mv(gw(bp + "ff_linear1.weight")), gw(bp + "ff_linear1.bias"))
+        o.lin_bwd_x(mv(df1), mv(p[bp + "ff_linear1.weight"]), mv(dy1), acc=True)
+        dx1 = self.f(Nn, 256)
+        o.lnmod_bwd(dy1, bt["x1"], bt["st_n2"], 256, TL.node_off, 1, B, ada, d_ada, *k.node.ln2, dx1, False)
+        dh_in, dattn = self.f(Nn, 256), self.f(Nn, 256)
+        o.gate_add_bwd(dx1, bt["attn"], 256, TL.node_off, 1, B, ada, d_ada, k.node.gate1, dh_in, False, dattn)
+        keep += (dy1, df2, df1, dx1)
+        return dh_in, dattn
+
+    # pair rows behind the attention: ``de`` (block output), ``dre`` (data pointer of the read-out slice's gradient, row stride 192) and
+    # ``ded`` (edge part of input_lin) -> (dfeat2, de_in, dhe); the FF weight gradients
+    def _pair_rear_bwd_fused(self, TL, ada, d_ada, k, bt, gw, drop, de, dre, ded):
+        o, wb, bp, i, Pp = self.ops, self.wb, k.bp, k.i, TL.Pp
+        # the five input gradients, both gated residuals and the LayerNorm backward of the rear chain as ONE kernel
+        dfeat2, df4, df3, de_in, dhe = self.f(Pp, 64), self.f(Pp, 64), self.f(Pp, 128), self.f(Pp, 64), self.f(Pp, 64)
+        o.pair_chain_bwd(TL, de, dre, 192, ded, bt["f4"], bt["f3"], bt["xe1"], bt["st_e2"], bt["he"], ada, d_ada, k.edge.gate1, *k.edge.ln2, k.edge.gate2,
+                         wb["WedT"][i], wb["WroT"][i], wb["W4T"][i], wb["W3T"][i], (*drop, k.drop(2)[0], k.drop(3)[0]), dfeat2, df4, df3, de_in, dhe)
+        o.lin_bwd_w(mv(df4), mv(bt["s3"]), mv(gw(bp + "ff_linear4.weight")), gw(bp + "ff_linear4.bias"))
+        o.lin_bwd_w(mv(df3), mv(bt["ye1"]), mv(gw(bp + "ff_linear3.weight")), gw(bp + "ff_linear3.bias"))
+        return dfeat2, de_in, dhe
+
+    def _pair_rear_bwd_ops(self, TL, ada, d_ada, k, bt, gw, drop, de, dre, ded):
+        o, p, bp, B, Pp = self.ops, self.p, k.bp, TL.B, TL.Pp                  # (dre: the block has added its input gradient to de)
+        Win = p[bp + "equi_update.input_lin.weight"]
+        o.lin_bwd_x(mv(ded), mv(Win, 512, 576), mv(de), acc=True)
+        dfeat2 = self.f(Pp, 64)
+        o.lin_bwd_x(mv(ded), mv(Win, 576, 640), mv(dfeat2))
+        dye1, df4 = self.f(Pp, 64), self.f(Pp, 64)
+        o.gate_add_bwd(de, bt["f4"], 64, TL.pair_off, 1, B, ada, d_ada, k.edge.gate2, dye1, False, df4, drop=(*drop, k.drop(3)[0]))
+        o.lin_bwd_w(mv(df4), mv(bt["s3"]), mv(gw(bp + "ff_linear4.weight")), gw(bp + "ff_linear4.bias"))
+        df3 = self.f(Pp, 128)
+        o.lin_bwd_x(mv(df4), mv(p[bp + "ff_linear4.weight"]), mv(df3), dact=SILU, ref=mv(bt["f3"]), drop=(*drop, *k.drop(2)))
+        o.lin_bwd_w(mv(df3), mv(bt["ye1"]), mv(gw(bp + "ff_linear3.weight")), gw(bp + "ff_linear3.bias"))
+        o.lin_bwd_x(mv(df3), mv(p[bp + "ff_linear3.weight"]), mv(dye1), acc=True)
+        dxe1 = self.f(Pp, 64)
+        o.lnmod_bwd(dye1, bt["xe1"], bt["st_e2"], 64, TL.pair_off, 1, B, ada, d_ada, *k.edge.ln2, dxe1, False)
+        de_in, dhe = self.f(Pp, 64), self.f(Pp, 64)
+        o.gate_add_bwd(dxe1, bt["he"], 64, TL.pair_off, 1, B, ada, d_ada, k.edge.gate1, de_in, False, dhe)
+        return dfeat2, de_in, dhe
 
     # ------------------------------------------------------------------ loss
     def loss(self, TL: TrainLayout, pos, atom_pred, edge_pred, tpos, tfeat, tedge, wm, weights=(1.0, 0.25, 0.1)):

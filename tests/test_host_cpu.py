@@ -361,3 +361,60 @@ def test_build_reports_on_stderr_only(tmp_path, capsys):
     assert open(obj + ".flags").read() == "-O3"
     with pytest.raises(FileNotFoundError):                   # a dependency that does not exist is an error, not an empty digest
         g._digest([str(tmp_path / "missing.h")])
+
+
+def test_bf16_weight_table_and_concatenated_weight_plan():
+    """The one table of the fused chains' bf16 weight copies (name, shape, source, transposed) and the plan of the concatenated buffers:
+    pinned to what the kernels were validated with - per block the twelve straight copies, then the nine transposed ones, in this order
+    (it is the order of the device table of ``dst_pack_bf16_pieces``)."""
+    from diffspectra_amd import train_engine as T
+    expected = [("W3", (128, 64), False), ("W4", (64, 128), False), ("Wed", (256, 128), False), ("Wro", (16, 64), False), ("Wee", (64, 128), False),
+                ("Wte", (512, 64), False), ("W0", (256, 256), False), ("W2", (3, 256), False), ("F1", (512, 256), False), ("F2", (256, 512), False),
+                ("Wac", (512, 256), False), ("Wn", (64, 256), False), ("W0T", (256, 256), True), ("WedT", (128, 256), True), ("WroT", (64, 16), True),
+                ("W4T", (128, 64), True), ("W3T", (64, 128), True), ("WacT", (256, 512), True), ("WnT", (256, 64), True), ("F2T", (512, 256), True),
+                ("F1T", (256, 512), True)]
+    assert [(n, sh, tr) for n, sh, _, tr in T.BF16_WEIGHTS] == expected
+    # a transposed copy has the source of the straight one and its shape reversed
+    by_name = {n: (sh, src) for n, sh, src, _ in T.BF16_WEIGHTS}
+    for n, sh, src, tr in T.BF16_WEIGHTS:
+        if tr:
+            straight = {"F1T": "F1", "F2T": "F2"}.get(n, n[:-1])
+            assert by_name[straight] == (sh[::-1], src), n
+    p = {f"e_block_3.{k}.weight": k for k in ("ff_linear3", "equi_update.coord_mlp.0")}
+    p.update({"edge_3.weight": "edge", "node_3.weight": "node"})
+    assert T._bf16_source(by_name["W3"][1], 3, p, {}) == "ff_linear3" and T._bf16_source(by_name["Wro"][1], 3, p, {}) == "edge"
+    assert T._bf16_source(by_name["Wac"][1], 3, p, {"Wac": list("abcdefgh")}) == "d"
+    w = torch.arange(256 * 640.0).reshape(256, 640)
+    assert torch.equal(T._bf16_source(by_name["WedT"][1], 3, {"e_block_3.equi_update.input_lin.weight": w}, {}), w[:, 512:640])
+    bufs, pieces = T.DmtTrainGraph.cat_plan()
+    assert bufs == [("Wada", (T.ADA, 1024)), ("bada", (T.ADA,)), ("Wqkv", (8, 768, 256)), ("bqkv", (8, 768)), ("Wte", (8, 512, 64)), ("Wac", (8, 512, 256))]
+    assert len(pieces) == 8 * 18 + 2
+    for i in range(8):
+        blk = pieces[18 * i:18 * (i + 1)]
+        o = i * T.ADA_STRIDE + T.NODE_OFF
+        assert blk[0] == ("Wada", (slice(o, o + 1536),), f"e_block_{i}.node_time_mlp.1.weight")
+        assert blk[8] == ("Wqkv", (i, slice(0, 252)), f"e_block_{i}.attn_mpnn.lin_query.weight")
+        assert blk[13] == ("bqkv", (i, slice(512, 768)), f"e_block_{i}.attn_mpnn.lin_value.bias")
+        assert blk[14:16] == [("Wte", (i, slice(0, 252)), f"e_block_{i}.attn_mpnn.lin_edge0.weight"),
+                              ("Wte", (i, slice(256, 512)), f"e_block_{i}.attn_mpnn.lin_edge1.weight")]
+        assert blk[-1] == ("Wac", (i, slice(256, 512)), (f"e_block_{i}.equi_update.input_lin.weight", slice(256, 512)))
+        assert [b for b, _, _ in blk] == ["Wada", "bada"] * 4 + ["Wqkv", "bqkv"] * 3 + ["Wte", "Wte", "Wac", "Wac"]
+    assert pieces[-2:] == [("Wada", (slice(T.ADA_TOP, T.ADA_TOP + 2),), "dist_layer.time_mlp.1.weight"),
+                           ("bada", (slice(T.ADA_TOP, T.ADA_TOP + 2),), "dist_layer.time_mlp.1.bias")]
+
+
+def test_block_slots_name_the_adaln_columns_and_dropout_streams():
+    """``train_engine.BLOCKS[i]`` names the columns of the adaLN table and the Philox streams of block ``i`` once, for the forward and the
+    backward in both forms: every slot equals the literal offset the call sites used to spell out."""
+    from diffspectra_amd import train_engine as T
+    assert len(T.BLOCKS) == T.NB == 8
+    for i, k in enumerate(T.BLOCKS):
+        a0 = i * T.ADA_STRIDE
+        n, e, q = a0 + T.NODE_OFF, a0 + T.EDGE_OFF, a0 + T.EQUI_OFF
+        assert (k.i, k.bp) == (i, f"e_block_{i}.")
+        assert (*k.node.ln1, k.node.gate1, *k.node.ln2, k.node.gate2) == (n, n + 256, n + 512, n + 768, n + 1024, n + 1280)
+        assert (*k.edge.ln1, k.edge.gate1, *k.edge.ln2, k.edge.gate2) == (e, e + 64, e + 128, e + 192, e + 256, e + 320)
+        assert k.equi_ln == (q, q + 256) and k.dist == a0 + T.DIST_OFF
+        assert [k.drop(j) for j in range(4)] == [(4 * i, 512), (4 * i + 1, 256), (4 * i + 2, 128), (4 * i + 3, 64)]
+    # the slots of a block lie inside its stride of the table, the last block's below the top-level distance slot
+    assert T.BLOCKS[-1].node.gate2 + 256 <= T.ADA_TOP and T.BLOCKS[-1].edge.gate2 + 64 <= T.ADA_TOP and T.ADA_TOP + 2 <= T.ADA

@@ -311,17 +311,15 @@ def test_geom(ops, gpu_device):
     g1, g2 = torch.randn(P, 70, generator=g), torch.randn(P, 64, generator=g)
     (feat * g1[:, 3:67].double()).sum().backward(retain_graph=True)
     (feat * g2.double()).sum().backward()
-    p = {"x.means.weight": means.detach().float().to(d), "x.stds.weight": stds.detach().float().to(d)}
-    graph = T.DmtTrainGraph.__new__(T.DmtTrainGraph)
-    graph.p, graph.lib, graph.dev, graph.ops = p, o.lib, d, o
+    meansd, stdsd = means.detach().float().to(d), stds.detach().float().to(d)
     X, xs, d2s = torch.zeros(P, 70, device=d), torch.empty(P, device=d), torch.empty(P, device=d)
     posd, adad = pos.detach().float().to(d), ada.detach().float().to(d)
-    graph._geom_fwd(TL, posd, adad, off, "x.", X, 70, 3, xs, d2s)
+    o.geom_fwd(TL, posd, adad, off, meansd, stdsd, X, 70, 3, xs, d2s)
     check(X[:, 3:67], feat, 3e-6, "geom features")
     assert float(X[:, :3].abs().max()) == 0 and float(X[:, 67:].abs().max()) == 0
     d_ada, dms, dd2, dpos = torch.zeros(B, T.ADA, device=d), torch.empty(B, 128, device=d), torch.empty(P, device=d), torch.zeros(Nn, 3, device=d)
     g1d = g1[:, 3:67].contiguous().to(d)
-    graph._geom_bwd(TL, posd, adad, d_ada, off, "x.", xs, d2s, g1d, g2.to(d), dms, dd2, dpos)
+    o.geom_bwd(TL, posd, adad, d_ada, off, meansd, stdsd, xs, d2s, g1d, g2.to(d), dms, dd2, dpos)
     check(dpos, pos.grad, 2e-5, "geom dpos")
     check(d_ada[:, off:off + 2], ada.grad[:, off:off + 2], 2e-5, "geom d(scale, shift)")
     check(dms[:, 1:64].sum(0), means.grad.view(-1), 2e-5, "geom dmeans")
@@ -1300,10 +1298,10 @@ def test_config5_as_benchmarked_against_the_reference_loss(gpu_device, monkeypat
     print(f"[config 5 as benchmarked] loss {float(loss.detach()):.5f} (reference, fp32: {ref_loss:.5f})")
 
 
-def _synthetic_train_batch(Bt, version, seed, d):
-    """A training batch in CollateSpectra's format (build_dataset.py:357-395) from the synthetic size histogram."""
+def _synthetic_train_batch(Bt, version, seed, d, n_atoms=None):
+    """A training batch in CollateSpectra's format (build_dataset.py:357-395) from the synthetic size histogram (or the given sizes)."""
     from diffspectra_amd import filler
-    n_atoms = filler.sample_n_atoms(Bt, seed=seed).tolist()
+    n_atoms = filler.sample_n_atoms(Bt, seed=seed).tolist() if n_atoms is None else list(n_atoms)
     node_mask, edge_mask = filler.masks_from_n_atoms(n_atoms)
     N = node_mask.shape[1]
     g = torch.Generator().manual_seed(100 + seed)
@@ -1317,6 +1315,44 @@ def _synthetic_train_batch(Bt, version, seed, d):
                 atom_one_hot=(F.one_hot(types, 5).float() * node_mask).to(d),
                 edge_one_hot=torch.stack([(order > 0).float(), order / 3.0], -1).to(d), formal_charges=torch.zeros(Bt, N, 1, device=d),
                 context=[c.to(d) for c in ctx] if isinstance(ctx, list) else ctx.to(d))
+
+
+def test_layout_shortcut_tells_two_cpu_batches_apart(gpu_device):
+    """Two consecutive ``loss_fn`` calls on CPU-resident batches of equal shape and different masks.  ``batch["atom_mask"].to(dev)`` is a
+    fresh temporary in every call and the caching allocator gives the second one the address (and version 0) of the first: a shortcut
+    that recognised a mask by its address returned the first batch's layout for the second mask.  The second call must use the layout
+    of its own mask, and its loss must equal - bit for bit - that of a fresh trainer on an identical copy of the model that sees the
+    second batch alone (same seeds right before the call; ``loss_fn`` alone changes no parameter, the step is bit-reproducible)."""
+    import copy
+    import random as _random
+    from diffspectra_amd import losses as Lh
+    from diffspectra_amd.noise_schedule import NoiseScheduleVP
+    d = gpu_device
+    cfg, model = _train_model("ir", d)
+    cfg.model.dropout = 0.1
+    fresh = copy.deepcopy(model)
+    loss_fn = Lh.get_sde_graph_loss_fn(NoiseScheduleVP("cosine", continuous_beta_0=0.1, continuous_beta_1=20.0), True, None, cfg)
+    sizes = ([9, 5, 7, 3], [4, 9, 2, 8])
+    b1, b2 = (_synthetic_train_batch(4, "ir", 1 + k, "cpu", n_atoms=n) for k, n in enumerate(sizes))
+    assert b1["atom_mask"].shape == b2["atom_mask"].shape and not torch.equal(b1["atom_mask"], b2["atom_mask"])
+    assert not b1["atom_mask"].is_cuda and not b2["atom_mask"].is_cuda
+
+    def call(m, batch):
+        torch.manual_seed(31)
+        _random.seed(5)
+        loss = loss_fn(m, batch)
+        torch.cuda.synchronize()
+        return loss.detach().clone(), loss_fn.last["layout"]
+
+    _, TL1 = call(model, b1)
+    assert (TL1.Nn, TL1.Pp) == (24, 70)
+    loss2, TL2 = call(model, b2)
+    print(f"[layout shortcut] second call: Nn {TL2.Nn} Pp {TL2.Pp} (its mask: 23, 71; the first mask: 24, 70), loss {float(loss2)!r}")
+    assert (TL2.Nn, TL2.Pp) == (sum(sizes[1]), sum(n * (n - 1) // 2 for n in sizes[1])) == (23, 71)
+    ref, TLr = call(fresh, b2)
+    print(f"[layout shortcut] fresh trainer on the second batch alone: loss {float(ref)!r}")
+    assert (TLr.Nn, TLr.Pp) == (23, 71)
+    assert torch.equal(loss2, ref), (float(loss2), float(ref))
 
 
 def _train_run(d, version, precision, steps, batches, lr=2e-4, seed=7, perturb=0.0):

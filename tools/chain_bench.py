@@ -41,18 +41,18 @@ def main():
 
     print(f"B {B} Nn {Nn} Pp {Pp}")
     for save in (True, False):
-        outs = dict(e_out=f(Pp, 64), ed=f(Pp, 256), ro=f(Pp, 16))
+        outs = dict(e_out=f(Pp, 64), ed=f(Pp, 256), re_=f(Pp, 16))
         if save:
-            outs.update(he=f(Pp, 64), xe1=f(Pp, 64), st=f(Pp, 2), ye1=f(Pp, 64), f3=f(Pp, 128), s3=f(Pp, 128), f4=f(Pp, 64), X2=f(Pp, 128))
+            outs.update(he=f(Pp, 64), xe1=f(Pp, 64), st_e2=f(Pp, 2), ye1=f(Pp, 64), f3=f(Pp, 128), s3=f(Pp, 128), f4=f(Pp, 64), X2=f(Pp, 128))
         run(f"pair_chain_fwd save={save}", lambda: o.pair_chain_fwd(TL, u, n2eb, e, X1, 128, ada, EDGE_OFF + 128, EDGE_OFF + 192, EDGE_OFF + 256, EDGE_OFF + 320,
                                                                    W3, b3, W4, b4, Wedb, 128, bed, Wro, bro, (0.1, 1234, 2, 3), outs))
         outs = dict(X1=f(Pp, 128), te=f(Pp, 512))
         if save:
-            outs.update(xs=f(Pp), d2=f(Pp), e1=f(Pp, 64), st=f(Pp, 2), en=f(Pp, 64))
+            outs.update(xs=f(Pp), d2=f(Pp), e1=f(Pp, 64), st_e1=f(Pp, 2), en=f(Pp, 64))
         run(f"pair_front_fwd save={save}", lambda: o.pair_front_fwd(TL, pos, ada, DIST_OFF, EDGE_OFF, EDGE_OFF + 64, means, stds, e, Wee, bee, Wte, outs))
         outs = dict(c2=f(D, 3))
         if save:
-            outs.update(zz=f(D, 256), st=f(D, 2), zn=f(D, 256), c0=f(D, 256), sc0=f(D, 256))
+            outs.update(zz=f(D, 256), st_z=f(D, 2), zn=f(D, 256), c0=f(D, 256), sc0=f(D, 256))
         run(f"dir_chain_fwd save={save}", lambda: o.dir_chain_fwd(TL, ac, ed, ada, EQUI_OFF, EQUI_OFF + 256, W0, b0, W2, outs))
 
 

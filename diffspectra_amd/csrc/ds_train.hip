@@ -10,6 +10,7 @@
 
 #include "../../include/diffspectra_hip.h"
 #include "../../include/diffspectra_train.h"
+#include "ds_svd3.h"
 #include "ds_train_common.h"
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
@@ -937,55 +938,7 @@ __global__ __launch_bounds__(256) void k_prepare_batch(dst_layout L, const float
   for (int it = threadIdx.x; it < np * 2; it += 256) ex[(int64_t)p0 * 2 + it] = (edge[(int64_t)p0 * 2 + it] * 2.0f - 1.0f) / edge_norm;
 }
 
-// 3x3 SVD by one-sided Jacobi on columns (fp64): A V = U S.
-__device__ void svd3(const double A[3][3], double U[3][3], double S[3], double V[3][3]) {
-  double W[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) { W[i][j] = A[i][j]; V[i][j] = (i == j) ? 1.0 : 0.0; }
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double al = 0, be = 0, ga = 0;
-        for (int i = 0; i < 3; ++i) { al += W[i][p] * W[i][p]; be += W[i][q] * W[i][q]; ga += W[i][p] * W[i][q]; }
-        off = fmax(off, fabs(ga) / (sqrt(al * be) + 1e-300));
-        if (fabs(ga) < 1e-300) continue;
-        const double zeta = (be - al) / (2.0 * ga);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int i = 0; i < 3; ++i) {
-          const double wp = W[i][p], wq = W[i][q];
-          W[i][p] = c * wp - s * wq; W[i][q] = s * wp + c * wq;
-          const double vp = V[i][p], vq = V[i][q];
-          V[i][p] = c * vp - s * vq; V[i][q] = s * vp + c * vq;
-        }
-      }
-    if (off < 1e-15) break;
-  }
-  for (int j = 0; j < 3; ++j) {
-    S[j] = sqrt(W[0][j] * W[0][j] + W[1][j] * W[1][j] + W[2][j] * W[2][j]);
-    for (int i = 0; i < 3; ++i) U[i][j] = S[j] > 1e-300 ? W[i][j] / S[j] : 0.0;
-  }
-  // sort singular values descending (the sign correction of Kabsch acts on the smallest one)
-  for (int a = 0; a < 2; ++a)
-    for (int b = a + 1; b < 3; ++b)
-      if (S[b] > S[a]) {
-        const double ts = S[a]; S[a] = S[b]; S[b] = ts;
-        for (int i = 0; i < 3; ++i) {
-          const double tu = U[i][a]; U[i][a] = U[i][b]; U[i][b] = tu;
-          const double tv = V[i][a]; V[i][a] = V[i][b]; V[i][b] = tv;
-        }
-      }
-  // complete a rank-deficient U to an orthonormal basis (columns with zero singular value)
-  if (S[2] <= 1e-300 * 0 + 1e-14 * (S[0] + 1e-300)) {
-    if (S[1] > 1e-14 * (S[0] + 1e-300)) {
-      U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-      U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-      U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-    }
-  }
-}
-
+// svd3 (3x3 fp64 Jacobi SVD): ds_svd3.h, shared with the structure metric of ds_match.hip
 __global__ __launch_bounds__(64) void k_kabsch(dst_layout L, const float* __restrict__ pred, int64_t ldp, const float* __restrict__ tar, int64_t ldt,
                                                 float* __restrict__ rot, float* __restrict__ aligned) {
   __shared__ float R[9];

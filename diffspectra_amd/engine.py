@@ -378,6 +378,55 @@ class Workspace:
         self.c = DsWorkspace(**{k: v.data_ptr() for k, v in self.t.items()})
 
 
+# ----------------------------------------------------------------------------------------- structure metric
+
+RECORD_BYTES = CONSTS["DS_RECORD_BYTES"]
+
+
+def match_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                  ref_index: Optional[torch.Tensor] = None, max_distance: float = 5.0, min_atoms: int = 3):
+    """``ds_match_records``: Hungarian-matched RMSD, type / bond accuracy and the exact-graph flag of P (generated, ground-truth) pairs.
+
+    ``prb_rec [P, 1248] u8`` / ``ref_rec [M, 1248] u8``: records in the layout of ``shard.pack_records_u8``; ``prb_n [P] i32`` / ``ref_n [M] i32``:
+    atom counts; ``ref_index [P] i64``: ground-truth row of every pair (``None``: pair p uses row p).  Returns the six device tensors
+    ``(rmsd [P] f64, n_matched [P] i32, type_acc [P] f32, bond_acc [P] f32, exact [P] u8, map [P, 29] i32)``, enqueued on the current stream
+    without synchronising.  The arguments are checked, never converted: a wrong dtype, shape or a non-contiguous tensor raises."""
+    def want(t, name, dtype, shape):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a tensor")
+        if t.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+        if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+            raise ValueError(f"{name} must have shape {list(shape)} (None = any), got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    want(prb_rec, "prb_rec", torch.uint8, (None, RECORD_BYTES))
+    want(ref_rec, "ref_rec", torch.uint8, (None, RECORD_BYTES))
+    P, M = prb_rec.shape[0], ref_rec.shape[0]
+    want(prb_n, "prb_n", torch.int32, (P,))
+    want(ref_n, "ref_n", torch.int32, (M,))
+    if ref_index is not None:
+        want(ref_index, "ref_index", torch.int64, (P,))
+    elif M < P:
+        raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
+    max_distance, min_atoms = float(max_distance), int(min_atoms)
+    if max_distance != max_distance:
+        raise ValueError("max_distance must not be NaN")
+    dev = prb_rec.device
+    tensors = [prb_rec, prb_n, ref_rec, ref_n] + ([ref_index] if ref_index is not None else [])
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise RuntimeError("match_records needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    lib = load_library()
+    out = (torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+           torch.empty(P, dtype=torch.float32, device=dev), torch.empty(P, dtype=torch.float32, device=dev),
+           torch.empty(P, dtype=torch.uint8, device=dev), torch.empty(P, MAX_ATOMS, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        st = lib.ds_match_records(_ptr(prb_rec), _ptr(prb_n), C.c_int64(P), _ptr(ref_rec), _ptr(ref_n), C.c_int64(M), _ptr(ref_index),
+                                  C.c_float(max_distance), C.c_int32(min_atoms), *(_ptr(t) for t in out), _stream())
+    _check(st, "ds_match_records")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -512,6 +561,10 @@ class DmtEngine:
                "ds_check_stability")
         n_atoms = torch.as_tensor(L.n_atoms, device=dev)
         return ok.bool(), nr.long(), n_atoms, (order.long() if want_orders else None)
+
+    def match_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, max_distance: float = 5.0, min_atoms: int = 3):
+        """``engine.match_records`` on this engine's library (the structure metric needs no weights)."""
+        return match_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, max_distance, min_atoms)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

@@ -58,10 +58,33 @@ def checkpoint_ids(config):
     return list(range(config.eval.begin_ckpt, config.eval.end_ckpt + 1))
 
 
+def _structure_summary(run, table, top_k: int) -> Dict:
+    """The structure metric of one finished sharded run: every sample slot's record against the ground-truth record of its dataset item."""
+    from .structure_metrics import hungarian_rmsd_batch, topk_summary
+    dev = run.records_by_slot.device
+    per_pair = hungarian_rmsd_batch((table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms)),
+                                    engine=run.eng, ref_index=run.slot_ds, raw=True)
+    ok = per_pair.valid
+    n_ok, P = int(ok.sum()), ok.numel()
+    mean = lambda t: float(t[ok].double().mean()) if n_ok else None
+    rmsd = per_pair.rmsd.cpu()
+    out = dict(rmsd_list=[None if v != v else v for v in rmsd.tolist()], success_rate=n_ok / P if P else 0.0, mean_rmsd=mean(per_pair.rmsd),
+               mean_atom_type_accuracy=mean(per_pair.type_acc), mean_bond_accuracy=mean(per_pair.bond_acc),
+               exact_rate=float(per_pair.exact.double().mean()) if P else 0.0, per_pair=per_pair)
+    if top_k > 1:
+        out["top_k"] = topk_summary(per_pair, top_k)
+    return out
+
+
 def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = "eval",
-                         metric_fns: Optional[Dict[str, Callable]] = None):
+                         metric_fns: Optional[Dict[str, Callable]] = None, structure_metrics: bool = False):
     """Sampling evaluation over the configured checkpoints; returns ``{ckpt: {'processed_mols', 'gt_pos', 'gt_rdmols',
     'metrics'}}``.  ``metric_fns[name](processed_mols, gt_pos, gt_rdmols)`` are optional host-side callbacks.
+
+    ``structure_metrics=True`` (needs a table with ``gt_records`` and the philox noise source) adds ``metrics['structure']``, computed on the
+    GPU from the run's ``records_by_slot`` (``structure_metrics.py``; no RDKit): ``rmsd_list, success_rate, mean_rmsd,
+    mean_atom_type_accuracy`` of ``eval_sampled_mols/rmsd.py:232-273``, ``mean_bond_accuracy``, ``exact_rate`` and the raw ``per_pair``
+    device tensors; with ``config.eval.top_k`` = K > 1 the run draws K candidates per spectrum and ``'top_k'`` holds ``topk_summary``.
 
     ``test_ds=None`` reads the reference's processed files under ``config.data.root`` (``run_lib.py:313`` ->
     ``build_dataset.py:31-42``: the 'test' entry of ``split_dict_diffspectra_qm9.pt``) into the device-resident table of
@@ -78,8 +101,12 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     noise_scheduler = NoiseScheduleVP(config.sde.schedule, continuous_beta_0=config.sde.continuous_beta_0,
                                       continuous_beta_1=config.sde.continuous_beta_1)
     inverse_scaler = get_data_inverse_scaler(config)
+    top_k = int(getattr(config.eval, "top_k", 1)) if structure_metrics else 1
+    if structure_metrics and getattr(test_ds, "gt_records", None) is None:
+        raise ValueError("structure_metrics=True needs a test_ds with gt_records (PackedSpectraTable built from a source that holds the "
+                         "molecular graphs: atom_type, edge_index, edge_type, fc, pos)")
     sampling_fn = get_cond_sampling_eval_fn(config, noise_scheduler, config.eval.batch_size, config.eval.num_samples,
-                                            inverse_scaler, test_ds)
+                                            inverse_scaler, test_ds, top_k=top_k)
     results = {}
     for ckpt in checkpoint_ids(config):
         ckpt_path = os.path.join(workdir, "checkpoints", "checkpoint_{}.pth".format(ckpt))
@@ -88,7 +115,15 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
         logging.info("load checkpoint: %s", ckpt_path)
         state = restore_checkpoint(ckpt_path, state, device=config.device)
         ema.copy_to(model.parameters())          # eval uses EMA weights; BatchNorm buffers stay the model's (run_lib.py:361-362)
-        processed_mols, gt_pos, gt_rdmols = sampling_fn(model)
+        if structure_metrics:
+            run = sampling_fn.start(model)
+            with torch.no_grad():
+                run.advance()
+                processed_mols, gt_pos, gt_rdmols = run.finish()
+        else:
+            processed_mols, gt_pos, gt_rdmols = sampling_fn(model)
         metrics = {name: fn(processed_mols, gt_pos, gt_rdmols) for name, fn in (metric_fns or {}).items()}
+        if structure_metrics:
+            metrics["structure"] = _structure_summary(run, test_ds, top_k)
         results[ckpt] = dict(processed_mols=processed_mols, gt_pos=gt_pos, gt_rdmols=gt_rdmols, metrics=metrics, step=state["step"])
     return results

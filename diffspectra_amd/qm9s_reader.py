@@ -29,7 +29,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .config import SPECTRUM_LENGTHS, used_spectra
-from .dataset_pack import PackedSpectraTable
+from .dataset_pack import GRAPH_FIELDS, PackedSpectraTable
 
 DATA_FILE = "data_qm9_allspectra.pt"            # qm9s_dataset.py:170-172 (every spectra_version shares it)
 SPLIT_FILE = "split_dict_diffspectra_qm9.pt"    # qm9s_dataset.py:311
@@ -141,7 +141,9 @@ class ProcessedQM9S:
 
         Every molecule contributes ONE row of each spectrum (``[1, L]`` items, ``sampling.py:399-411``), so the rows of a
         split are one ``index_select`` of the collated tensor - no per-molecule Python.  ``normalize`` applies the
-        reference transform's ``log10(x + 1)`` (``build_dataset.py:141-148``; ``config.data.use_normalize``).
+        reference transform's ``log10(x + 1)`` (``build_dataset.py:141-148``; ``config.data.use_normalize``).  When the file holds the
+        molecular graphs (``atom_type, edge_index, edge_type, fc, pos``, ``qm9s_dataset.py:267-268``) the table also carries them as
+        ``gt_records`` (``structure_metrics.records_from_graph``), the ground truth of the RDKit-free structure metric.
         """
         ids = self.split(split) if split is not None else torch.arange(self.num_molecules)
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.num_molecules):
@@ -161,4 +163,10 @@ class ProcessedQM9S:
         idl = ids.tolist()
         pos = [self.item_field("pos", j) for j in idl] if "pos" in self.fields else None
         rdmol = [self.item_field("rdmol", j) for j in idl] if "rdmol" in self.fields else None
-        return PackedSpectraTable(spectra, na.reshape(-1)[ids], pos, rdmol, device)
+        gt = None
+        if all(f in self.fields and torch.is_tensor(self.fields[f]) for f in GRAPH_FIELDS):     # the ground-truth graphs as records: no RDKit needed
+            from .structure_metrics import records_from_graph
+            f = self.fields
+            gt = records_from_graph(f["atom_type"], f["pos"], f["fc"], f["edge_index"], f["edge_type"], self.slices["atom_type"],
+                                    self.slices["edge_type"], ids)
+        return PackedSpectraTable(spectra, na.reshape(-1)[ids], pos, rdmol, device, gt_records=gt)

@@ -1,0 +1,128 @@
+"""Structural quality of sampled molecules without RDKit: Hungarian-matched RMSD, atom-type accuracy and certified Top-K hits.
+
+The reference scores structures with ``eval_sampled_mols/rmsd.py``: largest fragment of each RDKit molecule, a Hungarian atom match with
+atom-type penalties, a Kabsch fit on that match, a second, distance-clipped match, then the RMSD and the atom-type accuracy of the final
+map (``rmsd.py:12-73``) - one pair at a time, with a Python double loop per cost matrix.  Here the same five steps run in ONE launch of
+``ds_match_records`` (one wave per pair, fp64, ``csrc/ds_match.hip``; semantics in ``include/diffspectra_hip.h``) on the 1 248-byte records
+the sampler already holds on the GPU (``shard.pack_records_u8``), against ground-truth records built from the processed file's plain
+tensors (``records_from_graph``).  Two outputs go beyond the reference: ``bond_acc`` and ``exact`` - the kernel's atom map either is or is
+not a graph isomorphism, so ``exact = 1`` is a *certified* hit.  ``exact = 0`` proves nothing (a correct graph in another conformation can
+be matched atom-for-atom differently), so hit@K computed from it is a LOWER bound on Top-K accuracy.
+
+One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
+atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
+"""
+from __future__ import annotations
+
+from typing import Dict, NamedTuple, Optional, Sequence
+
+import torch
+
+from . import shard
+
+
+class PairMetrics(NamedTuple):
+    """Per-pair device tensors of ``ds_match_records``."""
+    rmsd: torch.Tensor        # [P] f64, NaN for an invalid pair
+    n_matched: torch.Tensor   # [P] i32
+    type_acc: torch.Tensor    # [P] f32
+    bond_acc: torch.Tensor    # [P] f32
+    exact: torch.Tensor       # [P] u8
+    map: torch.Tensor         # [P, 29] i32, -1 where unmatched
+
+    @property
+    def valid(self) -> torch.Tensor:
+        return ~torch.isnan(self.rmsd)
+
+
+def records_from_graph(atom_type: torch.Tensor, pos: torch.Tensor, fc: torch.Tensor, edge_index: torch.Tensor,
+                       edge_type: torch.Tensor, node_slices: torch.Tensor, edge_slices: torch.Tensor, ids=None,
+                       atom_type_list: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Ground-truth records ``[len(ids), 1248] u8`` from the collated tensors of the processed file (``qm9s_dataset.py:267-268``), in the
+    conventions of ``train_data.edge_com_transform``: an atom's type is its position in ``atom_type_list`` (QM9: H, C, N, O, F), bond code 4
+    (aromatic) counts as no bond, and the directed edge list is summed into the dense ``[n, n]`` matrix.  ``node_slices`` / ``edge_slices`` are
+    the cumulative offsets of the molecules along ``atom_type`` / ``edge_type``; ``edge_index`` is ``[2, E]`` with molecule-local atom indices.
+    No Python per molecule."""
+    from .train_data import QM9_ATOM_TYPES
+    W = shard.RECORD_ATOMS
+    types = torch.tensor(list(QM9_ATOM_TYPES if atom_type_list is None else atom_type_list), dtype=torch.int64)
+    node_slices, edge_slices = node_slices.to(torch.int64).cpu(), edge_slices.to(torch.int64).cpu()
+    n_mol = node_slices.numel() - 1
+    ids = torch.arange(n_mol) if ids is None else torch.as_tensor(ids, dtype=torch.int64).reshape(-1).cpu()
+    n, ne = node_slices[1:] - node_slices[:-1], edge_slices[1:] - edge_slices[:-1]
+    if ids.numel() and int(n[ids].max()) > W:
+        raise ValueError(f"records hold at most {W} atoms")
+    # one record per DISTINCT molecule of ids, then the rows of ids are gathered (Top-K tables repeat molecules)
+    uniq = torch.unique(ids)
+    row = torch.full((n_mol,), -1, dtype=torch.int64)
+    row[uniq] = torch.arange(uniq.numel())
+    K = uniq.numel()
+    mol_n = torch.repeat_interleave(torch.arange(n_mol), n)           # molecule and local index of every atom of the collated tensors
+    loc_n = torch.arange(mol_n.numel()) - node_slices[:-1][mol_n]
+    mol_e = torch.repeat_interleave(torch.arange(n_mol), ne)
+    keep_n, keep_e = row[mol_n] >= 0, row[mol_e] >= 0
+    rn, ln = row[mol_n][keep_n], loc_n[keep_n]
+    one_hot = atom_type.reshape(-1, 1).to(torch.int64).cpu()[keep_n] == types.unsqueeze(0)      # build_dataset.py:111-114
+    if not bool(one_hot.any(1).all()):
+        raise ValueError("atom_type outside atom_type_list")
+    pos_d, at_d, fc_d = torch.zeros(K, W, 3), torch.zeros(K, W, dtype=torch.int64), torch.zeros(K, W, dtype=torch.int64)
+    pos_d[rn, ln] = pos.reshape(-1, 3).to(torch.float32).cpu()[keep_n]
+    at_d[rn, ln] = one_hot.to(torch.int64).argmax(1)
+    fc_d[rn, ln] = fc.reshape(-1).to(torch.int64).cpu()[keep_n]
+    bond = edge_type.reshape(-1).to(torch.float32).cpu()[keep_e]
+    bond[bond == 4] = 0                                               # build_dataset.py:118-119
+    ei = edge_index.to(torch.int64).cpu()[:, keep_e]
+    if ei.numel() and (int(ei.min()) < 0 or bool((ei >= n[mol_e][keep_e].unsqueeze(0)).any())):
+        raise ValueError("edge_index outside its molecule")
+    et_d = torch.zeros(K * W * W)
+    et_d.scatter_add_(0, row[mol_e][keep_e] * (W * W) + ei[0] * W + ei[1], bond)               # build_dataset.py:128-131
+    et_d = et_d.round().clamp_(0, 255).reshape(K, W, W)
+    return shard.pack_records_u8(pos_d, at_d, fc_d, et_d)[row[ids]].contiguous()
+
+
+def hungarian_rmsd_batch(ref, prb, max_distance: float = 5.0, min_atoms: int = 3, engine=None, ref_index=None, raw: bool = False):
+    """``hungarian_rmsd_batch`` of ``eval_sampled_mols/rmsd.py:232-273`` on record tensors.  ``ref`` and ``prb`` are ``(records [*, 1248] u8,
+    n_atoms [*])`` pairs on the GPU (ground truth first, as in the reference's signature); ``ref_index [P]`` names the ground-truth row of
+    every generated molecule (``None``: row p for pair p), so the K candidates of a spectrum share one row.
+
+    Returns ``(rmsd_list, success_rate, mean_rmsd, mean_atom_type_accuracy)``: ``None`` for an invalid pair, the success rate over all
+    pairs, the means over the valid pairs (``None`` without any).  ``raw=True`` returns the ``PairMetrics`` of device tensors instead and
+    does not synchronise."""
+    from . import engine as E
+    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
+    i32 = lambda t: torch.as_tensor(t).to(device=prb_rec.device, dtype=torch.int32).contiguous()
+    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=prb_rec.device, dtype=torch.int64).contiguous()
+    fn = engine.match_records if engine is not None else E.match_records
+    out = PairMetrics(*fn(prb_rec, i32(prb_n), ref_rec, i32(ref_n), idx, max_distance, min_atoms))
+    if raw:
+        return out
+    rmsd = out.rmsd.cpu()
+    ok = ~torch.isnan(rmsd)
+    n_ok, P = int(ok.sum()), rmsd.numel()
+    rmsd_list = [float(v) if k else None for v, k in zip(rmsd.tolist(), ok.tolist())]
+    success_rate = n_ok / P if P else 0.0
+    mean_rmsd = float(rmsd[ok].mean()) if n_ok else None
+    mean_acc = float(out.type_acc.cpu()[ok].double().mean()) if n_ok else None
+    return rmsd_list, success_rate, mean_rmsd, mean_acc
+
+
+def topk_summary(per_pair, top_k: int) -> Dict[str, torch.Tensor]:
+    """Best-of-K reductions over the K consecutive candidates of every spectrum (``processed_mols[i*K:(i+1)*K]``).  ``per_pair``: a
+    ``PairMetrics`` or any object / dict with ``rmsd [S*K]`` (NaN = invalid) and ``exact [S*K]``.  Plain torch reductions on the tensors'
+    device: ``best_rmsd [S] f64`` (NaN when all K candidates are invalid), ``best_index [S] i64`` (candidate with the lowest RMSD, -1 when
+    all are invalid), ``hit [S] bool`` (any candidate certified exact) and ``hit_at_k`` (their mean, a 0-dim f64 tensor; a lower bound on
+    Top-K accuracy)."""
+    get = (lambda k: per_pair[k]) if isinstance(per_pair, dict) else (lambda k: getattr(per_pair, k))
+    rmsd, exact = get("rmsd"), get("exact")
+    if top_k < 1 or rmsd.numel() % top_k:
+        raise ValueError(f"{rmsd.numel()} pairs are not a whole number of top_k = {top_k} groups")
+    r = rmsd.reshape(-1, top_k).to(torch.float64)
+    bad = torch.isnan(r)
+    filled = torch.where(bad, torch.full_like(r, float("inf")), r)
+    best, arg = filled.min(dim=1)
+    none = bad.all(dim=1)
+    best = torch.where(none, torch.full_like(best, float("nan")), best)
+    arg = torch.where(none, torch.full_like(arg, -1), arg)
+    hit = exact.reshape(-1, top_k).bool().any(dim=1)
+    hit_at_k = hit.double().mean() if hit.numel() else torch.zeros((), dtype=torch.float64, device=hit.device)
+    return dict(best_rmsd=best, best_index=arg, hit=hit, hit_at_k=hit_at_k)

@@ -22,6 +22,7 @@
  *   ds_sampler_step_philox                                    models/utils.py:67-106 (+ sampling.py:442-447,604-624)
  *   ds_post_process       post_process + inverse scaler       sampling.py:53-97, utils.py:88-103
  *   ds_check_stability    check_stability (distance half)     evaluation/stability.py:40-73, evaluation/bond_analyze.py:108-133
+ *   ds_match_records      hungarian_atom_mapping              eval_sampled_mols/rmsd.py:12-73,106-128,153-227
  *   ds_gemm / ds_spec_*   SpecFormer.forward                  models/specformer.py:77-120,167-200,279-309,345-425,457-470
  *
  * Data layout ("packed-ragged", symmetric pair storage — DESIGN.md §3):
@@ -107,6 +108,7 @@ enum ds_global_slot {
 #define DS_W_NUM_SLOTS (DS_NBLOCKS * DS_W_BLOCK_SLOTS + DS_W_GLOBAL_SLOTS)
 
 #define DS_MAX_ATOMS 29               /* QM9 (data.max_node, configs/diffspectra_qm9s.py:28) */
+#define DS_RECORD_BYTES 1248          /* one result record (shard.pack_records_u8): 29*3 f32 positions | 29 u8 types | 29 i8 charges | 29*29 u8 bond orders | pad */
 
 typedef struct ds_weights {
   const float* base;                 /* device: packed weights */
@@ -261,6 +263,33 @@ int ds_post_process(const ds_layout* L, const float* xh, const float* edge_x,
  * bond_order [B,N,N] i32 (may be NULL), nr_stable [B] = atoms with the right valence, mol_stable [B] = 1 if all are. */
 int ds_check_stability(const ds_layout* L, const float* pos, const int32_t* atom_type, int32_t* bond_order,
                        int32_t* nr_stable, int32_t* mol_stable, void* stream);
+
+/* Structure metric of (generated, ground-truth) molecule pairs, one wave per pair, fp64 (eval_sampled_mols/rmsd.py:12-73,106-128,153-227
+ * without RDKit): both molecules are DS_RECORD_BYTES records in the layout of shard.pack_records_u8, atom types in decoder order H, C, N, O, F.
+ *   1. each side keeps its largest connected fragment (a bond is an order > 0, read from the upper triangle of the record's bond matrix;
+ *      among equally large fragments the one that holds the lowest atom index - RDKit's fragment order under Python's max; fragment atoms
+ *      stay in ascending original order) and is centred on that fragment's centroid; a non-finite coordinate in either fragment makes
+ *      the pair invalid (the reference's assignment refuses such a cost matrix, rmsd.py:164-168);
+ *   2. cost[p][r] = |x_p - x_r| + penalty (0 same type, 2 both in {C, N, O}, 10 otherwise), rows generated, columns ground-truth atoms;
+ *   3. minimum-cost assignment of the centred coordinates, unclipped; fewer than min_atoms assigned -> the pair is invalid
+ *      (the reference's PCA fallback cannot make such a pair valid and is not built);
+ *   4. Kabsch: H = P^T Q over the assigned rows (ascending generated index) = U S V^T, R = U V^T, with the last row of V^T negated when
+ *      det R < 0; aligned = centred_generated . R;
+ *   5. second assignment on the aligned coordinates with cost entries above max_distance (inf allowed: no clipping) set to 1000; matches
+ *      whose clipped cost is <= max_distance are kept; fewer than min_atoms (or none) kept -> invalid.
+ * Outputs per pair p (ground-truth row ref_index[p], or p when ref_index is NULL; a row outside [0, M) makes the pair invalid):
+ *   rmsd      f64  sqrt(mean |aligned_p - centred_r|^2) over the kept map (spatial distance only); NaN if invalid
+ *   n_matched i32  size of the kept map whenever step 5 was reached (0 otherwise), also for an invalid pair
+ *   type_acc  f32  share of kept matches with equal atom type; 0 if invalid
+ *   bond_acc  f32  share of the unordered pairs of mapped generated atoms whose bond order equals that of their images; 0 if invalid
+ *   exact     u8   1 when both fragments are the whole molecules, the atom counts agree, every atom is mapped and every type, formal
+ *                  charge and bond order agrees under the map: the map is then an explicit graph isomorphism (a certified hit; 0 proves
+ *                  nothing - a correct graph in another conformation can miss - so hit@K from it is a LOWER bound)
+ *   map [P,29] i32 ground-truth atom of every generated atom (original indices), -1 where unmatched / invalid
+ * prb_n [P], ref_n [M]: atom counts (clamped to 0..29).  P = 0 launches nothing.  (bond_acc / exact are build extensions.) */
+int ds_match_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
+                     const int64_t* ref_index, float max_distance, int32_t min_atoms, double* rmsd, int32_t* n_matched,
+                     float* type_acc, float* bond_acc, uint8_t* exact, int32_t* map, void* stream);
 
 /* SpecFormer pieces that are not plain GEMMs (specformer.py:385-425 residual-score attention; :119 LayerNorm).
  * qkv [B,L,3*heads*dk]; out [B,L,heads*dk]; scores: B*heads*L*L floats of caller-owned scratch that carries the

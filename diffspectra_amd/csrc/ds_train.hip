@@ -914,23 +914,25 @@ __global__ __launch_bounds__(256) void k_noising(dst_layout L, const float* __re
 }
 
 // process_edge_batch + get_data_scaler (losses.py:498-529, utils.py:33-68; centered data): CoM-free positions / pos_norm, one-hot types
-// * 2 - 1 over type_norm, charges over charge_norm; pair features * 2 - 1 over edge_norm.
+// * 2 - 1 over type_norm, charges over charge_norm; pair features * 2 - 1 over edge_norm.  The centre of mass is summed and subtracted in
+// fp64: a molecule may sit far from the origin (translation augmentation), and an fp32 sum of 29 coordinates of size 40 left a centre of
+// mass of 1.4e-6 of the molecule's extent in the "CoM-free" positions (fp64: 1e-8; three threads, 29 additions each).
 __global__ __launch_bounds__(256) void k_prepare_batch(dst_layout L, const float* __restrict__ pos, const float* __restrict__ one_hot, const float* __restrict__ fc,
                                                         const float* __restrict__ edge, float pos_norm, float type_norm, float fc_norm, float edge_norm,
                                                         float* __restrict__ x, float* __restrict__ ex) {
-  __shared__ float mean[3];
+  __shared__ double mean[3];
   const int m = blockIdx.x;
   const int n0 = L.node_off[m], n = L.node_off[m + 1] - n0, p0 = L.pair_off[m], np = n * (n - 1) / 2;
   if (threadIdx.x < 3) {
-    float t = 0.0f;
-    for (int i = 0; i < n; ++i) t += pos[(int64_t)(n0 + i) * 3 + threadIdx.x];
-    mean[threadIdx.x] = t / (float)n;
+    double t = 0.0;
+    for (int i = 0; i < n; ++i) t += (double)pos[(int64_t)(n0 + i) * 3 + threadIdx.x];
+    mean[threadIdx.x] = t / (double)n;
   }
   __syncthreads();
   for (int it = threadIdx.x; it < n * 9; it += 256) {
     const int i = it / 9, c = it % 9;
     float v;
-    if (c < 3) v = (pos[(int64_t)(n0 + i) * 3 + c] - mean[c]) / pos_norm;
+    if (c < 3) v = (float)((double)pos[(int64_t)(n0 + i) * 3 + c] - mean[c]) / pos_norm;
     else if (c < 8) v = (one_hot[(int64_t)(n0 + i) * 5 + (c - 3)] * 2.0f - 1.0f) / type_norm;
     else v = fc[n0 + i] / fc_norm;
     x[(int64_t)n0 * 9 + it] = v;
@@ -950,8 +952,14 @@ __global__ __launch_bounds__(64) void k_kabsch(dst_layout L, const float* __rest
       for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) A[i][j] += (double)pred[(int64_t)(n0 + k) * ldp + i] * (double)tar[(int64_t)(n0 + k) * ldt + j];
     svd3(A, U, S, V);
-    const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-                       A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+    // sign det A as det U * det V: the same sign wherever A has full rank (det A = det U * s1 s2 s3 * det V).  Three atoms, or any planar
+    // molecule, give s3 = 0: there det A itself is rounding noise (one ulp on an input flipped it, and with it the third column of the
+    // rotation), while U (completed by a cross product in svd3) and V still name the one proper rotation of the fit.
+    auto det3 = [](const double M[3][3]) {
+      return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+             M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+    };
+    const double det = det3(U) * det3(V);
     const double sg = det > 0 ? 1.0 : (det < 0 ? -1.0 : 0.0);
     for (int i = 0; i < 3; ++i)
       for (int l = 0; l < 3; ++l) R[i * 3 + l] = (float)(U[i][0] * V[l][0] + U[i][1] * V[l][1] + sg * U[i][2] * V[l][2]);
@@ -1332,15 +1340,15 @@ __global__ void k_ln_affine_bwd_params(const float* __restrict__ dy, const float
 
 // ------------------------------------------------------------------------------------------------------------------ optimizer
 __global__ void k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, float* __restrict__ vmax,
-                            float* __restrict__ ema, int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2,
-                            float clip, const float* __restrict__ clip_dev, float ema_omd) {
+                            float* __restrict__ ema, int64_t n, float lr, float beta1, float omb1, float beta2, float omb2, float eps, float wd,
+                            float bc1, float bc2, float clip, const float* __restrict__ clip_dev, float ema_omd) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float grad = g[i] * (clip_dev ? clip * clip_dev[0] : clip);
   float w = p[i];
   w *= (1.0f - lr * wd);                                    // decoupled weight decay (torch.optim.AdamW)
-  const float mi = beta1 * m[i] + (1.0f - beta1) * grad;
-  const float vi = beta2 * v[i] + (1.0f - beta2) * grad * grad;
+  const float mi = beta1 * m[i] + omb1 * grad;                // omb = 1 - beta, taken in double on the host side of the call
+  const float vi = beta2 * v[i] + omb2 * grad * grad;
   const float vm = fmaxf(vmax[i], vi);                      // amsgrad
   m[i] = mi; v[i] = vi; vmax[i] = vm;
   const float denom = sqrtf(vm) / sqrtf(bc2) + eps;
@@ -1376,8 +1384,8 @@ __global__ void k_clip_update(const float* __restrict__ norm_sq, float inv_world
 
 // four parameters per thread, 16-byte accesses (same arithmetic per element)
 __global__ void k_adamw_ema4(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m, float4* __restrict__ v, float4* __restrict__ vmax,
-                             float4* __restrict__ ema, int64_t n4, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2,
-                             float clip, const float* __restrict__ clip_dev, float ema_omd) {
+                             float4* __restrict__ ema, int64_t n4, float lr, float beta1, float omb1, float beta2, float omb2, float eps, float wd,
+                             float bc1, float bc2, float clip, const float* __restrict__ clip_dev, float ema_omd) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n4) return;
   const float cl = clip_dev ? clip * clip_dev[0] : clip;
@@ -1390,8 +1398,8 @@ __global__ void k_adamw_ema4(float4* __restrict__ p, const float4* __restrict__ 
   for (int e = 0; e < 4; ++e) {
     const float grad = gg[e] * cl;
     float wv = w[e] * (1.0f - lr * wd);
-    const float mi = beta1 * mm[e] + (1.0f - beta1) * grad;
-    const float vi = beta2 * vv[e] + (1.0f - beta2) * grad * grad;
+    const float mi = beta1 * mm[e] + omb1 * grad;
+    const float vi = beta2 * vv[e] + omb2 * grad * grad;
     const float vm = fmaxf(xx[e], vi);
     mm[e] = mi; vv[e] = vi; xx[e] = vm;
     const float denom = sqrtf(vm) / sq2 + eps;
@@ -1447,7 +1455,7 @@ int dst_colsum(const float* X, int64_t ld, int32_t R, int32_t C, float* out, int
 }
 
 int dst_sumsq(const float* x, int64_t n, float* out, int32_t accumulate, float* scratch, int64_t scratch_cap, void* stream) {
-  if (!x || !out || !scratch || scratch_cap < 256) return DS_ERR_ARG;
+  if (n < 0 || (n > 0 && !x) || !out || !scratch || scratch_cap < 257) return DS_ERR_ARG;   // an empty x (NULL) sums to 0; scratch: 256 block sums + their sum
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_sumsq_partial, dim3(256), dim3(256), 0, s, x, n, scratch);
   hipLaunchKernelGGL(k_colsum_partial, dim3(1, 1), dim3(256), 0, s, (const float*)scratch, (int64_t)1, 256, 1, scratch + 256, 256);
@@ -1468,7 +1476,7 @@ int dst_act_bwd(const float* dy, const float* ref, float* dx, int64_t n, int32_t
   return DST_CHECK_LAUNCH();
 }
 int dst_axpy(float a, const float* x, float* y, int64_t n, void* stream) {
-  if (!x || !y) return DS_ERR_ARG;
+  if (n < 0 || (n > 0 && (!x || !y))) return DS_ERR_ARG;
   if (n == 0) return DS_OK;
   if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0)
     hipLaunchKernelGGL(k_axpy4, grid1d(n / 4), dim3(256), 0, (hipStream_t)stream, a, reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), n / 4);
@@ -1723,18 +1731,19 @@ int dst_ln_affine_bwd(const float* dy, const float* x, const float* stats, int32
   return DST_CHECK_LAUNCH();
 }
 
-int dst_adamw_ema(float* p, const float* g, float* m, float* v, float* vmax, float* ema, int64_t n, float lr, float beta1, float beta2,
+int dst_adamw_ema(float* p, const float* g, float* m, float* v, float* vmax, float* ema, int64_t n, float lr, double beta1, double beta2,
                   float eps, float weight_decay, float bc1, float bc2, float clip_coef, const float* clip_coef_dev, float ema_one_minus_decay,
                   void* stream) {
-  if (!p || !g || !m || !v || !vmax || n < 0) return DS_ERR_ARG;
+  if (n < 0 || (n > 0 && (!p || !g || !m || !v || !vmax))) return DS_ERR_ARG;
   if (n == 0) return DS_OK;
+  const float b1 = (float)beta1, omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   if ((n & 3) == 0 && al16(p) && al16(g) && al16(m) && al16(v) && al16(vmax) && (!ema || al16(ema)))
     hipLaunchKernelGGL(k_adamw_ema4, grid1d(n >> 2), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(p), reinterpret_cast<const float4*>(g),
                        reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), reinterpret_cast<float4*>(vmax), reinterpret_cast<float4*>(ema), n >> 2, lr,
-                       beta1, beta2, eps, weight_decay, bc1, bc2, clip_coef, clip_coef_dev, ema_one_minus_decay);
+                       b1, omb1, b2, omb2, eps, weight_decay, bc1, bc2, clip_coef, clip_coef_dev, ema_one_minus_decay);
   else
-    hipLaunchKernelGGL(k_adamw_ema, grid1d(n), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, ema, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+    hipLaunchKernelGGL(k_adamw_ema, grid1d(n), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, ema, n, lr, b1, omb1, b2, omb2, eps, weight_decay, bc1, bc2,
                        clip_coef, clip_coef_dev, ema_one_minus_decay);
   return DST_CHECK_LAUNCH();
 }

@@ -199,7 +199,7 @@ class FusedAdamW:
             lo = self.rank * self.shard
             ema_ptr = self.ema_flat[lo:lo + self.shard]
         E._check(self.lib.dst_adamw_ema(E._ptr(self.Ps), E._ptr(self.Gs), E._ptr(self.M), E._ptr(self.V), E._ptr(self.Vmax), E._ptr(ema_ptr),
-                                        C.c_int64(self.shard), C.c_float(float(g["lr"])), C.c_float(b1), C.c_float(b2), C.c_float(g["eps"]),
+                                        C.c_int64(self.shard), C.c_float(float(g["lr"])), C.c_double(b1), C.c_double(b2), C.c_float(g["eps"]),
                                         C.c_float(g["weight_decay"]), C.c_float(1.0 - b1 ** self.steps), C.c_float(1.0 - b2 ** self.steps),
                                         C.c_float(float(clip_coef) / self.world), E._ptr(self.clip_state[51:52]) if self._clip_pending else None,
                                         C.c_float(ema_omd), E._stream()), "dst_adamw_ema")

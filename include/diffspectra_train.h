@@ -88,7 +88,7 @@ int dst_colsum(const float* X, int64_t ld, int32_t R, int32_t C, float* out, int
                int64_t scratch_cap, void* stream);
 
 /* Elementwise.  kind: 1 SiLU, 2 GELU(erf), 3 tanh.  Backward: dx = dy * f'(.), with ref = x for SiLU / GELU and ref = y for
- * tanh; dx may alias dy.  dst_axpy: y += a * x.  dst_scale_rows: y[r, :] = x[r, :] * s[r]. */
+ * tanh; dx may alias dy.  dst_axpy: y += a * x (n = 0: nothing to do, the pointers may be NULL).  dst_scale_rows: y[r, :] = x[r, :] * s[r]. */
 int dst_act_fwd(const float* x, float* y, int64_t n, int32_t kind, void* stream);
 int dst_act_bwd(const float* dy, const float* ref, float* dx, int64_t n, int32_t kind, void* stream);
 int dst_axpy(float a, const float* x, float* y, int64_t n, void* stream);
@@ -198,7 +198,8 @@ int dst_noising(const dst_layout* L, const float* alpha, const float* sigma, con
                 const float* eraw, float* ez, void* stream);
 
 /* Kabsch alignment (losses.py:414-452): rot[m] = U diag(1, 1, sign det A) V^T of A = sum_atoms pred_i tar_i^T (3x3 SVD by one-sided
- * Jacobi in fp64), aligned[i] = rot tar_i.  pred / tar / aligned [Nn, ld] (first three columns); rot [B,9]. */
+ * Jacobi in fp64), aligned[i] = rot tar_i.  sign det A is taken as det U * det V: the same where A has full rank, and the proper rotation
+ * instead of rounding noise where it has rank 2 (three atoms, planar molecules).  pred / tar / aligned [Nn, ld] (first three columns); rot [B,9]. */
 int dst_kabsch(const dst_layout* L, const float* pred, int64_t ld_pred, const float* tar, int64_t ld_tar, float* rot, float* aligned,
                void* stream);
 
@@ -249,8 +250,10 @@ int dst_ln_affine_bwd(const float* dy, const float* x, const float* stats, int32
 /* Fused optimizer step over one flat fp32 parameter buffer (losses.py:20 AdamW(amsgrad=True, weight_decay), torch semantics) followed
  * by the EMA update of models/ema.py:24-42: p, g, m, v, vmax, ema all [n].  The gradient is first multiplied by clip_coef and, when
  * clip_coef_dev is not NULL, by clip_coef_dev[0] (the device-resident coefficient of dst_clip_update: the step then needs no
- * device -> host synchronisation); bias corrections are passed in (1 - beta^t). */
-int dst_adamw_ema(float* p, const float* g, float* m, float* v, float* vmax, float* ema, int64_t n, float lr, float beta1, float beta2,
+ * device -> host synchronisation); bias corrections are passed in (1 - beta^t).  The betas are doubles: the kernels need 1 - beta, and
+ * 1.0f - (float)0.999 is 1.3e-5 off 0.001 (so was v after the first step); the complement is taken here in double, then rounded.
+ * n = 0 is a valid (empty) call. */
+int dst_adamw_ema(float* p, const float* g, float* m, float* v, float* vmax, float* ema, int64_t n, float lr, double beta1, double beta2,
                   float eps, float weight_decay, float bc1, float bc2, float clip_coef, const float* clip_coef_dev, float ema_one_minus_decay,
                   void* stream);
 
@@ -261,7 +264,8 @@ int dst_adamw_ema(float* p, const float* g, float* m, float* v, float* vmax, flo
  * taken min(norm, allowed).  Evaluated in double, as numpy does. */
 int dst_clip_update(const float* norm_sq, float inv_world, float max_grad, float* state, void* stream);
 
-/* sum of squares of x [n] into out[0] (accumulate != 0 adds): the global gradient norm of clip_grad_norm_. */
+/* sum of squares of x [n] into out[0] (accumulate != 0 adds): the global gradient norm of clip_grad_norm_.  n = 0 (x may be NULL) is the
+ * empty sum. */
 int dst_sumsq(const float* x, int64_t n, float* out, int32_t accumulate, float* scratch, int64_t scratch_cap, void* stream);
 
 /* The pair rows of one block behind the attention as ONE kernel (bf16 products, fp32 accumulation and fp32 everything else) - reference

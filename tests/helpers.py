@@ -21,3 +21,15 @@ def procedural_state_dict(version: str):
 
 def max_abs_diff(a: torch.Tensor, b: torch.Tensor) -> float:
     return float((a.double() - b.double()).abs().max())
+
+
+def relerr(a: torch.Tensor, b: torch.Tensor) -> float:
+    """The suite's error measure of a kernel against its high-precision reference: max |a - b| / max |b|."""
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
+
+
+def check(a: torch.Tensor, b: torch.Tensor, tol: float, what: str) -> float:
+    e = relerr(a, b)
+    assert e <= tol, f"{what}: max |diff| / max |ref| = {e:.3e} (tol {tol:g})"
+    return e

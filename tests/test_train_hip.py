@@ -14,20 +14,9 @@ import torch.nn.functional as F
 from oracle import train as otrain
 from oracle import dmt as odmt
 from tests.golden import cases
-from tests.helpers import procedural_state_dict
+from tests.helpers import check, procedural_state_dict, relerr
 
 pytestmark = pytest.mark.gpu
-
-
-def relerr(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
-
-
-def check(a, b, tol, what):
-    e = relerr(a, b)
-    assert e <= tol, f"{what}: max |diff| / max |ref| = {e:.3e} (tol {tol:g})"
-    return e
 
 
 @pytest.fixture(scope="module")

@@ -1,0 +1,275 @@
+// diffspectra_amd - molecular-graph identity of the evaluation path: is the generated molecule THE ground-truth molecule (same labelled graph:
+// atom type, formal charge, bond order), whatever its conformation, and a permutation-invariant hash per molecule.  One wave64 per pair /
+// per molecule, integers only, no atomics (ds_graph_identity_records and ds_graph_hash_records in include/diffspectra_hip.h state the
+// semantics and the exact hash formula; DESIGN.md section 10 has the algorithm and the figures).
+//
+// Soundness of k_graph_identity, in two lines that the code below keeps true:
+//   verdict 1 is written only after verify() has compared every type, charge and bond byte under an explicit bijection;
+//   verdict 0 is written only (a) for unequal atom counts, (b) when the ROOT colouring's histograms differ, or (c) when the search below the
+//     root is exhausted.  The colouring is a deterministic function of the labelled graph that commutes with renaming atoms (each round
+//     ranks a signature built from the atom's colour and the multiset of (bond, neighbour colour) jointly over both molecules), so an
+//     isomorphism maps every atom to an atom of its own colour: differing histograms prove that none exists, and if one exists it sends the
+//     individualised atom v to SOME atom w of v's class - the search tries every such w, and below the right w the same argument holds
+//     again, so an exhausted search proves that none exists.  The neighbour multiset is hashed (a commutative 64-bit sum): a collision can
+//     only leave two atoms in one class that an exact signature would split, which costs search nodes and never a wrong verdict, because
+//     neither (1) nor (0) relies on classes being as fine as possible.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/diffspectra_hip.h"
+#include "ds_train_common.h"   // DST_CHECK_LAUNCH
+
+namespace {
+
+constexpr int MA = DS_MAX_ATOMS;          // 29 atoms: lanes 0..28 hold the generated molecule, lanes 32..60 the ground truth
+constexpr int REC_TYPE = MA * 12, REC_FC = REC_TYPE + MA, REC_BOND = REC_FC + MA;   // 348, 377, 406 (shard.pack_records_u8)
+static_assert(REC_BOND + MA * MA <= DS_RECORD_BYTES && DS_RECORD_BYTES % 4 == 0, "record layout");
+constexpr int FRESH = 63;                 // colour of an individualised atom: ranks stay below 2 * 29 = 58
+
+__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the 64-bit finaliser and the pair mix of the header's hash formula (wrap-around arithmetic)
+__device__ __forceinline__ uint64_t fmix(uint64_t x) {
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27; x *= 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint64_t mix2(uint64_t a, uint64_t b) { return fmix(a + 0x9e3779b97f4a7c15ull * (b + 1ull)); }
+
+// Bond bytes of one record as a symmetric matrix adj[j * 32 + i] (the upper triangle of the record decides, as in ds_match_records; the
+// diagonal is no atom pair and reads 0).  The record is read as aligned dwords; every byte index stays inside the record.
+__device__ void load_bonds(unsigned char* __restrict__ adj, const unsigned char* __restrict__ rec, int lane) {
+  const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(rec);
+  for (int w = REC_BOND / 4 + lane; w < (REC_BOND + MA * MA + 3) / 4; w += 64) {      // dwords 101 .. 311 of 312
+    const uint32_t v = words[w];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int k = w * 4 + q - REC_BOND;
+      if (k < 0 || k >= MA * MA) continue;
+      const int i = k / MA, j = k - i * MA;
+      const unsigned char b = (unsigned char)(v >> (8 * q));
+      if (i < j) { adj[i * 32 + j] = b; adj[j * 32 + i] = b; }
+      else if (i == j) adj[i * 32 + i] = 0;
+    }
+  }
+}
+
+struct Pair {                             // both molecules of a pair in LDS; arrays of 64 are indexed by lane
+  unsigned char adj[2][MA * 32];
+  unsigned char type[64], fc[64];
+  unsigned long long sig[64], f[64];      // signatures being ranked; per-atom colour hash of the running round
+  unsigned char stack[MA][64];            // colours (ranks below 64) of every open level of the search, before its individualisation
+  int cell[MA], atom[MA], cursor[MA];     // per level: the class that is split, its generated atom, the next ground-truth atom to try
+  unsigned char inv[64], img[32];         // leaf: ground-truth atom of a colour; image of every generated atom
+};
+
+struct Ranked { int colour, eq_g, eq_r; bool leader; };
+
+// Joint rank of `sig` over the active lanes of both sides: colour = lanes with a smaller signature (ties share a colour); eq_g / eq_r = atoms
+// of the generated / ground-truth side with this signature; leader = no lower atom of the own side has it.
+__device__ Ranked rank_jointly(Pair& S, unsigned long long sig, int n, int lane) {
+  const int idx = lane & 31;
+  const bool right = lane >= 32;
+  S.sig[lane] = sig;
+  __syncthreads();
+  Ranked r = {0, 0, 0, true};
+  for (int k = 0; k < n; ++k) {
+    const unsigned long long a = S.sig[k], b = S.sig[32 + k];
+    r.colour += (a < sig) + (b < sig);
+    r.eq_g += a == sig;
+    r.eq_r += b == sig;
+    if (k < idx && (right ? b : a) == sig) r.leader = false;
+  }
+  __syncthreads();
+  return r;
+}
+
+enum { MISMATCH = 0, DISCRETE = 1, CELLS = 2 };
+
+// Colour refinement to the stable colouring, both molecules at once.  Signature of an atom: its colour in the top 6 bits (so a round only
+// ever splits classes), below it the commutative sum over its bonded neighbours j of hash(colour_j) * (2 bond_ij + 1).  At most n + 1 rounds:
+// every round but the last adds a class and there are at most n.  Returns MISMATCH as soon as the sides' histograms differ, else DISCRETE
+// (every class one atom per side) or CELLS with `multi` = the generated atoms that share their class.
+__device__ int refine(Pair& S, int& colour, bool active, int n, int lane, unsigned long long& multi) {
+  const int idx = lane & 31, side = lane >> 5;
+  int classes = 0;
+  multi = 0ull;
+  for (int round = 0; round <= n; ++round) {
+    S.f[lane] = fmix((unsigned long long)colour + 1ull);
+    __syncthreads();
+    unsigned long long acc = 0ull;
+    if (active)
+      for (int j = 0; j < n; ++j) {
+        const unsigned b = S.adj[side][j * 32 + idx];
+        if (b) acc += S.f[side * 32 + j] * (unsigned long long)(2u * b + 1u);
+      }
+    const Ranked r = rank_jointly(S, ((unsigned long long)colour << 58) | (acc >> 6), n, lane);
+    if (active) colour = r.colour;
+    if (__ballot(active && r.eq_g != r.eq_r) != 0ull) return MISMATCH;
+    const int now = __popcll(__ballot(active && side == 0 && r.leader));
+    multi = __ballot(active && side == 0 && r.eq_g > 1);
+    if (now == classes) break;
+    classes = now;
+  }
+  return multi ? CELLS : DISCRETE;
+}
+
+// Leaf of the search: every colour names one atom per side, which is the only bijection this branch allows.  It is checked in full - it is a
+// bijection, and every type, charge and bond byte agrees under it - before anything is called identical.  Leaves S.img = the map.
+__device__ bool verify(Pair& S, int colour, bool active, int n, int lane) {
+  const int idx = lane & 31;
+  const bool left = active && lane < 32, right = active && lane >= 32;
+  if (right) S.inv[colour] = (unsigned char)idx;
+  __syncthreads();
+  int m = 0;
+  if (left) { m = S.inv[colour] & 31; S.img[idx] = (unsigned char)m; }   // (& 31: an index inside the arrays whatever LDS held)
+  __syncthreads();
+  bool bad = false;
+  if (left) {
+    bad = m >= n || S.type[lane] != S.type[32 + m] || S.fc[lane] != S.fc[32 + m];
+    if (!bad)
+      for (int j = 0; j < n; ++j) bad |= S.adj[0][j * 32 + idx] != S.adj[1][S.img[j] * 32 + m];
+  }
+  if (right) {
+    int hits = 0;
+    for (int j = 0; j < n; ++j) hits += S.img[j] == idx;
+    bad = hits != 1;
+  }
+  __syncthreads();
+  return __ballot(bad) == 0ull;
+}
+
+__global__ __launch_bounds__(64) void k_graph_identity(const unsigned char* __restrict__ prb_rec, const int32_t* __restrict__ prb_n,
+                                                       const unsigned char* __restrict__ ref_rec, const int32_t* __restrict__ ref_n,
+                                                       const int64_t* __restrict__ ref_index, int64_t M, int max_nodes,
+                                                       unsigned char* __restrict__ verdict, int32_t* __restrict__ nodes, int32_t* __restrict__ map) {
+  __shared__ Pair S;
+  const int64_t p = blockIdx.x;
+  const int lane = threadIdx.x, idx = lane & 31, side = lane >> 5;
+  const int64_t r = ref_index ? ref_index[p] : p;
+  int out = DS_GRAPH_INVALID, used = 0;
+  if (r >= 0 && r < M) {                                     // a row outside ref_rec is an invalid pair, never a read
+    const int ng = min(max(prb_n[p], 0), MA), nr = min(max(ref_n[r], 0), MA);
+    const unsigned char* __restrict__ mine = side ? ref_rec + r * DS_RECORD_BYTES : prb_rec + p * DS_RECORD_BYTES;
+    out = DS_GRAPH_DIFFERENT;
+    if (ng == nr) {
+      const int n = ng;
+      const bool active = idx < n;
+      load_bonds(S.adj[0], prb_rec + p * DS_RECORD_BYTES, lane);
+      load_bonds(S.adj[1], ref_rec + r * DS_RECORD_BYTES, lane);
+      const unsigned type = active ? mine[REC_TYPE + idx] : 0u, fc = active ? mine[REC_FC + idx] : 0u;
+      S.type[lane] = (unsigned char)type;
+      S.fc[lane] = (unsigned char)fc;
+      __syncthreads();
+      // initial colour: (type, charge) ranked jointly
+      const Ranked first = rank_jointly(S, (unsigned long long)(type << 8 | fc), n, lane);
+      int colour = active ? first.colour : 0;
+      unsigned long long multi = 0ull;
+      int st = __ballot(active && first.eq_g != first.eq_r) ? MISMATCH : refine(S, colour, active, n, lane, multi);
+      int depth = 0;                                         // open levels: S.stack[0 .. depth-1]
+      out = DS_GRAPH_UNDECIDED;
+      for (int it = 0; it <= max_nodes; ++it) {              // every pass but the last spends one search node
+        if (st == DISCRETE && verify(S, colour, active, n, lane)) { out = DS_GRAPH_IDENTICAL; break; }
+        if (st == CELLS) {
+          if (depth >= MA) break;                            // (cannot happen: every level makes one more generated atom a class of its own)
+          // open a level on the lowest class with several atoms: its lowest generated atom will be individualised
+          int c = (active && side == 0 && ((multi >> lane) & 1ull)) ? colour : 64;
+#pragma unroll
+          for (int o = 16; o > 0; o >>= 1) c = min(c, __shfl_xor(c, o, 64));
+          c = uniform_i(c);
+          const int v = __ffsll((long long)__ballot(active && side == 0 && colour == c)) - 1;
+          S.stack[depth][lane] = (unsigned char)colour;
+          if (lane == 0) { S.cell[depth] = c; S.atom[depth] = v; S.cursor[depth] = 0; }
+          __syncthreads();
+          ++depth;
+        }
+        // the next untried ground-truth atom of the deepest level that has one; levels without are closed
+        int v = -1, w = -1;
+        while (depth > 0) {                                  // at most 29 levels
+          const int f = depth - 1;
+          const int c = uniform_i(S.cell[f]), from = uniform_i(S.cursor[f]);
+          colour = S.stack[f][lane];
+          const unsigned long long cand = __ballot(active && side == 1 && colour == c && idx >= from);
+          if (cand) { v = uniform_i(S.atom[f]); w = __ffsll((long long)cand) - 1 - 32; break; }
+          --depth;
+        }
+        if (w < 0) { out = DS_GRAPH_DIFFERENT; break; }      // nothing left to try anywhere: the root is dead
+        if (used >= max_nodes) break;                        // the budget does not cover this try: undecided
+        ++used;
+        __syncthreads();                                     // every lane has read the level's cursor
+        if (lane == 0) S.cursor[depth - 1] = w + 1;
+        if (active && (lane == v || lane == 32 + w)) colour = FRESH;
+        __syncthreads();
+        st = refine(S, colour, active, n, lane, multi);
+      }
+      if (out == DS_GRAPH_IDENTICAL && lane < n) map[p * MA + lane] = S.img[lane];
+      if (out == DS_GRAPH_IDENTICAL && lane >= n && lane < MA) map[p * MA + lane] = -1;
+    }
+  }
+  if (out != DS_GRAPH_IDENTICAL && lane < MA) map[p * MA + lane] = -1;
+  if (lane == 0) {
+    verdict[p] = (unsigned char)out;
+    nodes[p] = used;
+  }
+}
+
+struct Molecule {
+  unsigned char adj[MA * 32];
+  unsigned long long h[32];
+};
+
+// the hash of the header, term for term: lanes 0..28 are atoms
+__global__ __launch_bounds__(64) void k_graph_hash(const unsigned char* __restrict__ rec, const int32_t* __restrict__ n_atoms,
+                                                   unsigned long long* __restrict__ hash) {
+  __shared__ Molecule S;
+  const int64_t p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int n = min(max(n_atoms[p], 0), MA);
+  const unsigned char* __restrict__ mine = rec + p * DS_RECORD_BYTES;
+  const bool active = lane < n;
+  load_bonds(S.adj, mine, lane);
+  unsigned long long h = active ? mix2(mine[REC_TYPE + lane], mine[REC_FC + lane]) : 0ull;
+  for (int round = 0; round < MA; ++round) {
+    if (lane < 32) S.h[lane] = h;
+    __syncthreads();
+    unsigned long long acc = 0ull;
+    if (active)
+      for (int j = 0; j < n; ++j) {
+        const unsigned b = S.adj[j * 32 + lane];
+        if (b) acc += mix2(S.h[j], b);
+      }
+    __syncthreads();
+    if (active) h = mix2(h, acc);
+  }
+  if (lane < 32) S.h[lane] = fmix(h);
+  __syncthreads();
+  if (lane == 0) {
+    unsigned long long total = 0ull;
+    for (int j = 0; j < n; ++j) total += S.h[j];
+    hash[p] = mix2((unsigned long long)n, total);
+  }
+}
+
+}  // namespace
+
+extern "C" int ds_graph_identity_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n,
+                                         int64_t M, const int64_t* ref_index, int32_t max_nodes, uint8_t* verdict, int32_t* nodes, int32_t* map,
+                                         void* stream) {
+  if (P < 0 || M < 0 || P > 0x7fffffffll || max_nodes < 0 || max_nodes > DS_GRAPH_MAX_NODES) return DS_ERR_ARG;
+  if (P == 0) return DS_OK;
+  if (!prb_rec || !prb_n || !verdict || !nodes || !map) return DS_ERR_ARG;
+  if (M > 0 && (!ref_rec || !ref_n)) return DS_ERR_ARG;
+  if (!ref_index && M < P) return DS_ERR_ARG;                // identity pairing needs a ground-truth row for every pair
+  if (reinterpret_cast<uintptr_t>(prb_rec) & 3 || reinterpret_cast<uintptr_t>(ref_rec) & 3) return DS_ERR_ARG;   // records are read as dwords
+  hipLaunchKernelGGL(k_graph_identity, dim3((unsigned)P), dim3(64), 0, (hipStream_t)stream, prb_rec, prb_n, ref_rec, ref_n, ref_index, M,
+                     (int)max_nodes, verdict, nodes, map);
+  return DST_CHECK_LAUNCH();
+}
+
+extern "C" int ds_graph_hash_records(const uint8_t* rec, const int32_t* n, int64_t P, uint64_t* hash, void* stream) {
+  if (P < 0 || P > 0x7fffffffll) return DS_ERR_ARG;
+  if (P == 0) return DS_OK;
+  if (!rec || !n || !hash || reinterpret_cast<uintptr_t>(rec) & 3) return DS_ERR_ARG;
+  hipLaunchKernelGGL(k_graph_hash, dim3((unsigned)P), dim3(64), 0, (hipStream_t)stream, rec, n, reinterpret_cast<unsigned long long*>(hash));
+  return DST_CHECK_LAUNCH();
+}

@@ -383,6 +383,17 @@ class Workspace:
 RECORD_BYTES = CONSTS["DS_RECORD_BYTES"]
 
 
+def _want(t, name, dtype, shape):
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a tensor")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+        raise ValueError(f"{name} must have shape {list(shape)} (None = any), got {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
 def match_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
                   ref_index: Optional[torch.Tensor] = None, max_distance: float = 5.0, min_atoms: int = 3):
     """``ds_match_records``: Hungarian-matched RMSD, type / bond accuracy and the exact-graph flag of P (generated, ground-truth) pairs.
@@ -391,22 +402,13 @@ def match_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Ten
     atom counts; ``ref_index [P] i64``: ground-truth row of every pair (``None``: pair p uses row p).  Returns the six device tensors
     ``(rmsd [P] f64, n_matched [P] i32, type_acc [P] f32, bond_acc [P] f32, exact [P] u8, map [P, 29] i32)``, enqueued on the current stream
     without synchronising.  The arguments are checked, never converted: a wrong dtype, shape or a non-contiguous tensor raises."""
-    def want(t, name, dtype, shape):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{name} must be a tensor")
-        if t.dtype != dtype:
-            raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
-        if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
-            raise ValueError(f"{name} must have shape {list(shape)} (None = any), got {list(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-    want(prb_rec, "prb_rec", torch.uint8, (None, RECORD_BYTES))
-    want(ref_rec, "ref_rec", torch.uint8, (None, RECORD_BYTES))
+    _want(prb_rec, "prb_rec", torch.uint8, (None, RECORD_BYTES))
+    _want(ref_rec, "ref_rec", torch.uint8, (None, RECORD_BYTES))
     P, M = prb_rec.shape[0], ref_rec.shape[0]
-    want(prb_n, "prb_n", torch.int32, (P,))
-    want(ref_n, "ref_n", torch.int32, (M,))
+    _want(prb_n, "prb_n", torch.int32, (P,))
+    _want(ref_n, "ref_n", torch.int32, (M,))
     if ref_index is not None:
-        want(ref_index, "ref_index", torch.int64, (P,))
+        _want(ref_index, "ref_index", torch.int64, (P,))
     elif M < P:
         raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
     max_distance, min_atoms = float(max_distance), int(min_atoms)
@@ -424,6 +426,66 @@ def match_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Ten
         st = lib.ds_match_records(_ptr(prb_rec), _ptr(prb_n), C.c_int64(P), _ptr(ref_rec), _ptr(ref_n), C.c_int64(M), _ptr(ref_index),
                                   C.c_float(max_distance), C.c_int32(min_atoms), *(_ptr(t) for t in out), _stream())
     _check(st, "ds_match_records")
+    return out
+
+
+# ----------------------------------------------------------------------------------------- graph identity
+
+GRAPH_MAX_NODES = CONSTS["DS_GRAPH_MAX_NODES"]
+GRAPH_DIFFERENT, GRAPH_IDENTICAL, GRAPH_UNDECIDED, GRAPH_INVALID = (CONSTS["DS_GRAPH_" + k] for k in ("DIFFERENT", "IDENTICAL", "UNDECIDED", "INVALID"))
+
+
+def graph_identity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                           ref_index: Optional[torch.Tensor] = None, max_nodes: int = 4096):
+    """``ds_graph_identity_records``: is the generated molecule of each of P pairs the SAME labelled graph (atom type, formal charge, bond
+    order) as its ground truth, whatever the conformation - constitution-level identity, not InChIKey identity (no stereo layer, no
+    tautomer / charge normalisation; see the header).
+
+    The tensors are those of ``match_records``.  Returns the device tensors ``(verdict [P] u8, nodes [P] i32, map [P, 29] i32)``, enqueued on
+    the current stream without synchronising: verdict ``GRAPH_IDENTICAL`` (1: ``map`` is a checked isomorphism), ``GRAPH_DIFFERENT`` (0: proven),
+    ``GRAPH_UNDECIDED`` (2: the search needed more than ``max_nodes`` tries; 0 = colour refinement alone) or ``GRAPH_INVALID`` (3: ``ref_index``
+    outside the table).  The arguments are checked, never converted."""
+    _want(prb_rec, "prb_rec", torch.uint8, (None, RECORD_BYTES))
+    _want(ref_rec, "ref_rec", torch.uint8, (None, RECORD_BYTES))
+    P, M = prb_rec.shape[0], ref_rec.shape[0]
+    _want(prb_n, "prb_n", torch.int32, (P,))
+    _want(ref_n, "ref_n", torch.int32, (M,))
+    if ref_index is not None:
+        _want(ref_index, "ref_index", torch.int64, (P,))
+    elif M < P:
+        raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, int):
+        raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
+    if not 0 <= max_nodes <= GRAPH_MAX_NODES:
+        raise ValueError(f"max_nodes must lie in [0, {GRAPH_MAX_NODES}], got {max_nodes}")
+    dev = prb_rec.device
+    tensors = [prb_rec, prb_n, ref_rec, ref_n] + ([ref_index] if ref_index is not None else [])
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise RuntimeError("graph_identity_records needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    lib = load_library()
+    out = (torch.empty(P, dtype=torch.uint8, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+           torch.empty(P, MAX_ATOMS, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        st = lib.ds_graph_identity_records(_ptr(prb_rec), _ptr(prb_n), C.c_int64(P), _ptr(ref_rec), _ptr(ref_n), C.c_int64(M), _ptr(ref_index),
+                                           C.c_int32(max_nodes), *(_ptr(t) for t in out), _stream())
+    _check(st, "ds_graph_identity_records")
+    return out
+
+
+def graph_hash_records(rec: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
+    """``ds_graph_hash_records``: the permutation-invariant 64-bit hash of the labelled graph of every record (formula in the header).
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> ``[P] i64`` holding the hash's 64 bits (torch sorts and buckets int64; read them as unsigned with
+    ``& (2**64 - 1)``), on the current stream.  Equal hashes do not prove identity - ``graph_identity_records`` decides."""
+    _want(rec, "rec", torch.uint8, (None, RECORD_BYTES))
+    P = rec.shape[0]
+    _want(n, "n", torch.int32, (P,))
+    if rec.device.type != "cuda" or n.device != rec.device:
+        raise RuntimeError("graph_hash_records needs its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    lib = load_library()
+    out = torch.empty(P, dtype=torch.int64, device=rec.device)
+    with torch.cuda.device(rec.device):
+        st = lib.ds_graph_hash_records(_ptr(rec), _ptr(n), C.c_int64(P), _ptr(out), _stream())
+    _check(st, "ds_graph_hash_records")
     return out
 
 
@@ -565,6 +627,14 @@ class DmtEngine:
     def match_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, max_distance: float = 5.0, min_atoms: int = 3):
         """``engine.match_records`` on this engine's library (the structure metric needs no weights)."""
         return match_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, max_distance, min_atoms)
+
+    def graph_identity_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, max_nodes: int = 4096):
+        """``engine.graph_identity_records`` on this engine's library (graph identity needs no weights)."""
+        return graph_identity_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, max_nodes)
+
+    def graph_hash_records(self, rec, n):
+        """``engine.graph_hash_records`` on this engine's library."""
+        return graph_hash_records(rec, n)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

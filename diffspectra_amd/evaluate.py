@@ -60,10 +60,10 @@ def checkpoint_ids(config):
 
 def _structure_summary(run, table, top_k: int) -> Dict:
     """The structure metric of one finished sharded run: every sample slot's record against the ground-truth record of its dataset item."""
-    from .structure_metrics import hungarian_rmsd_batch, topk_summary
+    from .structure_metrics import graph_classes, graph_identity_batch, hungarian_rmsd_batch, topk_identity, topk_summary
     dev = run.records_by_slot.device
-    per_pair = hungarian_rmsd_batch((table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms)),
-                                    engine=run.eng, ref_index=run.slot_ds, raw=True)
+    ref, prb = (table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms))
+    per_pair = hungarian_rmsd_batch(ref, prb, engine=run.eng, ref_index=run.slot_ds, raw=True)
     ok = per_pair.valid
     n_ok, P = int(ok.sum()), ok.numel()
     mean = lambda t: float(t[ok].double().mean()) if n_ok else None
@@ -73,6 +73,14 @@ def _structure_summary(run, table, top_k: int) -> Dict:
                exact_rate=float(per_pair.exact.double().mean()) if P else 0.0, per_pair=per_pair)
     if top_k > 1:
         out["top_k"] = topk_summary(per_pair, top_k)
+    # graph identity: the conformation-independent decision behind Top-1 / Top-K accuracy, and the uniqueness of what was generated
+    same = graph_identity_batch(ref, prb, ref_index=run.slot_ds, engine=run.eng)
+    classes = graph_classes(prb[0], prb[1], engine=run.eng)
+    graph = dict(verdict=same.verdict, identity_rate=float(same.identical.double().mean()) if P else 0.0, undecided=int(same.undecided.sum()),
+                 unique_fraction=classes.unique().numel() / P if P else 0.0)
+    if top_k > 1:
+        graph["top_k"] = topk_identity(same.verdict, top_k)
+    out["graph"] = graph
     return out
 
 
@@ -85,6 +93,12 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     GPU from the run's ``records_by_slot`` (``structure_metrics.py``; no RDKit): ``rmsd_list, success_rate, mean_rmsd,
     mean_atom_type_accuracy`` of ``eval_sampled_mols/rmsd.py:232-273``, ``mean_bond_accuracy``, ``exact_rate`` and the raw ``per_pair``
     device tensors; with ``config.eval.top_k`` = K > 1 the run draws K candidates per spectrum and ``'top_k'`` holds ``topk_summary``.
+    ``metrics['structure']['graph']`` is the reference's headline number without RDKit: ``verdict`` (device tensor of
+    ``ds_graph_identity_records``: 1 = the generated molecule IS the ground-truth graph, in any conformation), ``identity_rate`` (Top-1
+    accuracy over all slots), ``undecided`` (pairs whose search ran out of budget; they count as misses), ``unique_fraction`` of the
+    generated records (``graph_classes``) and, with K > 1, ``top_k = topk_identity(...)`` whose ``acc_at_k`` is the Top-K accuracy.  Identity
+    is constitution-level (atom type, formal charge, bond order): unlike the reference's InChIKey comparison (``compute_metrics.py:222-230``)
+    it has no stereo layer and no InChI normalisation of tautomers or charges.
 
     ``test_ds=None`` reads the reference's processed files under ``config.data.root`` (``run_lib.py:313`` ->
     ``build_dataset.py:31-42``: the 'test' entry of ``split_dict_diffspectra_qm9.pt``) into the device-resident table of

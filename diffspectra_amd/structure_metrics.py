@@ -9,6 +9,12 @@ tensors (``records_from_graph``).  Two outputs go beyond the reference: ``bond_a
 not a graph isomorphism, so ``exact = 1`` is a *certified* hit.  ``exact = 0`` proves nothing (a correct graph in another conformation can
 be matched atom-for-atom differently), so hit@K computed from it is a LOWER bound on Top-K accuracy.
 
+The accuracy itself - is a generated molecule THE ground-truth molecule - is ``graph_identity_batch`` / ``topk_identity``: a
+conformation-independent decision per pair by ``ds_graph_identity_records`` (``csrc/ds_graph.hip``), and ``graph_classes`` gives the
+uniqueness figure of ``evaluation/rdkit_metric.py`` from a permutation-invariant hash plus the same decision.  Identity here is
+constitution-level (atom type, formal charge, bond order under a bijection, whole molecules): it is NOT InChIKey identity - no stereo
+layer, no InChI normalisation of tautomers or charges.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -126,3 +132,73 @@ def topk_summary(per_pair, top_k: int) -> Dict[str, torch.Tensor]:
     hit = exact.reshape(-1, top_k).bool().any(dim=1)
     hit_at_k = hit.double().mean() if hit.numel() else torch.zeros((), dtype=torch.float64, device=hit.device)
     return dict(best_rmsd=best, best_index=arg, hit=hit, hit_at_k=hit_at_k)
+
+
+# ------------------------------------------------------------------------------------------------------------------ graph identity
+
+class GraphIdentity(NamedTuple):
+    """Per-pair device tensors of ``ds_graph_identity_records``."""
+    verdict: torch.Tensor     # [P] u8: 1 identical (map is a checked isomorphism), 0 different (proven), 2 undecided (budget), 3 invalid row
+    nodes: torch.Tensor       # [P] i32 search nodes used
+    map: torch.Tensor         # [P, 29] i32 ground-truth atom of every generated atom when identical, else -1
+
+    @property
+    def identical(self) -> torch.Tensor:
+        return self.verdict == 1
+
+    @property
+    def undecided(self) -> torch.Tensor:
+        return self.verdict == 2
+
+
+def graph_identity_batch(ref, prb, ref_index=None, max_nodes: int = 4096, engine=None) -> GraphIdentity:
+    """Constitution-level identity (atom type, formal charge, bond order; no stereo, no tautomer / charge normalisation - not InChIKey
+    identity) of every generated molecule with its ground truth, independent of the conformation.  ``ref`` and ``prb`` are ``(records
+    [*, 1248] u8, n_atoms [*])`` pairs on the GPU, ground truth first as in ``hungarian_rmsd_batch``; ``ref_index [P]`` names the ground-truth
+    row of every generated molecule (``None``: row p).  Device tensors, no synchronisation."""
+    from . import engine as E
+    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
+    i32 = lambda t: torch.as_tensor(t).to(device=prb_rec.device, dtype=torch.int32).contiguous()
+    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=prb_rec.device, dtype=torch.int64).contiguous()
+    fn = engine.graph_identity_records if engine is not None else E.graph_identity_records
+    return GraphIdentity(*fn(prb_rec, i32(prb_n), ref_rec, i32(ref_n), idx, max_nodes))
+
+
+def topk_identity(verdict: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:
+    """Top-K accuracy over the K consecutive candidates of every spectrum from the verdicts of ``graph_identity_batch``: ``hit [S] bool`` (a
+    candidate is the ground-truth graph), ``first_hit [S] i64`` (index of the first such candidate, -1 if none), ``acc_at_k`` (mean of ``hit``, a
+    0-dim f64 tensor) and ``undecided`` (0-dim i64 count).  An undecided pair counts as a miss, so with ``undecided > 0`` the accuracy is a
+    lower bound, short by at most ``undecided / S``.  The accuracy is over constitution-level identity, not InChIKeys."""
+    if top_k < 1 or verdict.numel() % top_k:
+        raise ValueError(f"{verdict.numel()} pairs are not a whole number of top_k = {top_k} groups")
+    same = (verdict == 1).reshape(-1, top_k)
+    hit = same.any(dim=1)
+    first = torch.where(hit, same.to(torch.uint8).argmax(dim=1), torch.full_like(hit, -1, dtype=torch.int64))
+    acc = hit.double().mean() if hit.numel() else torch.zeros((), dtype=torch.float64, device=hit.device)
+    return dict(hit=hit, first_hit=first, acc_at_k=acc, undecided=(verdict == 2).sum())
+
+
+def graph_classes(records: torch.Tensor, n_atoms, engine=None) -> torch.Tensor:
+    """``class_id [P] i64``: the lowest row whose molecule is the same labelled graph as row p's (``unique_fraction = class_id.unique().numel()
+    / P``, the uniqueness of ``evaluation/rdkit_metric.py`` at constitution level).  Rows are bucketed by ``ds_graph_hash_records``; inside a
+    bucket every row is compared with the bucket's lowest unassigned row by ``ds_graph_identity_records`` (the table is its own ground
+    truth), and the rows that differ go round again - as many launches as the fullest bucket has classes, no Python per molecule.  An
+    undecided comparison raises."""
+    from . import engine as E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    hash_fn, same_fn = (engine.graph_hash_records, engine.graph_identity_records) if engine is not None else (E.graph_hash_records, E.graph_identity_records)
+    P = records.shape[0]
+    rows = torch.arange(P, device=records.device)
+    _, bucket = torch.unique(hash_fn(records, n), return_inverse=True)
+    class_id = torch.full((P,), -1, dtype=torch.int64, device=records.device)
+    pending = rows
+    while pending.numel():
+        lowest = torch.full((P,), P, dtype=torch.int64, device=records.device).scatter_reduce_(0, bucket[pending], pending, "amin")
+        rep = lowest[bucket[pending]]                                 # the lowest unassigned row of each pending row's bucket
+        verdict = same_fn(records[pending].contiguous(), n[pending].contiguous(), records, n, rep)[0]
+        if bool((verdict > 1).any()):
+            raise RuntimeError("graph_classes: a comparison ran out of its search budget (verdict 2); the classes are not known")
+        same = verdict == 1
+        class_id[pending[same]] = rep[same]
+        pending = pending[~same]
+    return class_id

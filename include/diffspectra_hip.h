@@ -23,6 +23,8 @@
  *   ds_post_process       post_process + inverse scaler       sampling.py:53-97, utils.py:88-103
  *   ds_check_stability    check_stability (distance half)     evaluation/stability.py:40-73, evaluation/bond_analyze.py:108-133
  *   ds_match_records      hungarian_atom_mapping              eval_sampled_mols/rmsd.py:12-73,106-128,153-227
+ *   ds_graph_identity_records   the InChIKey comparison behind Top-K accuracy   compute_metrics.py:222-230, run_lib.py:141
+ *   ds_graph_hash_records       the uniqueness count                           evaluation/rdkit_metric.py
  *   ds_gemm / ds_spec_*   SpecFormer.forward                  models/specformer.py:77-120,167-200,279-309,345-425,457-470
  *
  * Data layout ("packed-ragged", symmetric pair storage — DESIGN.md §3):
@@ -290,6 +292,46 @@ int ds_check_stability(const ds_layout* L, const float* pos, const int32_t* atom
 int ds_match_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
                      const int64_t* ref_index, float max_distance, int32_t min_atoms, double* rmsd, int32_t* n_matched,
                      float* type_acc, float* bond_acc, uint8_t* exact, int32_t* map, void* stream);
+
+/* Molecular-graph identity of (generated, ground-truth) pairs, one wave per pair, integers only: is there a bijection of the atoms that
+ * preserves the decoder atom type, the formal-charge byte and the bond-order byte of every atom pair?  Records, ref_index and the clamping
+ * of n are those of ds_match_records (bond bytes from the upper triangle of the record's matrix; the diagonal is no pair); coordinates are
+ * never read, so the answer does not depend on the conformation.  Whole molecules are compared, disconnected pieces included; unequal atom
+ * counts are different; two 0-atom molecules are identical with an empty map.
+ *   This is identity of the CONSTITUTION.  It is not InChIKey identity, which the reference compares (compute_metrics.py:222-230): there is
+ *   no stereo layer (enantiomers and E/Z isomers are identical here) and no InChI normalisation (two tautomers, or two ways of writing a
+ *   charge-separated group, are different here).
+ * Method: individualisation-refinement.  Colour = joint rank of (type, charge) over both molecules; a refinement round ranks, again jointly,
+ * (own colour, multiset of (bond order, neighbour colour) over the bonded neighbours) until the number of classes stops growing.  Differing
+ * colour histograms prove the graphs different; all classes singletons leaves one candidate bijection, which is verified byte by byte;
+ * otherwise the lowest generated atom of the lowest class with several atoms is individualised against every ground-truth atom of that
+ * class in ascending order (one SEARCH NODE per try), depth first, the first verified bijection wins.
+ *   verdict u8  DS_GRAPH_IDENTICAL  map is an isomorphism that the kernel has checked explicitly (every type, charge and bond byte)
+ *               DS_GRAPH_DIFFERENT  proven: unequal atom counts, an invariant mismatch at the root, or an exhausted search
+ *               DS_GRAPH_UNDECIDED  a further try would exceed max_nodes (max_nodes = 0 is plain colour refinement)
+ *               DS_GRAPH_INVALID    ref_index outside [0, M): nothing is read
+ *   nodes  i32  search nodes used (0 when refinement alone decides)
+ *   map [P,29] i32  ground-truth atom of every generated atom when verdict = DS_GRAPH_IDENTICAL, -1 everywhere otherwise
+ * max_nodes outside [0, DS_GRAPH_MAX_NODES] is DS_ERR_ARG.  Every loop of the kernel is bounded (rounds <= n + 1, depth <= n, tries <=
+ * max_nodes): a malformed record ends in a verdict.  P = 0 launches nothing.  No atomics; a pair's outputs do not depend on the batch. */
+#define DS_GRAPH_DIFFERENT 0
+#define DS_GRAPH_IDENTICAL 1
+#define DS_GRAPH_UNDECIDED 2
+#define DS_GRAPH_INVALID 3
+#define DS_GRAPH_MAX_NODES 1048576    /* 1 << 20 */
+int ds_graph_identity_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
+                              const int64_t* ref_index, int32_t max_nodes, uint8_t* verdict, int32_t* nodes, int32_t* map, void* stream);
+
+/* Permutation-invariant 64-bit hash of the labelled graph of every record, one wave per molecule (n clamped to 0..29, bond bytes as above).
+ * All arithmetic is unsigned 64-bit with wrap-around.  With
+ *   fmix(x):    x ^= x >> 30;  x *= 0xbf58476d1ce4e5b9;  x ^= x >> 27;  x *= 0x94d049bb133111eb;  x ^= x >> 31
+ *   mix(a, b) = fmix(a + 0x9e3779b97f4a7c15 * (b + 1))
+ * the atoms start at h_i = mix(type_i, charge_i) (both as the unsigned byte of the record), then 29 rounds of
+ *   h_i <- mix(h_i, sum over j != i with bond_ij > 0 of mix(h_j, bond_ij))          (all h_j of the previous round)
+ * and hash = mix(n, sum_i fmix(h_i)).  Identical graphs have equal hashes by construction.  Equal hashes do NOT prove identity: molecules
+ * that colour refinement cannot tell apart (a hexagon and two triangles of one atom type) collide on purpose, and 64 bits can collide
+ * by chance; ds_graph_identity_records decides. */
+int ds_graph_hash_records(const uint8_t* rec, const int32_t* n, int64_t P, uint64_t* hash, void* stream);
 
 /* SpecFormer pieces that are not plain GEMMs (specformer.py:385-425 residual-score attention; :119 LayerNorm).
  * qkv [B,L,3*heads*dk]; out [B,L,heads*dk]; scores: B*heads*L*L floats of caller-owned scratch that carries the

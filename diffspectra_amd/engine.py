@@ -489,6 +489,54 @@ def graph_hash_records(rec: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------------- MCES distance
+
+MCES_MAX_NODES = CONSTS["DS_MCES_MAX_NODES"]
+MCES_EXACT, MCES_UNDECIDED, MCES_INVALID = (CONSTS["DS_MCES_" + k] for k in ("EXACT", "UNDECIDED", "INVALID"))
+
+
+def mces_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                 ref_index: Optional[torch.Tensor] = None, drop_h: bool = True, max_nodes: int = 1 << 18):
+    """``ds_mces_records``: the exact maximum-common-edge-subgraph distance of each of P (generated, ground-truth) pairs as labelled graphs
+    (atom type and bond order; the formal charge is not compared; ``drop_h`` leaves the hydrogens out) - ``W_A + W_B - 2 max score``, an
+    integer, by branch-and-bound (definition and soundness in the header).  It stands in for the reference's "MCES (Average)" with two
+    stated deviations: the records hold Kekule orders 1..3 and not RDKit's aromatic 1.5 (two Kekule drawings of o-xylene are 2 apart), and
+    parity with the ``myopic_mces`` package itself is unpinned (it cannot be run here).
+
+    The tensors are those of ``match_records``.  Returns the device tensors ``(dist [P] i32, lower [P] i32, status [P] u8, nodes [P] i32,
+    map [P, 29] i32)``, enqueued on the current stream without synchronising: status ``MCES_EXACT`` (0: ``dist`` is the distance),
+    ``MCES_UNDECIDED`` (2: the search needed more than ``max_nodes`` tries; ``lower <= distance <= dist``, and ``map`` still achieves ``dist``)
+    or ``MCES_INVALID`` (3: ``ref_index`` outside the table, ``dist = lower = -1``).  The arguments are checked, never converted."""
+    _want(prb_rec, "prb_rec", torch.uint8, (None, RECORD_BYTES))
+    _want(ref_rec, "ref_rec", torch.uint8, (None, RECORD_BYTES))
+    P, M = prb_rec.shape[0], ref_rec.shape[0]
+    _want(prb_n, "prb_n", torch.int32, (P,))
+    _want(ref_n, "ref_n", torch.int32, (M,))
+    if ref_index is not None:
+        _want(ref_index, "ref_index", torch.int64, (P,))
+    elif M < P:
+        raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
+    if not isinstance(drop_h, bool):
+        raise TypeError(f"drop_h must be a bool, got {type(drop_h).__name__}")
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, int):
+        raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
+    if not 0 <= max_nodes <= MCES_MAX_NODES:
+        raise ValueError(f"max_nodes must lie in [0, {MCES_MAX_NODES}], got {max_nodes}")
+    dev = prb_rec.device
+    tensors = [prb_rec, prb_n, ref_rec, ref_n] + ([ref_index] if ref_index is not None else [])
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise RuntimeError("mces_records needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    lib = load_library()
+    out = (torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+           torch.empty(P, dtype=torch.uint8, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+           torch.empty(P, MAX_ATOMS, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        st = lib.ds_mces_records(_ptr(prb_rec), _ptr(prb_n), C.c_int64(P), _ptr(ref_rec), _ptr(ref_n), C.c_int64(M), _ptr(ref_index),
+                                 C.c_int32(int(drop_h)), C.c_int32(max_nodes), *(_ptr(t) for t in out), _stream())
+    _check(st, "ds_mces_records")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -635,6 +683,10 @@ class DmtEngine:
     def graph_hash_records(self, rec, n):
         """``engine.graph_hash_records`` on this engine's library."""
         return graph_hash_records(rec, n)
+
+    def mces_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, drop_h: bool = True, max_nodes: int = 1 << 18):
+        """``engine.mces_records`` on this engine's library (the MCES distance needs no weights)."""
+        return mces_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, drop_h, max_nodes)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

@@ -15,6 +15,11 @@ uniqueness figure of ``evaluation/rdkit_metric.py`` from a permutation-invariant
 constitution-level (atom type, formal charge, bond order under a bijection, whole molecules): it is NOT InChIKey identity - no stereo
 layer, no InChI normalisation of tautomers or charges.
 
+How far a wrong molecule is from the right one is ``mces_batch`` / ``topk_mces``: the exact maximum-common-edge-subgraph distance per pair by
+``ds_mces_records`` (``csrc/ds_mces.hip``), the reference's "MCES (Average)" (``compute_metrics.py:235-243``: one ``myopic_mces`` ILP per
+pair).  It deviates from that number in two stated ways: Kekule bond orders 1..3 instead of RDKit's aromatic 1.5, and parity with the
+``myopic_mces`` package itself is unpinned (it cannot be run here).
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -202,3 +207,57 @@ def graph_classes(records: torch.Tensor, n_atoms, engine=None) -> torch.Tensor:
         class_id[pending[same]] = rep[same]
         pending = pending[~same]
     return class_id
+
+
+# ------------------------------------------------------------------------------------------------------------------ MCES distance
+
+class Mces(NamedTuple):
+    """Per-pair device tensors of ``ds_mces_records``."""
+    dist: torch.Tensor        # [P] i32: W_A + W_B - 2 best, an upper bound that ``map`` achieves (the distance when exact); -1 for an invalid row
+    lower: torch.Tensor       # [P] i32: a lower bound on the distance (= dist when exact)
+    status: torch.Tensor      # [P] u8: 0 exact, 2 undecided (budget), 3 invalid row
+    nodes: torch.Tensor       # [P] i32 tries used
+    map: torch.Tensor         # [P, 29] i32 ground-truth atom of every generated atom in the best map, -1 where unmapped or dropped
+
+    @property
+    def exact(self) -> torch.Tensor:
+        return self.status == 0
+
+    @property
+    def undecided(self) -> torch.Tensor:
+        return self.status == 2
+
+
+def mces_batch(ref, prb, ref_index=None, drop_h: bool = True, max_nodes: int = 1 << 18, engine=None) -> Mces:
+    """Exact maximum-common-edge-subgraph distance of every generated molecule from its ground truth (``ds_mces_records``,
+    ``csrc/ds_mces.hip``): ``W_A + W_B - 2 max score`` over the type-preserving partial atom maps, bond weight = bond order, formal charges
+    not compared, hydrogens left out with ``drop_h`` - the graded number next to ``graph_identity_batch``'s verdict, standing in for the
+    reference's "MCES (Average)" (``compute_metrics.py:235-243``).  Two deviations from that number: the records hold Kekule orders 1..3, not
+    RDKit's aromatic 1.5, so two Kekule drawings of one substituted ring are a non-zero distance apart (o-xylene: 2); and parity with the
+    ``myopic_mces`` package itself is unpinned, because it cannot be run here.  Arguments as ``graph_identity_batch``.  Device tensors, no
+    synchronisation."""
+    from . import engine as E
+    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
+    i32 = lambda t: torch.as_tensor(t).to(device=prb_rec.device, dtype=torch.int32).contiguous()
+    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=prb_rec.device, dtype=torch.int64).contiguous()
+    fn = engine.mces_records if engine is not None else E.mces_records
+    return Mces(*fn(prb_rec, i32(prb_n), ref_rec, i32(ref_n), idx, drop_h, max_nodes))
+
+
+def topk_mces(dist: torch.Tensor, status: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:
+    """Best-of-K reductions of ``mces_batch`` over the K consecutive candidates of every spectrum: ``best [S] i32`` (the smallest distance
+    among the valid candidates, -1 when all K are invalid), ``best_index [S] i64`` (the first candidate with it, -1 when all are invalid),
+    ``mean_best`` (mean of ``best`` over the spectra that have one, a 0-dim f64 tensor; NaN without any) and ``undecided`` (0-dim i64 count).
+    An undecided pair keeps its upper bound ``dist``, so with ``undecided > 0`` ``best`` and ``mean_best`` are upper bounds.  Plain torch
+    reductions on the tensors' device."""
+    if top_k < 1 or dist.numel() % top_k or status.shape != dist.shape:
+        raise ValueError(f"{dist.numel()} pairs (status: {status.numel()}) are not a whole number of top_k = {top_k} groups")
+    d, bad = dist.reshape(-1, top_k), (status == 3).reshape(-1, top_k)
+    filled = torch.where(bad, torch.full_like(d, torch.iinfo(d.dtype).max), d)
+    best = filled.min(dim=1).values
+    arg = (filled == best.unsqueeze(1)).to(torch.uint8).argmax(dim=1)             # the first candidate that reaches the minimum
+    none = bad.all(dim=1)
+    best = torch.where(none, torch.full_like(best, -1), best)
+    arg = torch.where(none, torch.full_like(arg, -1), arg)
+    mean_best = torch.where(none, torch.zeros_like(best), best).double().sum() / (~none).sum()      # 0 / 0 = NaN without any spectrum
+    return dict(best=best, best_index=arg, mean_best=mean_best, undecided=(status == 2).sum())

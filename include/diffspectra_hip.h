@@ -25,6 +25,7 @@
  *   ds_match_records      hungarian_atom_mapping              eval_sampled_mols/rmsd.py:12-73,106-128,153-227
  *   ds_graph_identity_records   the InChIKey comparison behind Top-K accuracy   compute_metrics.py:222-230, run_lib.py:141
  *   ds_graph_hash_records       the uniqueness count                           evaluation/rdkit_metric.py
+ *   ds_mces_records             MCES (Average): one myopic_mces ILP per pair   compute_metrics.py:235-243, run_lib.py:149
  *   ds_gemm / ds_spec_*   SpecFormer.forward                  models/specformer.py:77-120,167-200,279-309,345-425,457-470
  *
  * Data layout ("packed-ragged", symmetric pair storage — DESIGN.md §3):
@@ -332,6 +333,56 @@ int ds_graph_identity_records(const uint8_t* prb_rec, const int32_t* prb_n, int6
  * that colour refinement cannot tell apart (a hexagon and two triangles of one atom type) collide on purpose, and 64 bits can collide
  * by chance; ds_graph_identity_records decides. */
 int ds_graph_hash_records(const uint8_t* rec, const int32_t* n, int64_t P, uint64_t* hash, void* stream);
+
+/* Exact MCES (maximum common edge subgraph) distance of (generated, ground-truth) pairs, one wave per pair, integers only: how far a wrong
+ * molecule is from the right one as a labelled graph.  Replaces the reference's "MCES (Average)" (compute_metrics.py:235-243, run_lib.py:149:
+ * one myopic_mces ILP per pair through pulp, on SMILES made by RDKit).  Records, ref_index and the clamping of n (0..29) are those of
+ * ds_graph_identity_records: bond bytes from the upper triangle, coordinates never read.  drop_h = 1 leaves out the atoms of decoder type 0
+ * (hydrogen) and their bonds, as the reference's SMILES route does; drop_h = 0 keeps every atom.
+ *   A bond's weight w is its bond-order byte, an integer.  The formal-charge byte is NOT compared (myopic_mces labels nodes by element only).
+ *   A common subgraph is a partial injective map pi from atoms of A (generated) to atoms of B (ground truth) of the same type.
+ *     score(pi) = sum over bonds (i, j) of A with both ends mapped and (pi i, pi j) bonded in B of min(w_A(i, j), w_B(pi i, pi j))
+ *     dist      = W_A + W_B - 2 max_pi score(pi),   W = a side's total bond weight
+ *   which restates the myopic_mces objective: an unmatched bond costs its weight, a matched one |w - w'|.  dist is an integer, symmetric in A
+ *   and B, and 0 exactly when the kept graphs, their bondless atoms set aside (an atom without a bond has no edge to lose: methane / water is
+ *   0), are identical up to the formal charges.
+ * Two deviations from the reference's number:
+ *   - the records hold Kekule orders 1..3, not RDKit's aromatic 1.5, so two Kekule drawings of one substituted ring are a non-zero distance
+ *     apart (o-xylene, its two drawings: 2; benzene: 0);
+ *   - parity with the myopic_mces package itself is unpinned: it cannot be run where this project runs.  The tests compare with the same
+ *     integer program restated on scipy.optimize.milp and with exhaustive enumeration (tests/mces_mirror.py).
+ * Method: depth-first branch-and-bound.  The atoms of A are ordered (largest weighted degree first, then the largest bond weight into the
+ * atoms already ordered, ties to the larger weighted degree, then the lower index); at a level every unused ground-truth atom of the same
+ * type is a candidate image, tried in descending gain (score added by the bonds into already-mapped neighbours; lowest index on ties), then
+ * "unmapped".  One try is one SEARCH NODE.  A try whose score beats the best so far becomes the best map at once (a partial map is a common
+ * subgraph).  The search descends only if bound > best, bound = score + min(rem_a, rem_b):
+ *     ub_A(e) = max over bonds f of B whose end types match e's of min(w_e, w_f); ub_B likewise
+ *     rem_a   = sum of ub_A(e) over bonds of A with an undecided end and no end decided "unmapped"
+ *     rem_b   = sum of ub_B(f) over bonds of B whose ends are not both used
+ * and the remaining images of a level are skipped once score + gain + rem_a <= best.  The search ends when best reaches the root bound
+ * min(sum ub_A, sum ub_B) or nothing is left to try.
+ * Soundness: every bond of A that can still add to the score has an undecided end and no end left out, and adds at most ub_A; a bond of B
+ * with both ends used has its preimage decided, so its share is in the score, and every other adds at most ub_B once - both terms are upper
+ * bounds on any completion, so a skipped subtree holds nothing better than best.  dist is computed from a map the kernel holds (returned in
+ * `map`), so it is an upper bound whatever the budget; lower comes from the root bound.  (Types beyond the seventh distinct one of a pair
+ * share one class in ub only, which can only raise the bound.)
+ *   dist   i32  W_A + W_B - 2 best: an upper bound that `map` achieves; the distance when status = DS_MCES_EXACT
+ *   lower  i32  W_A + W_B - 2 (root bound) when undecided, = dist when exact
+ *   status u8   DS_MCES_EXACT      the search was exhausted or best reached the root bound
+ *               DS_MCES_UNDECIDED  a further try would exceed max_nodes: lower <= distance <= dist
+ *               DS_MCES_INVALID    ref_index outside [0, M): nothing is read, dist = lower = -1, map all -1
+ *   nodes  i32  tries used
+ *   map [P,29] i32  ground-truth atom of every generated atom in the best map (original indices), -1 where unmapped or dropped
+ * max_nodes outside [0, DS_MCES_MAX_NODES] and drop_h outside {0, 1} are DS_ERR_ARG.  Every loop of the kernel is bounded (depth <= 29,
+ * passes <= 2 max_nodes + 64): a malformed record ends in a verdict.  P = 0 launches nothing.  No atomics; a pair's outputs do not depend on
+ * the batch. */
+#define DS_MCES_EXACT 0
+#define DS_MCES_UNDECIDED 2
+#define DS_MCES_INVALID 3
+#define DS_MCES_MAX_NODES 4194304     /* 1 << 22 */
+int ds_mces_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
+                    const int64_t* ref_index, int32_t drop_h, int32_t max_nodes, int32_t* dist, int32_t* lower, uint8_t* status,
+                    int32_t* nodes, int32_t* map, void* stream);
 
 /* SpecFormer pieces that are not plain GEMMs (specformer.py:385-425 residual-score attention; :119 LayerNorm).
  * qkv [B,L,3*heads*dk]; out [B,L,heads*dk]; scores: B*heads*L*L floats of caller-owned scratch that carries the

@@ -17,16 +17,15 @@
 #include <stdint.h>
 
 #include "../../include/diffspectra_hip.h"
+#include "ds_records.h"
 #include "ds_train_common.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-constexpr int MA = DS_MAX_ATOMS;          // 29 atoms: lanes 0..28 hold the generated molecule, lanes 32..60 the ground truth
-constexpr int REC_TYPE = MA * 12, REC_FC = REC_TYPE + MA, REC_BOND = REC_FC + MA;   // 348, 377, 406 (shard.pack_records_u8)
-static_assert(REC_BOND + MA * MA <= DS_RECORD_BYTES && DS_RECORD_BYTES % 4 == 0, "record layout");
+using ds_rec::MA;                         // 29 atoms: lanes 0..28 hold the generated molecule, lanes 32..60 the ground truth
+using ds_rec::uniform_i;
 constexpr int FRESH = 63;                 // colour of an individualised atom: ranks stay below 2 * 29 = 58
-
-__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+constexpr unsigned ALL = ~0u;             // keep mask of ds_rec::load_bonds: every atom (the kernels below mask by n where they read)
 
 // the 64-bit finaliser and the pair mix of the header's hash formula (wrap-around arithmetic)
 __device__ __forceinline__ uint64_t fmix(uint64_t x) {
@@ -35,24 +34,6 @@ __device__ __forceinline__ uint64_t fmix(uint64_t x) {
   return x ^ (x >> 31);
 }
 __device__ __forceinline__ uint64_t mix2(uint64_t a, uint64_t b) { return fmix(a + 0x9e3779b97f4a7c15ull * (b + 1ull)); }
-
-// Bond bytes of one record as a symmetric matrix adj[j * 32 + i] (the upper triangle of the record decides, as in ds_match_records; the
-// diagonal is no atom pair and reads 0).  The record is read as aligned dwords; every byte index stays inside the record.
-__device__ void load_bonds(unsigned char* __restrict__ adj, const unsigned char* __restrict__ rec, int lane) {
-  const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(rec);
-  for (int w = REC_BOND / 4 + lane; w < (REC_BOND + MA * MA + 3) / 4; w += 64) {      // dwords 101 .. 311 of 312
-    const uint32_t v = words[w];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = w * 4 + q - REC_BOND;
-      if (k < 0 || k >= MA * MA) continue;
-      const int i = k / MA, j = k - i * MA;
-      const unsigned char b = (unsigned char)(v >> (8 * q));
-      if (i < j) { adj[i * 32 + j] = b; adj[j * 32 + i] = b; }
-      else if (i == j) adj[i * 32 + i] = 0;
-    }
-  }
-}
 
 struct Pair {                             // both molecules of a pair in LDS; arrays of 64 are indexed by lane
   unsigned char adj[2][MA * 32];
@@ -146,18 +127,18 @@ __global__ __launch_bounds__(64) void k_graph_identity(const unsigned char* __re
   __shared__ Pair S;
   const int64_t p = blockIdx.x;
   const int lane = threadIdx.x, idx = lane & 31, side = lane >> 5;
-  const int64_t r = ref_index ? ref_index[p] : p;
+  const ds_rec::Pair q = ds_rec::pair_of(p, prb_rec, prb_n, ref_rec, ref_n, ref_index, M);
   int out = DS_GRAPH_INVALID, used = 0;
-  if (r >= 0 && r < M) {                                     // a row outside ref_rec is an invalid pair, never a read
-    const int ng = min(max(prb_n[p], 0), MA), nr = min(max(ref_n[r], 0), MA);
-    const unsigned char* __restrict__ mine = side ? ref_rec + r * DS_RECORD_BYTES : prb_rec + p * DS_RECORD_BYTES;
+  if (q.valid) {
+    const int ng = q.n_prb(), nr = q.n_ref();
+    const unsigned char* __restrict__ mine = side ? q.ref : q.prb;
     out = DS_GRAPH_DIFFERENT;
     if (ng == nr) {
       const int n = ng;
       const bool active = idx < n;
-      load_bonds(S.adj[0], prb_rec + p * DS_RECORD_BYTES, lane);
-      load_bonds(S.adj[1], ref_rec + r * DS_RECORD_BYTES, lane);
-      const unsigned type = active ? mine[REC_TYPE + idx] : 0u, fc = active ? mine[REC_FC + idx] : 0u;
+      ds_rec::load_bonds(S.adj[0], q.prb, ALL, lane);
+      ds_rec::load_bonds(S.adj[1], q.ref, ALL, lane);
+      const unsigned type = active ? mine[DS_REC_TYPE + idx] : 0u, fc = active ? mine[DS_REC_FC + idx] : 0u;
       S.type[lane] = (unsigned char)type;
       S.fc[lane] = (unsigned char)fc;
       __syncthreads();
@@ -224,11 +205,11 @@ __global__ __launch_bounds__(64) void k_graph_hash(const unsigned char* __restri
   __shared__ Molecule S;
   const int64_t p = blockIdx.x;
   const int lane = threadIdx.x;
-  const int n = min(max(n_atoms[p], 0), MA);
+  const int n = ds_rec::atoms_of(n_atoms, p);
   const unsigned char* __restrict__ mine = rec + p * DS_RECORD_BYTES;
   const bool active = lane < n;
-  load_bonds(S.adj, mine, lane);
-  unsigned long long h = active ? mix2(mine[REC_TYPE + lane], mine[REC_FC + lane]) : 0ull;
+  ds_rec::load_bonds(S.adj, mine, ALL, lane);
+  unsigned long long h = active ? mix2(mine[DS_REC_TYPE + lane], mine[DS_REC_FC + lane]) : 0ull;
   for (int round = 0; round < MA; ++round) {
     if (lane < 32) S.h[lane] = h;
     __syncthreads();
@@ -255,21 +236,17 @@ __global__ __launch_bounds__(64) void k_graph_hash(const unsigned char* __restri
 extern "C" int ds_graph_identity_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n,
                                          int64_t M, const int64_t* ref_index, int32_t max_nodes, uint8_t* verdict, int32_t* nodes, int32_t* map,
                                          void* stream) {
-  if (P < 0 || M < 0 || P > 0x7fffffffll || max_nodes < 0 || max_nodes > DS_GRAPH_MAX_NODES) return DS_ERR_ARG;
-  if (P == 0) return DS_OK;
-  if (!prb_rec || !prb_n || !verdict || !nodes || !map) return DS_ERR_ARG;
-  if (M > 0 && (!ref_rec || !ref_n)) return DS_ERR_ARG;
-  if (!ref_index && M < P) return DS_ERR_ARG;                // identity pairing needs a ground-truth row for every pair
-  if (reinterpret_cast<uintptr_t>(prb_rec) & 3 || reinterpret_cast<uintptr_t>(ref_rec) & 3) return DS_ERR_ARG;   // records are read as dwords
+  const int go = ds_rec::check_pairs(max_nodes >= 0 && max_nodes <= DS_GRAPH_MAX_NODES, P, M, prb_rec, prb_n, ref_rec, ref_n, ref_index,
+                                     {verdict, nodes, map});
+  if (go != ds_rec::LAUNCH) return go;
   hipLaunchKernelGGL(k_graph_identity, dim3((unsigned)P), dim3(64), 0, (hipStream_t)stream, prb_rec, prb_n, ref_rec, ref_n, ref_index, M,
                      (int)max_nodes, verdict, nodes, map);
   return DST_CHECK_LAUNCH();
 }
 
 extern "C" int ds_graph_hash_records(const uint8_t* rec, const int32_t* n, int64_t P, uint64_t* hash, void* stream) {
-  if (P < 0 || P > 0x7fffffffll) return DS_ERR_ARG;
-  if (P == 0) return DS_OK;
-  if (!rec || !n || !hash || reinterpret_cast<uintptr_t>(rec) & 3) return DS_ERR_ARG;
+  const int go = ds_rec::check_table(true, P, rec, n, {hash});
+  if (go != ds_rec::LAUNCH) return go;
   hipLaunchKernelGGL(k_graph_hash, dim3((unsigned)P), dim3(64), 0, (hipStream_t)stream, rec, n, reinterpret_cast<unsigned long long*>(hash));
   return DST_CHECK_LAUNCH();
 }

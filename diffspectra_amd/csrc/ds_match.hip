@@ -6,17 +6,15 @@
 #include <stdint.h>
 
 #include "../../include/diffspectra_hip.h"
+#include "ds_records.h"
 #include "ds_svd3.h"
 #include "ds_train_common.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-constexpr int MA = DS_MAX_ATOMS;          // 29 atoms: lanes 0..28 are atoms / assignment columns
-constexpr int REC_TYPE = MA * 12, REC_FC = REC_TYPE + MA, REC_BOND = REC_FC + MA;   // 348, 377, 406 (shard.pack_records_u8)
-static_assert(REC_BOND + MA * MA <= DS_RECORD_BYTES, "record layout");
+using ds_rec::MA;                         // 29 atoms: lanes 0..28 are atoms / assignment columns
+using ds_rec::uniform_i;
 
-// the value of lane 0 in every lane, as a wave-uniform (scalar) value
-__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ double uniform_d(double v) {
   const long long b = __double_as_longlong(v);
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
@@ -48,7 +46,7 @@ __device__ __forceinline__ int bond_of(const Side& s, int i, int j) { return s.b
 // Largest connected fragment (a bond is an order > 0; ties: the fragment that holds the lowest atom index; fragment atoms keep ascending
 // original order), its coordinates centred on its own centroid.  Lane = original atom.
 __device__ void load_side(Side& s, const unsigned char* __restrict__ rec, int n, int lane) {
-  for (int k = lane; k < MA * MA; k += 64) s.bond[k] = rec[REC_BOND + k];
+  for (int k = lane; k < MA * MA; k += 64) s.bond[k] = rec[DS_REC_BOND + k];
   if (lane == 0) s.n = n;
   __syncthreads();
   unsigned mine = 0;
@@ -80,8 +78,8 @@ __device__ void load_side(Side& s, const unsigned char* __restrict__ rec, int n,
   if (in) {
     const float* pos = reinterpret_cast<const float*>(rec) + lane * 3;
     p[0] = (double)pos[0]; p[1] = (double)pos[1]; p[2] = (double)pos[2];
-    s.type[k] = rec[REC_TYPE + lane];
-    s.fc[k] = (signed char)rec[REC_FC + lane];
+    s.type[k] = rec[DS_REC_TYPE + lane];
+    s.fc[k] = (signed char)rec[DS_REC_FC + lane];
     s.orig[k] = (unsigned char)lane;
     s.x[k][0] = p[0]; s.x[k][1] = p[1]; s.x[k][2] = p[2];
   }
@@ -180,13 +178,13 @@ __global__ __launch_bounds__(64) void k_match_records(const unsigned char* __res
   __shared__ int match[32];
   const int64_t p = blockIdx.x;
   const int lane = threadIdx.x;
-  const int64_t r = ref_index ? ref_index[p] : p;
+  const ds_rec::Pair q = ds_rec::pair_of(p, prb_rec, prb_n, ref_rec, ref_n, ref_index, M);
   const double NaN = __longlong_as_double(0x7ff8000000000000ll);
   int count = 0;
-  bool valid = r >= 0 && r < M;                              // a row outside ref_rec is an invalid pair, never a read
+  bool valid = q.valid;
   if (valid) {
-    load_side(G, prb_rec + p * DS_RECORD_BYTES, min(max(prb_n[p], 0), MA), lane);
-    load_side(R_, ref_rec + r * DS_RECORD_BYTES, min(max(ref_n[r], 0), MA), lane);
+    load_side(G, q.prb, q.n_prb(), lane);
+    load_side(R_, q.ref, q.n_ref(), lane);
     valid = min(G.nf, R_.nf) >= max(min_atoms, 1);           // the unclipped first match assigns every atom of the smaller fragment
     // a fragment with a non-finite coordinate (a diverged sample) has no cost matrix: the pair is invalid, as the reference's assignment
     // refuses such a matrix (rmsd.py:164-168).  Centring spreads one bad value over the whole fragment, so every lane sees it.
@@ -279,12 +277,9 @@ __global__ __launch_bounds__(64) void k_match_records(const unsigned char* __res
 extern "C" int ds_match_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
                                 const int64_t* ref_index, float max_distance, int32_t min_atoms, double* rmsd, int32_t* n_matched,
                                 float* type_acc, float* bond_acc, uint8_t* exact, int32_t* map, void* stream) {
-  if (P < 0 || M < 0 || P > 0x7fffffffll || max_distance != max_distance) return DS_ERR_ARG;
-  if (P == 0) return DS_OK;
-  if (!prb_rec || !prb_n || !rmsd || !n_matched || !type_acc || !bond_acc || !exact || !map) return DS_ERR_ARG;
-  if (M > 0 && (!ref_rec || !ref_n)) return DS_ERR_ARG;
-  if (!ref_index && M < P) return DS_ERR_ARG;                // identity pairing needs a ground-truth row for every pair
-  if (reinterpret_cast<uintptr_t>(prb_rec) & 3 || reinterpret_cast<uintptr_t>(ref_rec) & 3) return DS_ERR_ARG;   // fp32 positions inside
+  const int go = ds_rec::check_pairs(max_distance == max_distance, P, M, prb_rec, prb_n, ref_rec, ref_n, ref_index,
+                                     {rmsd, n_matched, type_acc, bond_acc, exact, map});
+  if (go != ds_rec::LAUNCH) return go;
   hipLaunchKernelGGL(k_match_records, dim3((unsigned)P), dim3(64), 0, (hipStream_t)stream, prb_rec, prb_n, ref_rec, ref_n, ref_index, M,
                      max_distance, (int)min_atoms, rmsd, n_matched, type_acc, bond_acc, exact, map);
   return DST_CHECK_LAUNCH();

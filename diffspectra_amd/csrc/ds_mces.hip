@@ -20,36 +20,15 @@
 #include <stdint.h>
 
 #include "../../include/diffspectra_hip.h"
+#include "ds_records.h"
 #include "ds_train_common.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-constexpr int MA = DS_MAX_ATOMS;          // 29 atoms: lanes 0..28 hold the generated molecule (A), lanes 32..60 the ground truth (B)
-constexpr int REC_TYPE = MA * 12, REC_FC = REC_TYPE + MA, REC_BOND = REC_FC + MA;   // 348, 377, 406 (shard.pack_records_u8)
-static_assert(REC_BOND + MA * MA <= DS_RECORD_BYTES && DS_RECORD_BYTES % 4 == 0, "record layout");
+using ds_rec::MA;                         // 29 atoms: lanes 0..28 hold the generated molecule (A), lanes 32..60 the ground truth (B)
+using ds_rec::uniform_i;
 constexpr int NCLS = 8;                   // type classes of the bound: one byte each of a 64-bit row
 constexpr unsigned NONE = 255;
-
-__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// Bond weights of one record as a symmetric matrix w[i * 32 + j] over ORIGINAL atom indices (the upper triangle of the record decides, the
-// diagonal reads 0); every pair with an end that is not kept (beyond n, or a dropped hydrogen) reads 0, so all 29 x 29 entries are defined.
-// The record is read as aligned dwords; every byte index stays inside the record.
-__device__ void load_weights(unsigned char* __restrict__ w, const unsigned char* __restrict__ rec, unsigned keep, int lane) {
-  const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(rec);
-  for (int d = REC_BOND / 4 + lane; d < (REC_BOND + MA * MA + 3) / 4; d += 64) {      // dwords 101 .. 311 of 312
-    const uint32_t v = words[d];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = d * 4 + q - REC_BOND;
-      if (k < 0 || k >= MA * MA) continue;
-      const int i = k / MA, j = k - i * MA;
-      const unsigned char b = ((keep >> i) & (keep >> j) & 1u) ? (unsigned char)(v >> (8 * q)) : (unsigned char)0;
-      if (i < j) { w[i * 32 + j] = b; w[j * 32 + i] = b; }
-      else if (i == j) w[i * 32 + i] = 0;
-    }
-  }
-}
 
 struct Level {                            // an open level d of the search: the state BEFORE atom order[d] is decided
   int used;                               // ground-truth atoms taken by levels 0 .. d-1
@@ -72,7 +51,7 @@ struct Lanes {
 };
 
 struct Search {
-  unsigned char w[2][MA * 32];            // bond weights, side 0 = A, 1 = B
+  unsigned char w[2][MA * 32];            // bond weights w[s][i * 32 + j] (ds_rec::load_bonds; 0 where an end is not kept), side 0 = A, 1 = B
   unsigned char cls[2][32];               // class 0..7 of every atom's type
   unsigned long long row[2][32];          // set-up: byte u of row[s][k] = heaviest bond of atom k of side s into class u
   unsigned long long tab[2][NCLS];        // byte u of tab[s][t] = heaviest bond of side s between classes t and u
@@ -140,21 +119,21 @@ __global__ __launch_bounds__(64) void k_mces_records(const unsigned char* __rest
   __shared__ Search S;
   const int64_t p = blockIdx.x;
   const int lane = threadIdx.x, idx = lane & 31, side = lane >> 5;
-  const int64_t r = ref_index ? ref_index[p] : p;
-  if (r < 0 || r >= M) {                                                   // a row outside ref_rec is an invalid pair, never a read
+  const ds_rec::Pair q = ds_rec::pair_of(p, prb_rec, prb_n, ref_rec, ref_n, ref_index, M);
+  if (!q.valid) {
     if (lane < MA) map[p * MA + lane] = -1;
     if (lane == 0) { dist[p] = -1; lower[p] = -1; status[p] = DS_MCES_INVALID; nodes[p] = 0; }
     return;
   }
-  const int n_a = min(max(prb_n[p], 0), MA), n_b = min(max(ref_n[r], 0), MA);
-  const unsigned char* __restrict__ mine = side ? ref_rec + r * DS_RECORD_BYTES : prb_rec + p * DS_RECORD_BYTES;
+  const int n_a = q.n_prb(), n_b = q.n_ref();
+  const unsigned char* __restrict__ mine = side ? q.ref : q.prb;
   const bool present = idx < (side ? n_b : n_a);
-  const unsigned type = present ? mine[REC_TYPE + idx] : 0u;
+  const unsigned type = present ? mine[DS_REC_TYPE + idx] : 0u;
   const bool keep = present && !(drop_h && type == 0u);
   const unsigned long long kept = __ballot(keep);
   const int row_of = min(idx, MA - 1);
-  load_weights(S.w[0], prb_rec + p * DS_RECORD_BYTES, (unsigned)kept, lane);
-  load_weights(S.w[1], ref_rec + r * DS_RECORD_BYTES, (unsigned)(kept >> 32), lane);
+  ds_rec::load_bonds(S.w[0], q.prb, (unsigned)kept, lane);                 // a pair with an end beyond n, or a dropped hydrogen, weighs 0
+  ds_rec::load_bonds(S.w[1], q.ref, (unsigned)(kept >> 32), lane);
   // class of an atom: its type's place among the pair's distinct types in order of first appearance (A before B), at most 7
   int cls = 0;
   {
@@ -289,12 +268,9 @@ __global__ __launch_bounds__(64) void k_mces_records(const unsigned char* __rest
 extern "C" int ds_mces_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
                                const int64_t* ref_index, int32_t drop_h, int32_t max_nodes, int32_t* dist, int32_t* lower, uint8_t* status,
                                int32_t* nodes, int32_t* map, void* stream) {
-  if (P < 0 || M < 0 || P > 0x7fffffffll || max_nodes < 0 || max_nodes > DS_MCES_MAX_NODES || (drop_h != 0 && drop_h != 1)) return DS_ERR_ARG;
-  if (P == 0) return DS_OK;
-  if (!prb_rec || !prb_n || !dist || !lower || !status || !nodes || !map) return DS_ERR_ARG;
-  if (M > 0 && (!ref_rec || !ref_n)) return DS_ERR_ARG;
-  if (!ref_index && M < P) return DS_ERR_ARG;                // identity pairing needs a ground-truth row for every pair
-  if (reinterpret_cast<uintptr_t>(prb_rec) & 3 || reinterpret_cast<uintptr_t>(ref_rec) & 3) return DS_ERR_ARG;   // records are read as dwords
+  const int go = ds_rec::check_pairs(max_nodes >= 0 && max_nodes <= DS_MCES_MAX_NODES && (drop_h == 0 || drop_h == 1), P, M, prb_rec, prb_n,
+                                     ref_rec, ref_n, ref_index, {dist, lower, status, nodes, map});
+  if (go != ds_rec::LAUNCH) return go;
   hipLaunchKernelGGL(k_mces_records, dim3((unsigned)P), dim3(64), 0, (hipStream_t)stream, prb_rec, prb_n, ref_rec, ref_n, ref_index, M,
                      (int)drop_h, (int)max_nodes, dist, lower, status, nodes, map);
   return DST_CHECK_LAUNCH();

@@ -394,6 +394,48 @@ def _want(t, name, dtype, shape):
         raise ValueError(f"{name} must be contiguous")
 
 
+def _record_call(name, tables, ref_index, scalars, outputs):
+    """The binding of an entry point on result records.  ``tables``: ``[(rec, n)]`` (``ds_graph_hash_records``; ``ref_index`` unused) or
+    ``[(prb_rec, prb_n), (ref_rec, ref_n)]`` with ``ref_index`` (the record pairs of the header).  Checks the tensors (never converts them),
+    the pairing rule and the one-device rule, allocates ``outputs`` - ``[(dtype, trailing shape)]``, one row per pair - and issues ``ds_<name>``
+    with the C ``scalars`` between the tables and the outputs, on the current stream of the tensors' device.  Returns the output tensors."""
+    pairs = len(tables) == 2
+    tensors, args = [], []
+    for (rec, n), (rec_name, n_name) in zip(tables, (("prb_rec", "prb_n"), ("ref_rec", "ref_n")) if pairs else (("rec", "n"),)):
+        _want(rec, rec_name, torch.uint8, (None, RECORD_BYTES))
+        _want(n, n_name, torch.int32, (rec.shape[0],))
+        tensors += [rec, n]
+        args += [_ptr(rec), _ptr(n), C.c_int64(rec.shape[0])]
+    P = tensors[0].shape[0]
+    if pairs:
+        if ref_index is not None:
+            _want(ref_index, "ref_index", torch.int64, (P,))
+            tensors.append(ref_index)
+        elif tensors[2].shape[0] < P:
+            raise ValueError(f"without ref_index pair p reads ground-truth row p: {tensors[2].shape[0]} rows for {P} pairs")
+        args.append(_ptr(ref_index))
+    dev = tensors[0].device
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise RuntimeError(f"{name} needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    lib = load_library()
+    out = tuple(torch.empty(P, *shape, dtype=dtype, device=dev) for dtype, shape in outputs)
+    with torch.cuda.device(dev):
+        st = getattr(lib, "ds_" + name)(*args, *scalars, *(_ptr(t) for t in out), _stream())
+    _check(st, "ds_" + name)
+    return out
+
+
+def _node_budget(max_nodes, most):
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, int):
+        raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
+    if not 0 <= max_nodes <= most:
+        raise ValueError(f"max_nodes must lie in [0, {most}], got {max_nodes}")
+    return C.c_int32(max_nodes)
+
+
+_MAP = (torch.int32, (MAX_ATOMS,))        # the atom map that every record-pair entry point returns last
+
+
 def match_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
                   ref_index: Optional[torch.Tensor] = None, max_distance: float = 5.0, min_atoms: int = 3):
     """``ds_match_records``: Hungarian-matched RMSD, type / bond accuracy and the exact-graph flag of P (generated, ground-truth) pairs.
@@ -402,31 +444,11 @@ def match_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Ten
     atom counts; ``ref_index [P] i64``: ground-truth row of every pair (``None``: pair p uses row p).  Returns the six device tensors
     ``(rmsd [P] f64, n_matched [P] i32, type_acc [P] f32, bond_acc [P] f32, exact [P] u8, map [P, 29] i32)``, enqueued on the current stream
     without synchronising.  The arguments are checked, never converted: a wrong dtype, shape or a non-contiguous tensor raises."""
-    _want(prb_rec, "prb_rec", torch.uint8, (None, RECORD_BYTES))
-    _want(ref_rec, "ref_rec", torch.uint8, (None, RECORD_BYTES))
-    P, M = prb_rec.shape[0], ref_rec.shape[0]
-    _want(prb_n, "prb_n", torch.int32, (P,))
-    _want(ref_n, "ref_n", torch.int32, (M,))
-    if ref_index is not None:
-        _want(ref_index, "ref_index", torch.int64, (P,))
-    elif M < P:
-        raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
     max_distance, min_atoms = float(max_distance), int(min_atoms)
     if max_distance != max_distance:
         raise ValueError("max_distance must not be NaN")
-    dev = prb_rec.device
-    tensors = [prb_rec, prb_n, ref_rec, ref_n] + ([ref_index] if ref_index is not None else [])
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError("match_records needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
-    lib = load_library()
-    out = (torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
-           torch.empty(P, dtype=torch.float32, device=dev), torch.empty(P, dtype=torch.float32, device=dev),
-           torch.empty(P, dtype=torch.uint8, device=dev), torch.empty(P, MAX_ATOMS, dtype=torch.int32, device=dev))
-    with torch.cuda.device(dev):
-        st = lib.ds_match_records(_ptr(prb_rec), _ptr(prb_n), C.c_int64(P), _ptr(ref_rec), _ptr(ref_n), C.c_int64(M), _ptr(ref_index),
-                                  C.c_float(max_distance), C.c_int32(min_atoms), *(_ptr(t) for t in out), _stream())
-    _check(st, "ds_match_records")
-    return out
+    return _record_call("match_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [C.c_float(max_distance), C.c_int32(min_atoms)],
+                        [(torch.float64, ()), (torch.int32, ()), (torch.float32, ()), (torch.float32, ()), (torch.uint8, ()), _MAP])
 
 
 # ----------------------------------------------------------------------------------------- graph identity
@@ -445,48 +467,15 @@ def graph_identity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: 
     the current stream without synchronising: verdict ``GRAPH_IDENTICAL`` (1: ``map`` is a checked isomorphism), ``GRAPH_DIFFERENT`` (0: proven),
     ``GRAPH_UNDECIDED`` (2: the search needed more than ``max_nodes`` tries; 0 = colour refinement alone) or ``GRAPH_INVALID`` (3: ``ref_index``
     outside the table).  The arguments are checked, never converted."""
-    _want(prb_rec, "prb_rec", torch.uint8, (None, RECORD_BYTES))
-    _want(ref_rec, "ref_rec", torch.uint8, (None, RECORD_BYTES))
-    P, M = prb_rec.shape[0], ref_rec.shape[0]
-    _want(prb_n, "prb_n", torch.int32, (P,))
-    _want(ref_n, "ref_n", torch.int32, (M,))
-    if ref_index is not None:
-        _want(ref_index, "ref_index", torch.int64, (P,))
-    elif M < P:
-        raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
-    if isinstance(max_nodes, bool) or not isinstance(max_nodes, int):
-        raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
-    if not 0 <= max_nodes <= GRAPH_MAX_NODES:
-        raise ValueError(f"max_nodes must lie in [0, {GRAPH_MAX_NODES}], got {max_nodes}")
-    dev = prb_rec.device
-    tensors = [prb_rec, prb_n, ref_rec, ref_n] + ([ref_index] if ref_index is not None else [])
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError("graph_identity_records needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
-    lib = load_library()
-    out = (torch.empty(P, dtype=torch.uint8, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
-           torch.empty(P, MAX_ATOMS, dtype=torch.int32, device=dev))
-    with torch.cuda.device(dev):
-        st = lib.ds_graph_identity_records(_ptr(prb_rec), _ptr(prb_n), C.c_int64(P), _ptr(ref_rec), _ptr(ref_n), C.c_int64(M), _ptr(ref_index),
-                                           C.c_int32(max_nodes), *(_ptr(t) for t in out), _stream())
-    _check(st, "ds_graph_identity_records")
-    return out
+    return _record_call("graph_identity_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [_node_budget(max_nodes, GRAPH_MAX_NODES)],
+                        [(torch.uint8, ()), (torch.int32, ()), _MAP])
 
 
 def graph_hash_records(rec: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
     """``ds_graph_hash_records``: the permutation-invariant 64-bit hash of the labelled graph of every record (formula in the header).
     ``rec [P, 1248] u8``, ``n [P] i32`` -> ``[P] i64`` holding the hash's 64 bits (torch sorts and buckets int64; read them as unsigned with
     ``& (2**64 - 1)``), on the current stream.  Equal hashes do not prove identity - ``graph_identity_records`` decides."""
-    _want(rec, "rec", torch.uint8, (None, RECORD_BYTES))
-    P = rec.shape[0]
-    _want(n, "n", torch.int32, (P,))
-    if rec.device.type != "cuda" or n.device != rec.device:
-        raise RuntimeError("graph_hash_records needs its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
-    lib = load_library()
-    out = torch.empty(P, dtype=torch.int64, device=rec.device)
-    with torch.cuda.device(rec.device):
-        st = lib.ds_graph_hash_records(_ptr(rec), _ptr(n), C.c_int64(P), _ptr(out), _stream())
-    _check(st, "ds_graph_hash_records")
-    return out
+    return _record_call("graph_hash_records", [(rec, n)], None, [], [(torch.int64, ())])[0]
 
 
 # ----------------------------------------------------------------------------------------- MCES distance
@@ -507,34 +496,10 @@ def mces_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tens
     map [P, 29] i32)``, enqueued on the current stream without synchronising: status ``MCES_EXACT`` (0: ``dist`` is the distance),
     ``MCES_UNDECIDED`` (2: the search needed more than ``max_nodes`` tries; ``lower <= distance <= dist``, and ``map`` still achieves ``dist``)
     or ``MCES_INVALID`` (3: ``ref_index`` outside the table, ``dist = lower = -1``).  The arguments are checked, never converted."""
-    _want(prb_rec, "prb_rec", torch.uint8, (None, RECORD_BYTES))
-    _want(ref_rec, "ref_rec", torch.uint8, (None, RECORD_BYTES))
-    P, M = prb_rec.shape[0], ref_rec.shape[0]
-    _want(prb_n, "prb_n", torch.int32, (P,))
-    _want(ref_n, "ref_n", torch.int32, (M,))
-    if ref_index is not None:
-        _want(ref_index, "ref_index", torch.int64, (P,))
-    elif M < P:
-        raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
     if not isinstance(drop_h, bool):
         raise TypeError(f"drop_h must be a bool, got {type(drop_h).__name__}")
-    if isinstance(max_nodes, bool) or not isinstance(max_nodes, int):
-        raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
-    if not 0 <= max_nodes <= MCES_MAX_NODES:
-        raise ValueError(f"max_nodes must lie in [0, {MCES_MAX_NODES}], got {max_nodes}")
-    dev = prb_rec.device
-    tensors = [prb_rec, prb_n, ref_rec, ref_n] + ([ref_index] if ref_index is not None else [])
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError("mces_records needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
-    lib = load_library()
-    out = (torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
-           torch.empty(P, dtype=torch.uint8, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
-           torch.empty(P, MAX_ATOMS, dtype=torch.int32, device=dev))
-    with torch.cuda.device(dev):
-        st = lib.ds_mces_records(_ptr(prb_rec), _ptr(prb_n), C.c_int64(P), _ptr(ref_rec), _ptr(ref_n), C.c_int64(M), _ptr(ref_index),
-                                 C.c_int32(int(drop_h)), C.c_int32(max_nodes), *(_ptr(t) for t in out), _stream())
-    _check(st, "ds_mces_records")
-    return out
+    return _record_call("mces_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [C.c_int32(int(drop_h)), _node_budget(max_nodes, MCES_MAX_NODES)],
+                        [(torch.int32, ()), (torch.int32, ()), (torch.uint8, ()), (torch.int32, ()), _MAP])
 
 
 # ----------------------------------------------------------------------------------------- engine

@@ -9,6 +9,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from . import abi
+
 
 def shard_bounds(total: int, rank: int, world: int):
     """Contiguous, balanced [lo, hi) block of ``total`` molecules for ``rank`` (first ``total % world`` ranks get +1)."""
@@ -36,8 +38,11 @@ def unpack_records(rec: torch.Tensor, N: int):
     return pos, atom, fc, et
 
 
-RECORD_ATOMS = 29          # DS_MAX_ATOMS: records have one width whatever the padded width of the batch they came from
-RECORD_BYTES = 1248        # 29*3 f32 (348) + 29 u8 atom types + 29 i8 charges + 29*29 u8 bond orders (841) = 1247, padded to 16
+# The record layout is the header's (include/diffspectra_hip.h, DS_RECORD_BYTES and the DS_REC_* offsets): 29*3 f32 positions | 29 u8 atom types |
+# 29 i8 charges | 29*29 u8 bond orders | pad.  Records have one width whatever the padded width of the batch they came from.
+_K = abi.SAMPLING.consts
+RECORD_ATOMS, RECORD_BYTES = _K["DS_MAX_ATOMS"], _K["DS_RECORD_BYTES"]
+_POS, _TYPE, _FC, _BOND = (slice(_K["DS_REC_" + a], _K["DS_REC_" + b]) for a, b in (("POS", "TYPE"), ("TYPE", "FC"), ("FC", "BOND"), ("BOND", "BOND_END")))
 
 
 def pack_records_u8(pos, atom_type, fc, edge_type) -> torch.Tensor:
@@ -57,20 +62,20 @@ def pack_records_u8(pos, atom_type, fc, edge_type) -> torch.Tensor:
     e = torch.zeros(B, W, W, dtype=torch.uint8, device=dev)
     e[:, :N, :N] = edge_type.to(torch.uint8)
     rec = torch.zeros(B, RECORD_BYTES, dtype=torch.uint8, device=dev)
-    rec[:, :348] = p.reshape(B, W * 3).view(torch.uint8)            # (explicit widths: a rank without molecules packs B = 0 rows)
-    rec[:, 348:377] = a
-    rec[:, 377:406] = c.view(torch.uint8)
-    rec[:, 406:1247] = e.reshape(B, W * W)
+    rec[:, _POS] = p.reshape(B, W * 3).view(torch.uint8)            # (explicit widths: a rank without molecules packs B = 0 rows)
+    rec[:, _TYPE] = a
+    rec[:, _FC] = c.view(torch.uint8)
+    rec[:, _BOND] = e.reshape(B, W * W)
     return rec
 
 
 def unpack_records_u8(rec: torch.Tensor):
     """→ ``(pos [M,29,3] f32, atom_type [M,29] i64, fc [M,29] i64, edge_type [M,29,29] f32)``."""
     M = rec.shape[0]
-    pos = rec[:, :348].contiguous().view(torch.float32).reshape(M, RECORD_ATOMS, 3)
-    atom = rec[:, 348:377].long()
-    fc = rec[:, 377:406].contiguous().view(torch.int8).long()
-    et = rec[:, 406:1247].reshape(M, RECORD_ATOMS, RECORD_ATOMS).float()
+    pos = rec[:, _POS].contiguous().view(torch.float32).reshape(M, RECORD_ATOMS, 3)
+    atom = rec[:, _TYPE].long()
+    fc = rec[:, _FC].contiguous().view(torch.int8).long()
+    et = rec[:, _BOND].reshape(M, RECORD_ATOMS, RECORD_ATOMS).float()
     return pos, atom, fc, et
 
 

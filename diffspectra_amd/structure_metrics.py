@@ -91,6 +91,16 @@ def records_from_graph(atom_type: torch.Tensor, pos: torch.Tensor, fc: torch.Ten
     return shard.pack_records_u8(pos_d, at_d, fc_d, et_d)[row[ids]].contiguous()
 
 
+def _pair_call(name, engine, ref, prb, ref_index, *scalars):
+    """``engine.<name>`` (the module's function without an engine) on ``(records, n_atoms)`` pairs, ground truth first: the counts and
+    ``ref_index`` are converted to the device and dtype the binding wants, the records are passed as they are."""
+    from . import engine as E
+    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
+    i32 = lambda t: torch.as_tensor(t).to(device=prb_rec.device, dtype=torch.int32).contiguous()
+    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=prb_rec.device, dtype=torch.int64).contiguous()
+    return getattr(engine if engine is not None else E, name)(prb_rec, i32(prb_n), ref_rec, i32(ref_n), idx, *scalars)
+
+
 def hungarian_rmsd_batch(ref, prb, max_distance: float = 5.0, min_atoms: int = 3, engine=None, ref_index=None, raw: bool = False):
     """``hungarian_rmsd_batch`` of ``eval_sampled_mols/rmsd.py:232-273`` on record tensors.  ``ref`` and ``prb`` are ``(records [*, 1248] u8,
     n_atoms [*])`` pairs on the GPU (ground truth first, as in the reference's signature); ``ref_index [P]`` names the ground-truth row of
@@ -99,12 +109,7 @@ def hungarian_rmsd_batch(ref, prb, max_distance: float = 5.0, min_atoms: int = 3
     Returns ``(rmsd_list, success_rate, mean_rmsd, mean_atom_type_accuracy)``: ``None`` for an invalid pair, the success rate over all
     pairs, the means over the valid pairs (``None`` without any).  ``raw=True`` returns the ``PairMetrics`` of device tensors instead and
     does not synchronise."""
-    from . import engine as E
-    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
-    i32 = lambda t: torch.as_tensor(t).to(device=prb_rec.device, dtype=torch.int32).contiguous()
-    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=prb_rec.device, dtype=torch.int64).contiguous()
-    fn = engine.match_records if engine is not None else E.match_records
-    out = PairMetrics(*fn(prb_rec, i32(prb_n), ref_rec, i32(ref_n), idx, max_distance, min_atoms))
+    out = PairMetrics(*_pair_call("match_records", engine, ref, prb, ref_index, max_distance, min_atoms))
     if raw:
         return out
     rmsd = out.rmsd.cpu()
@@ -161,12 +166,7 @@ def graph_identity_batch(ref, prb, ref_index=None, max_nodes: int = 4096, engine
     identity) of every generated molecule with its ground truth, independent of the conformation.  ``ref`` and ``prb`` are ``(records
     [*, 1248] u8, n_atoms [*])`` pairs on the GPU, ground truth first as in ``hungarian_rmsd_batch``; ``ref_index [P]`` names the ground-truth
     row of every generated molecule (``None``: row p).  Device tensors, no synchronisation."""
-    from . import engine as E
-    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
-    i32 = lambda t: torch.as_tensor(t).to(device=prb_rec.device, dtype=torch.int32).contiguous()
-    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=prb_rec.device, dtype=torch.int64).contiguous()
-    fn = engine.graph_identity_records if engine is not None else E.graph_identity_records
-    return GraphIdentity(*fn(prb_rec, i32(prb_n), ref_rec, i32(ref_n), idx, max_nodes))
+    return GraphIdentity(*_pair_call("graph_identity_records", engine, ref, prb, ref_index, max_nodes))
 
 
 def topk_identity(verdict: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:
@@ -236,12 +236,7 @@ def mces_batch(ref, prb, ref_index=None, drop_h: bool = True, max_nodes: int = 1
     RDKit's aromatic 1.5, so two Kekule drawings of one substituted ring are a non-zero distance apart (o-xylene: 2); and parity with the
     ``myopic_mces`` package itself is unpinned, because it cannot be run here.  Arguments as ``graph_identity_batch``.  Device tensors, no
     synchronisation."""
-    from . import engine as E
-    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
-    i32 = lambda t: torch.as_tensor(t).to(device=prb_rec.device, dtype=torch.int32).contiguous()
-    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=prb_rec.device, dtype=torch.int64).contiguous()
-    fn = engine.mces_records if engine is not None else E.mces_records
-    return Mces(*fn(prb_rec, i32(prb_n), ref_rec, i32(ref_n), idx, drop_h, max_nodes))
+    return Mces(*_pair_call("mces_records", engine, ref, prb, ref_index, drop_h, max_nodes))
 
 
 def topk_mces(dist: torch.Tensor, status: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:

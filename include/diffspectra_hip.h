@@ -112,6 +112,31 @@ enum ds_global_slot {
 
 #define DS_MAX_ATOMS 29               /* QM9 (data.max_node, configs/diffspectra_qm9s.py:28) */
 #define DS_RECORD_BYTES 1248          /* one result record (shard.pack_records_u8): 29*3 f32 positions | 29 u8 types | 29 i8 charges | 29*29 u8 bond orders | pad */
+#define DS_REC_POS 0                                              /* byte offsets of a record's fields; DS_REC_BOND_END is where the pad starts */
+#define DS_REC_TYPE (DS_MAX_ATOMS * 12)
+#define DS_REC_FC (DS_REC_TYPE + DS_MAX_ATOMS)
+#define DS_REC_BOND (DS_REC_FC + DS_MAX_ATOMS)
+#define DS_REC_BOND_END (DS_REC_BOND + DS_MAX_ATOMS * DS_MAX_ATOMS)
+#ifdef __cplusplus
+static_assert(DS_REC_BOND_END <= DS_RECORD_BYTES && DS_RECORD_BYTES % 4 == 0, "a record holds its fields and is a whole number of dwords");
+static_assert((DS_REC_BOND_END + 3) / 4 * 4 <= DS_RECORD_BYTES, "the dwords that cover the bond block stay inside the record");
+#endif
+
+/* Record pairs: the contract that ds_match_records, ds_graph_identity_records and ds_mces_records share (ds_graph_hash_records takes the
+ * single-table part of it: one record table, n, alignment, P).
+ *   Records   prb_rec [P] / ref_rec [M]: DS_RECORD_BYTES bytes each, fields at the DS_REC_* offsets above - fp32 positions [29][3], atom type
+ *             bytes in decoder order H, C, N, O, F, formal-charge bytes (i8), the bond-order matrix [29][29] u8, pad.  Both tables must be
+ *             4-byte aligned (records are read as dwords and hold fp32 positions).
+ *   Counts    prb_n [P], ref_n [M]: atoms of every molecule, clamped to 0..29.
+ *   Bonds     of an unordered atom pair i < j the byte at row i, column j decides (the upper triangle); the diagonal is no pair.
+ *   Pairing   pair p compares prb_rec[p] with ref_rec[ref_index[p]], or with ref_rec[p] when ref_index is NULL (identity pairing, which needs
+ *             M >= P).  A row outside [0, M) makes the pair INVALID: neither record is read, and every output of the pair has its stated
+ *             invalid value.  M = 0 with a ref_index is therefore allowed (ref_rec / ref_n may then be NULL).
+ *   P = 0     launches nothing and returns DS_OK, whatever the pointers.
+ *   DS_ERR_ARG  checked in this order: the entry point's own scalars (each section names them) together with P < 0, M < 0, P > 2^31 - 1;
+ *             then, for P > 0: a NULL prb_rec, prb_n or output; with M > 0 a NULL ref_rec or ref_n; a NULL ref_index with M < P; a table
+ *             that is not 4-byte aligned.
+ *   One wave per pair, no atomics: a pair's outputs do not depend on the batch. */
 
 typedef struct ds_weights {
   const float* base;                 /* device: packed weights */
@@ -268,7 +293,7 @@ int ds_check_stability(const ds_layout* L, const float* pos, const int32_t* atom
                        int32_t* nr_stable, int32_t* mol_stable, void* stream);
 
 /* Structure metric of (generated, ground-truth) molecule pairs, one wave per pair, fp64 (eval_sampled_mols/rmsd.py:12-73,106-128,153-227
- * without RDKit): both molecules are DS_RECORD_BYTES records in the layout of shard.pack_records_u8, atom types in decoder order H, C, N, O, F.
+ * without RDKit).  Records, counts, bonds, pairing and the argument check are those of "record pairs" above; NaN max_distance is DS_ERR_ARG.
  *   1. each side keeps its largest connected fragment (a bond is an order > 0, read from the upper triangle of the record's bond matrix;
  *      among equally large fragments the one that holds the lowest atom index - RDKit's fragment order under Python's max; fragment atoms
  *      stay in ascending original order) and is centred on that fragment's centroid; a non-finite coordinate in either fragment makes
@@ -280,7 +305,7 @@ int ds_check_stability(const ds_layout* L, const float* pos, const int32_t* atom
  *      det R < 0; aligned = centred_generated . R;
  *   5. second assignment on the aligned coordinates with cost entries above max_distance (inf allowed: no clipping) set to 1000; matches
  *      whose clipped cost is <= max_distance are kept; fewer than min_atoms (or none) kept -> invalid.
- * Outputs per pair p (ground-truth row ref_index[p], or p when ref_index is NULL; a row outside [0, M) makes the pair invalid):
+ * Outputs per pair p:
  *   rmsd      f64  sqrt(mean |aligned_p - centred_r|^2) over the kept map (spatial distance only); NaN if invalid
  *   n_matched i32  size of the kept map whenever step 5 was reached (0 otherwise), also for an invalid pair
  *   type_acc  f32  share of kept matches with equal atom type; 0 if invalid
@@ -289,14 +314,14 @@ int ds_check_stability(const ds_layout* L, const float* pos, const int32_t* atom
  *                  charge and bond order agrees under the map: the map is then an explicit graph isomorphism (a certified hit; 0 proves
  *                  nothing - a correct graph in another conformation can miss - so hit@K from it is a LOWER bound)
  *   map [P,29] i32 ground-truth atom of every generated atom (original indices), -1 where unmatched / invalid
- * prb_n [P], ref_n [M]: atom counts (clamped to 0..29).  P = 0 launches nothing.  (bond_acc / exact are build extensions.) */
+ * (bond_acc / exact are build extensions.) */
 int ds_match_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
                      const int64_t* ref_index, float max_distance, int32_t min_atoms, double* rmsd, int32_t* n_matched,
                      float* type_acc, float* bond_acc, uint8_t* exact, int32_t* map, void* stream);
 
 /* Molecular-graph identity of (generated, ground-truth) pairs, one wave per pair, integers only: is there a bijection of the atoms that
- * preserves the decoder atom type, the formal-charge byte and the bond-order byte of every atom pair?  Records, ref_index and the clamping
- * of n are those of ds_match_records (bond bytes from the upper triangle of the record's matrix; the diagonal is no pair); coordinates are
+ * preserves the decoder atom type, the formal-charge byte and the bond-order byte of every atom pair?  Records, counts, bonds, pairing and the
+ * argument check are those of "record pairs" above; coordinates are
  * never read, so the answer does not depend on the conformation.  Whole molecules are compared, disconnected pieces included; unequal atom
  * counts are different; two 0-atom molecules are identical with an empty map.
  *   This is identity of the CONSTITUTION.  It is not InChIKey identity, which the reference compares (compute_metrics.py:222-230): there is
@@ -314,7 +339,7 @@ int ds_match_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, co
  *   nodes  i32  search nodes used (0 when refinement alone decides)
  *   map [P,29] i32  ground-truth atom of every generated atom when verdict = DS_GRAPH_IDENTICAL, -1 everywhere otherwise
  * max_nodes outside [0, DS_GRAPH_MAX_NODES] is DS_ERR_ARG.  Every loop of the kernel is bounded (rounds <= n + 1, depth <= n, tries <=
- * max_nodes): a malformed record ends in a verdict.  P = 0 launches nothing.  No atomics; a pair's outputs do not depend on the batch. */
+ * max_nodes): a malformed record ends in a verdict. */
 #define DS_GRAPH_DIFFERENT 0
 #define DS_GRAPH_IDENTICAL 1
 #define DS_GRAPH_UNDECIDED 2
@@ -323,7 +348,8 @@ int ds_match_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, co
 int ds_graph_identity_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
                               const int64_t* ref_index, int32_t max_nodes, uint8_t* verdict, int32_t* nodes, int32_t* map, void* stream);
 
-/* Permutation-invariant 64-bit hash of the labelled graph of every record, one wave per molecule (n clamped to 0..29, bond bytes as above).
+/* Permutation-invariant 64-bit hash of the labelled graph of every record, one wave per molecule (record table, counts, bonds, alignment and P as in
+ * "record pairs" above).
  * All arithmetic is unsigned 64-bit with wrap-around.  With
  *   fmix(x):    x ^= x >> 30;  x *= 0xbf58476d1ce4e5b9;  x ^= x >> 27;  x *= 0x94d049bb133111eb;  x ^= x >> 31
  *   mix(a, b) = fmix(a + 0x9e3779b97f4a7c15 * (b + 1))
@@ -336,8 +362,8 @@ int ds_graph_hash_records(const uint8_t* rec, const int32_t* n, int64_t P, uint6
 
 /* Exact MCES (maximum common edge subgraph) distance of (generated, ground-truth) pairs, one wave per pair, integers only: how far a wrong
  * molecule is from the right one as a labelled graph.  Replaces the reference's "MCES (Average)" (compute_metrics.py:235-243, run_lib.py:149:
- * one myopic_mces ILP per pair through pulp, on SMILES made by RDKit).  Records, ref_index and the clamping of n (0..29) are those of
- * ds_graph_identity_records: bond bytes from the upper triangle, coordinates never read.  drop_h = 1 leaves out the atoms of decoder type 0
+ * one myopic_mces ILP per pair through pulp, on SMILES made by RDKit).  Records, counts, bonds, pairing and the argument check are those of
+ * "record pairs" above; coordinates are never read.  drop_h = 1 leaves out the atoms of decoder type 0
  * (hydrogen) and their bonds, as the reference's SMILES route does; drop_h = 0 keeps every atom.
  *   A bond's weight w is its bond-order byte, an integer.  The formal-charge byte is NOT compared (myopic_mces labels nodes by element only).
  *   A common subgraph is a partial injective map pi from atoms of A (generated) to atoms of B (ground truth) of the same type.
@@ -374,8 +400,7 @@ int ds_graph_hash_records(const uint8_t* rec, const int32_t* n, int64_t P, uint6
  *   nodes  i32  tries used
  *   map [P,29] i32  ground-truth atom of every generated atom in the best map (original indices), -1 where unmapped or dropped
  * max_nodes outside [0, DS_MCES_MAX_NODES] and drop_h outside {0, 1} are DS_ERR_ARG.  Every loop of the kernel is bounded (depth <= 29,
- * passes <= 2 max_nodes + 64): a malformed record ends in a verdict.  P = 0 launches nothing.  No atomics; a pair's outputs do not depend on
- * the batch. */
+ * passes <= 2 max_nodes + 64): a malformed record ends in a verdict. */
 #define DS_MCES_EXACT 0
 #define DS_MCES_UNDECIDED 2
 #define DS_MCES_INVALID 3

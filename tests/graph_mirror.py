@@ -125,6 +125,11 @@ def carbons(n, edges):
     return molecule([1] * n, edges)
 
 
+def k29():
+    """The complete graph on 29 carbons: every class of the refinement is all of the molecule."""
+    return carbons(29, [(i, j) for i in range(29) for j in range(i + 1, 29)])
+
+
 def saturated(mol):
     """Hydrogens (type 0) on every atom up to valence 4."""
     n = len(mol["type"])
@@ -164,21 +169,6 @@ def hard_pairs():
 def nonane():
     """A saturated C9H20 (2,2,4,4-tetramethylpentane: many equivalent hydrogens), 29 atoms."""
     return saturated(carbons(9, _path(0, 1, 2, 3, 4) + [(1, 5), (1, 6), (3, 7), (3, 8)]))
-
-
-def records(mols):
-    """(rec [len, 1248] u8, n [len] i32) of a list of molecule dicts, in the layout of ``shard.pack_records_u8`` (written here with numpy
-    because thousands of molecules go through it; tests/test_graph_identity_cpu.py compares it with the project's packer)."""
-    rec = np.zeros((len(mols), SM.RECORD_BYTES), np.uint8)
-    for k, m in enumerate(mols):
-        n = len(m["type"])
-        pos, bond = np.zeros((W, 3), np.float32), np.zeros((W, W), np.uint8)
-        pos[:n], bond[:n, :n] = m["pos"], np.asarray(m["bond"]).astype(np.uint8)
-        rec[k, :348] = pos.reshape(-1).view(np.uint8)
-        rec[k, 348:348 + n] = np.asarray(m["type"]).astype(np.uint8)
-        rec[k, 377:377 + n] = np.asarray(m["fc"]).astype(np.int8).view(np.uint8)
-        rec[k, 406:406 + W * W] = bond.reshape(-1)
-    return rec, np.array([len(m["type"]) for m in mols], np.int32)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the seeded pair set

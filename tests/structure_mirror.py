@@ -14,15 +14,33 @@ from scipy.optimize import linear_sum_assignment
 
 W = 29                       # atoms per record (DS_MAX_ATOMS)
 RECORD_BYTES = 1248
+# byte offsets of a record's fields and the end of the bond block: plain numbers on purpose - this mirror is a yardstick of the header's
+# DS_REC_* and of shard.pack_records_u8 (tests/test_record_pairs_cpu.py compares the three), so it does not import them
+POS, TYPE, FC, BOND, BOND_END = 0, 348, 377, 406, 1247
 
 
 def mol_from_record(rec, n):
     """Record row (uint8 [1248], layout of ``shard.pack_records_u8``) -> molecule dict of its first ``n`` atoms."""
     rec = np.ascontiguousarray(np.asarray(rec, dtype=np.uint8))
     n = int(min(max(int(n), 0), W))
-    pos = rec[:348].view(np.float32).reshape(W, 3)[:n].astype(np.float64)
-    return dict(pos=pos, type=rec[348:377][:n].astype(np.int64), fc=rec[377:406].view(np.int8)[:n].astype(np.int64),
-                bond=rec[406:1247].reshape(W, W)[:n, :n].astype(np.int64))
+    pos = rec[POS:TYPE].view(np.float32).reshape(W, 3)[:n].astype(np.float64)
+    return dict(pos=pos, type=rec[TYPE:FC][:n].astype(np.int64), fc=rec[FC:BOND].view(np.int8)[:n].astype(np.int64),
+                bond=rec[BOND:BOND_END].reshape(W, W)[:n, :n].astype(np.int64))
+
+
+def records(mols):
+    """(rec [len, 1248] u8, n [len] i32) of a list of molecule dicts, in the layout of ``shard.pack_records_u8`` (written here with numpy
+    because thousands of molecules go through it; tests/test_graph_identity_cpu.py compares it with the project's packer)."""
+    rec = np.zeros((len(mols), RECORD_BYTES), np.uint8)
+    for k, m in enumerate(mols):
+        n = len(m["type"])
+        pos, bond = np.zeros((W, 3), np.float32), np.zeros((W, W), np.uint8)
+        pos[:n], bond[:n, :n] = m["pos"], np.asarray(m["bond"]).astype(np.uint8)
+        rec[k, POS:TYPE] = pos.reshape(-1).view(np.uint8)
+        rec[k, TYPE:TYPE + n] = np.asarray(m["type"]).astype(np.uint8)
+        rec[k, FC:FC + n] = np.asarray(m["fc"]).astype(np.int8).view(np.uint8)
+        rec[k, BOND:BOND_END] = bond.reshape(-1)
+    return rec, np.array([len(m["type"]) for m in mols], np.int32)
 
 
 def record_from_mol(pos, atom_type, fc, bond):

@@ -134,7 +134,7 @@ def test_seeded_pairs_discriminate_and_records_match_the_packer():
     for k in (1, 3):                                                  # the bond switch and the type swap leave both answers well populated
         share = same[kind == k].mean()
         assert 0.05 <= share <= 0.95, (k, share)
-    rec, n = GM.records(ref[:40] + prb[:40])
+    rec, n = SM.records(ref[:40] + prb[:40])
     for k, m in enumerate(ref[:40] + prb[:40]):
         assert np.array_equal(rec[k], SM.record_from_mol(m["pos"], m["type"], m["fc"], m["bond"])) and n[k] == len(m["type"])
         back = SM.mol_from_record(rec[k], n[k])

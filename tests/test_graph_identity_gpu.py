@@ -1,6 +1,8 @@
 """GPU: ``ds_graph_identity_records`` and ``ds_graph_hash_records`` (one wave per pair / molecule) against the plain-Python mirror of
 tests/graph_mirror.py - every verdict equal, every returned map checked here to be an isomorphism, no tolerance anywhere - plus the hard
 pairs, the edges of the shape, conformation independence, batch independence, the classes and the evaluation driver end to end."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -8,25 +10,11 @@ import torch
 from diffspectra_amd import engine as E, shard
 from diffspectra_amd.structure_metrics import GraphIdentity, graph_classes, graph_identity_batch, topk_identity
 from tests import graph_mirror as GM, structure_mirror as SM
+from tests.helpers import run_records, to_dev
 
 pytestmark = pytest.mark.gpu
 
-
-def _t(dev, a, dt):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
-
-
-def _run(dev, ref_rec, ref_n, prb_rec, prb_n, ref_index=None, max_nodes=4096):
-    idx = None if ref_index is None else _t(dev, ref_index, torch.int64)
-    out = E.graph_identity_records(_t(dev, prb_rec, torch.uint8), _t(dev, prb_n, torch.int32), _t(dev, ref_rec, torch.uint8),
-                                   _t(dev, ref_n, torch.int32), idx, max_nodes)
-    torch.cuda.synchronize()
-    return GraphIdentity(*(o.cpu().numpy() for o in out))
-
-
-def _run_mols(dev, ref, prb, **kw):
-    (rr, rn), (pr, pn) = GM.records(ref), GM.records(prb)
-    return _run(dev, rr, rn, pr, pn, **kw)
+_run = functools.partial(run_records, E.graph_identity_records, GraphIdentity)       # (dev, ref, prb, ref_index=None, **scalars) -> GraphIdentity of numpy arrays
 
 
 def _check_maps(got, ref, prb, what=""):
@@ -46,7 +34,7 @@ def test_parity_on_seeded_pairs(gpu_device):
     assert len(ref) == 2000 and want[kind == 0].all()
     for k in (1, 3):                                                  # the set discriminates: both answers occur among the bond switches and type swaps
         assert 0.05 <= want[kind == k].mean() <= 0.95, (k, want[kind == k].mean())
-    got = _run_mols(gpu_device, ref, prb)
+    got = _run(gpu_device, ref, prb)
     print(f"[graph] 2000 pairs: {int(want.sum())} identical; nodes mean {got.nodes.mean():.3f} max {got.nodes.max()}; "
           f"disagreements {int((got.verdict != want).sum())}, undecided {int((got.verdict == 2).sum())}")
     assert (got.verdict != 2).all(), np.nonzero(got.verdict == 2)[0][:10]
@@ -55,33 +43,29 @@ def test_parity_on_seeded_pairs(gpu_device):
     assert (got.nodes >= 0).all() and (got.nodes <= 4096).all()
 
 
-def _k29():
-    return GM.carbons(29, [(i, j) for i in range(29) for j in range(i + 1, 29)])
-
-
 def test_hard_pairs(gpu_device):
     rng = np.random.default_rng(8)
     hard = GM.hard_pairs()
     cross_prb, cross_ref = [GM.permuted(a, rng) for _, a, b in hard] + [GM.permuted(b, rng) for _, a, b in hard], [b for _, a, b in hard] + [a for _, a, b in hard]
-    got = _run_mols(gpu_device, cross_ref, cross_prb)
+    got = _run(gpu_device, cross_ref, cross_prb)
     print(f"[graph] hard cross pairs: nodes {got.nodes.tolist()}")
     assert got.verdict.tolist() == [0] * len(cross_prb)              # proven different at the default budget
     _check_maps(got, cross_ref, cross_prb, "cross")
-    plain = _run_mols(gpu_device, cross_ref, cross_prb, max_nodes=0)  # refinement alone cannot separate them: the budget path, no fault
+    plain = _run(gpu_device, cross_ref, cross_prb, max_nodes=0)  # refinement alone cannot separate them: the budget path, no fault
     assert plain.verdict.tolist() == [2] * len(cross_prb) and (plain.nodes == 0).all() and (plain.map == -1).all()
-    one = _run_mols(gpu_device, cross_ref, cross_prb, max_nodes=1)    # a budget is a cap: never more nodes than allowed, never a wrong answer
+    one = _run(gpu_device, cross_ref, cross_prb, max_nodes=1)    # a budget is a cap: never more nodes than allowed, never a wrong answer
     assert (one.nodes <= 1).all() and set(one.verdict.tolist()) <= {0, 2}
     # every molecule against a permuted copy of itself; the deepest stacks; a saturated C9H20
-    own = [m for _, a, b in hard for m in (a, b)] + [_k29(), GM.carbons(29, []), GM.nonane()]
+    own = [m for _, a, b in hard for m in (a, b)] + [GM.k29(), GM.carbons(29, []), GM.nonane()]
     moved = [GM.permuted(m, rng) for m in own]
-    got = _run_mols(gpu_device, own, moved)
+    got = _run(gpu_device, own, moved)
     print(f"[graph] self pairs: nodes {got.nodes.tolist()}")
     assert got.verdict.tolist() == [1] * len(own)
     _check_maps(got, own, moved, "self")
     assert got.nodes[-3] >= 1 and got.nodes[-2] >= 1                  # K29 and the bondless molecule cannot be decided without the search
-    tight = _run_mols(gpu_device, own[-3:], moved[-3:], max_nodes=int(got.nodes[-3:].max()))
+    tight = _run(gpu_device, own[-3:], moved[-3:], max_nodes=int(got.nodes[-3:].max()))
     assert tight.verdict.tolist() == [1, 1, 1]                        # exactly the nodes a search used are enough for it
-    short = _run_mols(gpu_device, own[-3:-1], moved[-3:-1], max_nodes=int(got.nodes[-3:-1].min()) - 1)
+    short = _run(gpu_device, own[-3:-1], moved[-3:-1], max_nodes=int(got.nodes[-3:-1].min()) - 1)
     assert short.verdict.tolist() == [2, 2] and (short.map == -1).all()
 
 
@@ -105,31 +89,31 @@ def test_edges_of_the_shape(gpu_device):
              (GM.permuted(loud, rng), loud, 1), (GM.permuted(loud, rng), big, 0), (GM.permuted(big, rng), loud, 0)]
     prb_m, ref_m, want = [c[0] for c in cases], [c[1] for c in cases], [c[2] for c in cases]
     assert [int(GM.same_graph(a, b)) for a, b in zip(prb_m, ref_m)] == want
-    got = _run_mols(gpu_device, ref_m, prb_m)
+    got = _run(gpu_device, ref_m, prb_m)
     assert got.verdict.tolist() == want
     _check_maps(got, ref_m, prb_m, "edge")
     assert got.nodes[0] == 0 and (got.map[0] == -1).all() and got.map[1].tolist() == [0] + [-1] * 28
     # n is clamped to 0..29, as in ds_match_records: a count of 40 reads 29 atoms, a negative one none
-    (rr, rn), (pr, pn) = GM.records([big, empty]), GM.records([GM.permuted(big, rng), empty])
-    clamped = _run(gpu_device, rr, np.array([40, -3], np.int32), pr, np.array([29, 0], np.int32))
+    (rr, rn), (pr, pn) = SM.records([big, empty]), SM.records([GM.permuted(big, rng), empty])
+    clamped = _run(gpu_device, (rr, np.array([40, -3], np.int32)), (pr, np.array([29, 0], np.int32)))
     assert clamped.verdict.tolist() == [1, 1]
     # the lower triangle and the diagonal of a record's bond matrix are not read
     noisy = pr.copy()
     m = noisy[0, 406:406 + 841].reshape(29, 29)
     m[np.tril_indices(29)] = 77
-    assert _run(gpu_device, rr, rn, noisy, pn).verdict.tolist() == [1, 1]
+    assert _run(gpu_device, (rr, rn), (noisy, pn)).verdict.tolist() == [1, 1]
     # ref_index: several candidates share a ground-truth row; a row outside the table is verdict 3 and nothing else changes
     S, K = 20, 4
     rows = np.repeat(np.arange(S), K)
     cand = [prb[s] if k == 0 else (GM.permuted(ref[s], rng) if k == 2 else prb[(s + 7 * k) % 100]) for s in range(S) for k in range(K)]
     want = np.array([int(GM.same_graph(c, ref[r])) for c, r in zip(cand, rows)], np.uint8)
-    (rr, rn), (pr, pn) = GM.records(ref[:S]), GM.records(cand)
-    got = _run(gpu_device, rr, rn, pr, pn, ref_index=rows)
+    (rr, rn), (pr, pn) = SM.records(ref[:S]), SM.records(cand)
+    got = _run(gpu_device, (rr, rn), (pr, pn), ref_index=rows)
     assert np.array_equal(got.verdict, want) and want.reshape(S, K)[:, 2].all()
     _check_maps(got, [ref[r] for r in rows], cand, "ref_index")
     bad_rows = rows.copy()
     bad_rows[[3, 50]] = [S, -1]
-    bad = _run(gpu_device, rr, rn, pr, pn, ref_index=bad_rows)
+    bad = _run(gpu_device, (rr, rn), (pr, pn), ref_index=bad_rows)
     assert bad.verdict[[3, 50]].tolist() == [3, 3] and (bad.map[[3, 50]] == -1).all() and (bad.nodes[[3, 50]] == 0).all()
     keep = np.ones(S * K, bool)
     keep[[3, 50]] = False
@@ -137,10 +121,10 @@ def test_edges_of_the_shape(gpu_device):
     top = topk_identity(torch.as_tensor(got.verdict), K)
     assert top["hit"].tolist() == want.reshape(S, K).any(1).tolist() and int(top["undecided"]) == 0
     # P = 0
-    none = _run(gpu_device, rr, rn, pr[:0], pn[:0])
+    none = _run(gpu_device, (rr, rn), (pr[:0], pn[:0]))
     assert none.verdict.shape == (0,) and none.nodes.shape == (0,) and none.map.shape == (0, SM.W)
-    assert _run(gpu_device, rr[:0], rn[:0], pr[:0], pn[:0]).verdict.shape == (0,)
-    assert E.graph_hash_records(_t(gpu_device, pr[:0], torch.uint8), _t(gpu_device, pn[:0], torch.int32)).shape == (0,)
+    assert _run(gpu_device, (rr[:0], rn[:0]), (pr[:0], pn[:0])).verdict.shape == (0,)
+    assert E.graph_hash_records(to_dev(gpu_device, pr[:0], torch.uint8), to_dev(gpu_device, pn[:0], torch.int32)).shape == (0,)
 
 
 @pytest.fixture(scope="module")
@@ -156,16 +140,16 @@ def test_conformation_independence(gpu_device, synthetic):
     count = 200
     truth = [SM.mol_from_record(ref_rec[p], ref_n[p]) for p in range(count)]
     moved = [GM.permuted(m, rng) for m in truth]
-    pr, pn = GM.records(moved)
-    dev = lambda a, dt: _t(gpu_device, a, dt)
+    pr, pn = SM.records(moved)
+    dev = lambda a, dt: to_dev(gpu_device, a, dt)
     exact = E.match_records(dev(pr, torch.uint8), dev(pn, torch.int32), dev(ref_rec[:count], torch.uint8), dev(ref_n[:count], torch.int32))[4].cpu().numpy()
-    got = _run(gpu_device, ref_rec[:count], ref_n[:count], pr, pn)
+    got = _run(gpu_device, (ref_rec[:count], ref_n[:count]), (pr, pn))
     print(f"[graph] {count} re-embedded ground truths: ds_match_records certifies {int(exact.sum())}, ds_graph_identity_records {int((got.verdict == 1).sum())}")
     assert (exact == 0).any() and (got.verdict == 1).all()
     _check_maps(got, truth, moved, "re-embedded")
     # whatever the geometric match certifies on the unmodified pairs is identical here too
     exact = E.match_records(dev(prb_rec, torch.uint8), dev(prb_n, torch.int32), dev(ref_rec, torch.uint8), dev(ref_n, torch.int32))[4].cpu().numpy()
-    got = _run(gpu_device, ref_rec, ref_n, prb_rec, prb_n)
+    got = _run(gpu_device, (ref_rec, ref_n), (prb_rec, prb_n))
     assert exact.sum() > 0 and (got.verdict[exact == 1] == 1).all() and (got.verdict <= 1).all()
     batch = graph_identity_batch((dev(ref_rec, torch.uint8), dev(ref_n, torch.int32)), (dev(prb_rec, torch.uint8), torch.as_tensor(prb_n)))
     assert np.array_equal(batch.verdict.cpu().numpy(), got.verdict) and np.array_equal(batch.identical.cpu().numpy(), got.verdict == 1)
@@ -175,20 +159,20 @@ def test_batch_independence(gpu_device):
     """A pair's verdict, nodes and map are bit-identical alone, first, last and in the middle of 10 000."""
     ref, prb, _ = GM.seeded_pairs()
     hard = GM.hard_pairs()
-    probes = [(prb[5], ref[5]), (prb[1001], ref[1001]), (hard[7][1], hard[7][2]), (GM.permuted(_k29(), np.random.default_rng(11)), _k29())]
-    (rr, rn), (pr, pn) = GM.records(ref), GM.records(prb)
+    probes = [(prb[5], ref[5]), (prb[1001], ref[1001]), (hard[7][1], hard[7][2]), (GM.permuted(GM.k29(), np.random.default_rng(11)), GM.k29())]
+    (rr, rn), (pr, pn) = SM.records(ref), SM.records(prb)
     rep = np.arange(10000) % 2000
     R, N, Pr, Pn = rr[rep], rn[rep], pr[rep], pn[rep]
     places = [0, 4321, 9999]
     for a, b in probes:
-        (r1, n1), (p1, m1) = GM.records([b]), GM.records([a])
-        alone = _run(gpu_device, r1, n1, p1, m1)
+        (r1, n1), (p1, m1) = SM.records([b]), SM.records([a])
+        alone = _run(gpu_device, (r1, n1), (p1, m1))
         R[places], N[places], Pr[places], Pn[places] = r1[0], n1[0], p1[0], m1[0]
-        full = _run(gpu_device, R, N, Pr, Pn)
+        full = _run(gpu_device, (R, N), (Pr, Pn))
         for x, y in zip(alone, full):
             for where in places:
                 assert x[0].tobytes() == y[where].tobytes(), where
-    assert len({int(_run(gpu_device, *GM.records([b]), *GM.records([a])).verdict[0]) for a, b in probes}) == 2     # both answers were probed
+    assert len({int(_run(gpu_device, SM.records([b]), SM.records([a])).verdict[0]) for a, b in probes}) == 2     # both answers were probed
 
 
 def test_hash_and_classes(gpu_device):
@@ -199,11 +183,11 @@ def test_hash_and_classes(gpu_device):
     mols += [GM.permuted(mols[k], rng) for k in planted]             # permuted duplicates ...
     for _, a, b in GM.hard_pairs():                                   # ... and graphs that collide in the hash without being equal
         mols += [a, GM.permuted(b, rng), GM.permuted(a, rng)]
-    mols += [GM.molecule([], []), GM.molecule([], []), _k29(), GM.permuted(_k29(), rng)]
+    mols += [GM.molecule([], []), GM.molecule([], []), GM.k29(), GM.permuted(GM.k29(), rng)]
     order = rng.permutation(len(mols))
     mols = [mols[k] for k in order]
-    rec, n = GM.records(mols)
-    got = E.graph_hash_records(_t(gpu_device, rec, torch.uint8), _t(gpu_device, n, torch.int32))
+    rec, n = SM.records(mols)
+    got = E.graph_hash_records(to_dev(gpu_device, rec, torch.uint8), to_dev(gpu_device, n, torch.int32))
     assert got.dtype == torch.int64 and got.shape == (len(mols),)
     got = [int(v) & GM.MASK for v in got.cpu().tolist()]
     want = [GM.graph_hash(m) for m in mols]
@@ -219,10 +203,10 @@ def test_hash_and_classes(gpu_device):
     for k, h in enumerate(want):
         buckets.setdefault(h, set()).add(want_class[k])
     assert max(len(v) for v in buckets.values()) >= 2                 # buckets with several classes do occur
-    classes = graph_classes(_t(gpu_device, rec, torch.uint8), torch.as_tensor(n))
+    classes = graph_classes(to_dev(gpu_device, rec, torch.uint8), torch.as_tensor(n))
     assert classes.dtype == torch.int64 and classes.tolist() == want_class
     assert classes.unique().numel() == len(reps) < len(mols)
-    assert graph_classes(_t(gpu_device, rec[:0], torch.uint8), torch.as_tensor(n[:0])).shape == (0,)
+    assert graph_classes(to_dev(gpu_device, rec[:0], torch.uint8), torch.as_tensor(n[:0])).shape == (0,)
 
 
 def test_evaluate_reports_graph_identity(gpu_device, tmp_path, monkeypatch):
@@ -256,7 +240,7 @@ def test_evaluate_reports_graph_identity(gpu_device, tmp_path, monkeypatch):
 
     def gather_and_plant(rec, n_atoms):
         by_slot = gather(rec, n_atoms)
-        by_slot[planted] = torch.as_tensor(GM.records([moved])[0][0]).to(by_slot.device)
+        by_slot[planted] = torch.as_tensor(SM.records([moved])[0][0]).to(by_slot.device)
         return by_slot
     monkeypatch.setattr(shard, "gather_by_slot", gather_and_plant)
     res = EV.diffspectra_evaluate(cfg, str(tmp_path), table, structure_metrics=True)

@@ -1,6 +1,8 @@
 """GPU: ``ds_mces_records`` (one wave per pair, branch-and-bound) against the integer program of tests/mces_mirror.py - every distance
 equal, every returned map rescored here from the records, no tolerance anywhere - plus the budget, the edges of the shape, batch
 independence, the agreement with ``ds_graph_identity_records`` and the evaluation driver end to end."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -8,28 +10,14 @@ import torch
 from diffspectra_amd import engine as E, shard
 from diffspectra_amd.structure_metrics import Mces, mces_batch, topk_mces
 from tests import graph_mirror as GM, mces_mirror as MM, structure_mirror as SM
+from tests.helpers import run_records, to_dev
 
 pytestmark = pytest.mark.gpu
 
+_run = functools.partial(run_records, E.mces_records, Mces)       # (dev, ref, prb, ref_index=None, **scalars) -> Mces of numpy arrays
+
 DEFAULT_NODES = 1 << 18
 LARGE = dict(count=40, seed=20261102, heavy=(10, 12))
-
-
-def _t(dev, a, dt):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
-
-
-def _run(dev, ref_rec, ref_n, prb_rec, prb_n, ref_index=None, drop_h=True, max_nodes=DEFAULT_NODES):
-    idx = None if ref_index is None else _t(dev, ref_index, torch.int64)
-    out = E.mces_records(_t(dev, prb_rec, torch.uint8), _t(dev, prb_n, torch.int32), _t(dev, ref_rec, torch.uint8), _t(dev, ref_n, torch.int32),
-                         idx, drop_h, max_nodes)
-    torch.cuda.synchronize()
-    return Mces(*(o.cpu().numpy() for o in out))
-
-
-def _run_mols(dev, ref, prb, **kw):
-    (rr, rn), (pr, pn) = GM.records(ref), GM.records(prb)
-    return _run(dev, rr, rn, pr, pn, **kw)
 
 
 def _check_maps(got, ref, prb, drop_h=True, what=""):
@@ -50,7 +38,7 @@ def test_parity_on_seeded_pairs(gpu_device, seeded):
     ref, prb, kind, want = seeded
     assert len(ref) == 600 and max(int((m["type"] != 0).sum()) for m in ref + prb) <= 9 and (want[kind == 0] == 0).all()
     assert (want > 0).sum() > 300                                       # the set discriminates
-    got = _run_mols(gpu_device, ref, prb)
+    got = _run(gpu_device, ref, prb)
     print(f"[mces] 600 pairs, drop_h = 1: dist mean {want.mean():.3f}; nodes mean {got.nodes.mean():.2f} max {got.nodes.max()}; "
           f"disagreements {int((got.dist != want).sum())}, undecided {int((got.status == 2).sum())}")
     assert (got.status == 0).all(), np.nonzero(got.status != 0)[0][:10]
@@ -62,7 +50,7 @@ def test_parity_on_seeded_pairs(gpu_device, seeded):
     assert len(few) == 100
     ref_h, prb_h = [ref[p] for p in few], [prb[p] for p in few]
     want_h = np.array([MM.mces_milp(a, b, False) for a, b in zip(prb_h, ref_h)])
-    got_h = _run_mols(gpu_device, ref_h, prb_h, drop_h=False)
+    got_h = _run(gpu_device, ref_h, prb_h, drop_h=False)
     print(f"[mces] 100 pairs, drop_h = 0: nodes mean {got_h.nodes.mean():.2f} max {got_h.nodes.max()}")
     assert (got_h.status == 0).all() and np.array_equal(got_h.dist, want_h) and (want_h != want[few]).any()
     _check_maps(got_h, ref_h, prb_h, False, "with hydrogens")
@@ -73,7 +61,7 @@ def test_larger_molecules(gpu_device):
     want = MM.seeded_distances(**LARGE)
     heavy = [int((m["type"] != 0).sum()) for m in ref]
     assert min(heavy) >= 10 and max(heavy) <= 12
-    got = _run_mols(gpu_device, ref, prb, max_nodes=E.MCES_MAX_NODES)
+    got = _run(gpu_device, ref, prb, max_nodes=E.MCES_MAX_NODES)
     print(f"[mces] 40 pairs of 10-12 heavy atoms: nodes mean {got.nodes.mean():.1f} max {got.nodes.max()}")
     assert (got.status == 0).all() and np.array_equal(got.dist, want), np.nonzero(got.dist != want)[0][:10]
     _check_maps(got, ref, prb, True, "large")
@@ -82,7 +70,7 @@ def test_larger_molecules(gpu_device):
 @pytest.mark.parametrize("budget", [0, 64])
 def test_budget(gpu_device, seeded, budget):
     ref, prb, _, want = seeded
-    got = _run_mols(gpu_device, ref, prb, max_nodes=budget)
+    got = _run(gpu_device, ref, prb, max_nodes=budget)
     undecided = got.status == 2
     print(f"[mces] budget {budget}: {int(undecided.sum())} of 600 undecided")
     assert set(got.status.tolist()) <= {0, 2}
@@ -93,18 +81,14 @@ def test_budget(gpu_device, seeded, budget):
     _check_maps(got, ref, prb, True, f"budget {budget}")                # dist is what the returned map achieves, decided or not
 
 
-def _k29():
-    return GM.carbons(29, [(i, j) for i in range(29) for j in range(i + 1, 29)])
-
-
 def test_edges_of_the_shape(gpu_device, seeded):
     rng = np.random.default_rng(31)
     ref, prb, _, want = seeded
     table = MM.hand_table()
     for drop_h in (True, False):
-        got = _run_mols(gpu_device, [b for _, a, b, _ in table], [a for _, a, b, _ in table], drop_h=drop_h)
+        got = _run(gpu_device, [b for _, a, b, _ in table], [a for _, a, b, _ in table], drop_h=drop_h)
         assert got.dist.tolist() == [d for *_, d in table] and (got.status == 0).all(), [(row[0], int(d)) for row, d in zip(table, got.dist) if d != row[3]]
-        back = _run_mols(gpu_device, [a for _, a, b, _ in table], [b for _, a, b, _ in table], drop_h=drop_h)
+        back = _run(gpu_device, [a for _, a, b, _ in table], [b for _, a, b, _ in table], drop_h=drop_h)
         assert back.dist.tolist() == got.dist.tolist()
         _check_maps(got, [b for _, a, b, _ in table], [a for _, a, b, _ in table], drop_h, "hand")
     empty = GM.molecule([], [])
@@ -114,7 +98,7 @@ def test_edges_of_the_shape(gpu_device, seeded):
     cases = [(empty, empty), (empty, ethanol), (ethanol, empty), (h4, h4), (h4, ethanol), (bondless, bondless_b), (bondless, ethanol), (ethanol, bondless)]
     prb_m, ref_m = [c[0] for c in cases], [c[1] for c in cases]
     for drop_h in (True, False):
-        got = _run_mols(gpu_device, ref_m, prb_m, drop_h=drop_h)
+        got = _run(gpu_device, ref_m, prb_m, drop_h=drop_h)
         assert got.dist.tolist() == [MM.mces_milp(a, b, drop_h) for a, b in cases] and (got.status == 0).all()
         _check_maps(got, ref_m, prb_m, drop_h, "edge")
         if drop_h:      # hydrogens only: both W are 0, dist 0, exact, nothing mapped
@@ -122,38 +106,38 @@ def test_edges_of_the_shape(gpu_device, seeded):
             assert got.dist[1] == got.dist[2] == MM.total_weight(ethanol) == 2
     # n is clamped to 0..29 and the lower triangle of a record's bond matrix is not read
     big = max((p for p in range(600) if want[p] > 0), key=lambda p: len(ref[p]["type"]))      # (the atoms beyond its n are bondless hydrogens)
-    (rr, rn), (pr, pn) = GM.records([ref[big], empty]), GM.records([prb[big], empty])
+    (rr, rn), (pr, pn) = SM.records([ref[big], empty]), SM.records([prb[big], empty])
     noisy = pr.copy()
     noisy[0, 406:406 + 841].reshape(29, 29)[np.tril_indices(29)] = 77
-    got = _run(gpu_device, rr, np.array([40, -3], np.int32), noisy, pn)
+    got = _run(gpu_device, (rr, np.array([40, -3], np.int32)), (noisy, pn))
     assert got.dist.tolist() == [want[big], 0] and (got.status == 0).all()
     # ref_index: K candidates share one ground-truth row; a row outside the table is invalid and nothing else changes
     S, K = 20, 4
     rows = np.repeat(np.arange(S), K)
     cand = [prb[s] if k == 0 else (GM.permuted(ref[s], rng) if k == 2 else prb[(s + 7 * k) % 100]) for s in range(S) for k in range(K)]
     wanted = np.array([MM.mces_milp(c, ref[r]) for c, r in zip(cand, rows)])
-    (rr, rn), (pr, pn) = GM.records(ref[:S]), GM.records(cand)
-    got = _run(gpu_device, rr, rn, pr, pn, ref_index=rows)
+    (rr, rn), (pr, pn) = SM.records(ref[:S]), SM.records(cand)
+    got = _run(gpu_device, (rr, rn), (pr, pn), ref_index=rows)
     assert np.array_equal(got.dist, wanted) and (got.status == 0).all() and (wanted.reshape(S, K)[:, 2] == 0).all()
     _check_maps(got, [ref[r] for r in rows], cand, True, "ref_index")
     top = topk_mces(torch.as_tensor(got.dist), torch.as_tensor(got.status), K)
     assert top["best"].tolist() == [0] * S and int(top["undecided"]) == 0
     bad_rows = rows.copy()
     bad_rows[[3, 50]] = [S, -1]
-    bad = _run(gpu_device, rr, rn, pr, pn, ref_index=bad_rows)
+    bad = _run(gpu_device, (rr, rn), (pr, pn), ref_index=bad_rows)
     assert bad.status[[3, 50]].tolist() == [3, 3] and bad.dist[[3, 50]].tolist() == [-1, -1] and bad.lower[[3, 50]].tolist() == [-1, -1]
     assert (bad.map[[3, 50]] == -1).all() and (bad.nodes[[3, 50]] == 0).all()
     keep = np.ones(S * K, bool)
     keep[[3, 50]] = False
     assert all(np.array_equal(a[keep], b[keep]) for a, b in zip(bad, got))
     # P = 0
-    none = _run(gpu_device, rr, rn, pr[:0], pn[:0])
+    none = _run(gpu_device, (rr, rn), (pr[:0], pn[:0]))
     assert none.dist.shape == (0,) and none.status.shape == (0,) and none.map.shape == (0, SM.W)
     # the deepest stack: K29 of one type against itself, hydrogens (there are none) kept - it ends, within its budget
-    k29 = _k29()
+    k29 = GM.k29()
     moved = GM.permuted(k29, rng)
     for budget in (16, 4096):
-        got = _run_mols(gpu_device, [k29, k29], [k29, moved], drop_h=False, max_nodes=budget)
+        got = _run(gpu_device, [k29, k29], [k29, moved], drop_h=False, max_nodes=budget)
         assert set(got.status.tolist()) <= {0, 2} and (got.nodes <= budget).all() and (got.lower == 0).all()
         assert np.array_equal(got.status == 0, got.dist == 0)
         _check_maps(got, [k29, k29], [k29, moved], False, "K29")
@@ -163,19 +147,19 @@ def test_edges_of_the_shape(gpu_device, seeded):
 def test_batch_independence(gpu_device, seeded):
     """A pair's five outputs are bit-identical alone, first, last and in the middle of 10 000."""
     ref, prb, _, want = seeded
-    at64 = _run_mols(gpu_device, ref, prb, max_nodes=64)
+    at64 = _run(gpu_device, ref, prb, max_nodes=64)
     hard, easy = int(np.argmax(at64.nodes * (at64.status == 2))), int(np.argmax(want == 0))
     far = int(np.argmax(want))
     probes = [(hard, 64), (hard, DEFAULT_NODES), (easy, 64), (far, DEFAULT_NODES)]
     assert at64.status[hard] == 2
-    (rr, rn), (pr, pn) = GM.records(ref), GM.records(prb)
+    (rr, rn), (pr, pn) = SM.records(ref), SM.records(prb)
     rep = np.arange(10000) % 600
     places = [0, 4321, 9999]
     for which, budget in probes:
-        alone = _run(gpu_device, rr[which:which + 1], rn[which:which + 1], pr[which:which + 1], pn[which:which + 1], max_nodes=budget)
+        alone = _run(gpu_device, (rr[which:which + 1], rn[which:which + 1]), (pr[which:which + 1], pn[which:which + 1]), max_nodes=budget)
         R, N, Pr, Pn = rr[rep], rn[rep], pr[rep], pn[rep]
         R[places], N[places], Pr[places], Pn[places] = rr[which], rn[which], pr[which], pn[which]
-        full = _run(gpu_device, R, N, Pr, Pn, max_nodes=budget)
+        full = _run(gpu_device, (R, N), (Pr, Pn), max_nodes=budget)
         for x, y in zip(alone, full):
             for where in places:
                 assert x[0].tobytes() == y[where].tobytes(), (which, budget, where)
@@ -186,16 +170,16 @@ def test_batch_independence(gpu_device, seeded):
 def test_identical_graphs_are_zero_apart(gpu_device, seeded):
     """Cross-kernel: whatever ds_graph_identity_records calls identical (whole molecules, hydrogens included) is 0 apart on the heavy atoms."""
     ref, prb, _, want = seeded
-    (rr, rn), (pr, pn) = GM.records(ref), GM.records(prb)
-    dev = lambda a, dt: _t(gpu_device, a, dt)
+    (rr, rn), (pr, pn) = SM.records(ref), SM.records(prb)
+    dev = lambda a, dt: to_dev(gpu_device, a, dt)
     args = (dev(pr, torch.uint8), dev(pn, torch.int32), dev(rr, torch.uint8), dev(rn, torch.int32))
     verdict = E.graph_identity_records(*args)[0].cpu().numpy()
     same = verdict == 1
     assert same.sum() >= 100 and (verdict <= 1).all()
-    heavy = _run(gpu_device, rr, rn, pr, pn)
+    heavy = _run(gpu_device, (rr, rn), (pr, pn))
     assert (heavy.dist[same] == 0).all() and (heavy.status == 0).all()
     # with the hydrogens kept the many equivalent hydrogens can exhaust a budget even on identical graphs: then the root bound still says 0
-    whole = _run(gpu_device, rr, rn, pr, pn, drop_h=False, max_nodes=4096)
+    whole = _run(gpu_device, (rr, rn), (pr, pn), drop_h=False, max_nodes=4096)
     assert (whole.lower[same] == 0).all() and (whole.dist[same & (whole.status == 0)] == 0).all() and (same & (whole.status == 0)).sum() >= 50
     batch = mces_batch((args[2], args[3]), (args[0], torch.as_tensor(pn)))
     assert np.array_equal(batch.dist.cpu().numpy(), heavy.dist) and np.array_equal(batch.exact.cpu().numpy(), heavy.status == 0)
@@ -231,7 +215,7 @@ def test_evaluate_reports_mces(gpu_device, tmp_path, monkeypatch):
 
     def gather_and_plant(rec, n_atoms):
         by_slot = gather(rec, n_atoms)
-        by_slot[planted] = torch.as_tensor(GM.records([moved])[0][0]).to(by_slot.device)
+        by_slot[planted] = torch.as_tensor(SM.records([moved])[0][0]).to(by_slot.device)
         return by_slot
     monkeypatch.setattr(shard, "gather_by_slot", gather_and_plant)
     res = EV.diffspectra_evaluate(cfg, str(tmp_path), table, structure_metrics=True)

@@ -1,5 +1,6 @@
 """GPU: ``ds_match_records`` (one wave per pair, fp64) against the CPU mirror of tests/structure_mirror.py - assignment decisions exact, RMSD
 within 1e-9 A - plus edge cases, batch independence and the evaluation driver end to end."""
+import functools
 from types import SimpleNamespace
 
 import numpy as np
@@ -9,20 +10,15 @@ import torch
 from diffspectra_amd import engine as E, shard
 from diffspectra_amd.structure_metrics import PairMetrics, hungarian_rmsd_batch, topk_summary
 from tests import structure_mirror as SM
+from tests.helpers import run_records
 
 pytestmark = pytest.mark.gpu
+
+_run = functools.partial(run_records, E.match_records, PairMetrics)       # (dev, ref, prb, ref_index=None, **scalars) -> PairMetrics of numpy arrays
 
 # fp64 sums of at most 29 terms of order 10 on both sides: ~1e-13 of rounding; the gate sits four orders above that and about six orders
 # below the fp32 spacing of the input coordinates
 RMSD_TOL = 1e-9
-
-
-def _run(dev, ref_rec, ref_n, prb_rec, prb_n, ref_index=None, **kw):
-    t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
-    idx = None if ref_index is None else t(ref_index, torch.int64)
-    out = E.match_records(t(prb_rec, torch.uint8), t(prb_n, torch.int32), t(ref_rec, torch.uint8), t(ref_n, torch.int32), idx, **kw)
-    torch.cuda.synchronize()
-    return PairMetrics(*(o.cpu().numpy() for o in out))
 
 
 def _compare(got, want, tie_budget=0.0, what=""):
@@ -65,7 +61,7 @@ def test_parity_on_seeded_synthetic_pairs(gpu_device, synthetic):
     jittered = SM.match_batch(prb_rec, prb_n, ref_rec, ref_n, jitter=np.random.default_rng(1))
     moved = sum(not np.array_equal(a["map"], b["map"]) for a, b in zip(want, jittered))
     assert moved == 0, f"{moved} maps change under a 1e-7 cost jitter: those pairs sit on ties two correct solvers may break differently"
-    got = _run(gpu_device, ref_rec, ref_n, prb_rec, prb_n)
+    got = _run(gpu_device, (ref_rec, ref_n), (prb_rec, prb_n))
     ties, worst = _compare(got, want, tie_budget=0.001, what="synthetic")
     print(f"[structure] {len(want)} pairs: {invalid} invalid, {int(got.exact.sum())} exact, {ties} tie pairs, max |rmsd - mirror| = {worst:.3e}")
     # the same pairs without clipping and with a looser floor
@@ -74,7 +70,7 @@ def test_parity_on_seeded_synthetic_pairs(gpu_device, synthetic):
         w = SM.match_batch(prb_rec[sub], prb_n[sub], ref_rec[sub], ref_n[sub], want_internals=True, **kw)
         j = SM.match_batch(prb_rec[sub], prb_n[sub], ref_rec[sub], ref_n[sub], jitter=np.random.default_rng(1), **kw)
         assert all(np.array_equal(a["map"], b["map"]) for a, b in zip(w, j)), f"{kw}: a map moves under the 1e-7 jitter"
-        _compare(_run(gpu_device, ref_rec[sub], ref_n[sub], prb_rec[sub], prb_n[sub], **kw), w, tie_budget=0.001, what=str(kw))
+        _compare(_run(gpu_device, (ref_rec[sub], ref_n[sub]), (prb_rec[sub], prb_n[sub]), **kw), w, tie_budget=0.001, what=str(kw))
     # the list interface of the reference (rmsd.py:232-273)
     dev = lambda a: torch.as_tensor(a).to(gpu_device)
     rl, rate, mean_rmsd, mean_acc = hungarian_rmsd_batch((dev(ref_rec), dev(ref_n)), (dev(prb_rec), dev(prb_n)))
@@ -142,7 +138,7 @@ def test_edge_cases(gpu_device, synthetic):
     cases += [(planar_moved, 6, planar, 6), (planar, 6, planar, 6), (co2_moved, 3, co2, 3), (co2, 3, co2, 3), (planar, 6, co2, 3), (co2, 3, planar, 6)]
     pr, pn, rr, rn = (np.stack([c[0] for c in cases]), np.array([c[1] for c in cases], np.int32), np.stack([c[2] for c in cases]),
                       np.array([c[3] for c in cases], np.int32))
-    got = _run(gpu_device, rr, rn, pr, pn)
+    got = _run(gpu_device, (rr, rn), (pr, pn))
     want = SM.match_batch(pr, pn, rr, rn, want_internals=True)
     # where the answer does not hang on the completion of a rank-deficient SVD (which LAPACK and a Jacobi sweep choose differently) the mirror decides
     _compare(PairMetrics(*(a[:first_invalid_free] for a in got)), want[:first_invalid_free], what="edge")
@@ -158,15 +154,15 @@ def test_edge_cases(gpu_device, synthetic):
     assert got.rmsd[first_invalid_free] < 0.1 and got.rmsd[first_invalid_free + 2] < 0.1
     _compare(PairMetrics(*(a[first_invalid_free:first_invalid_free + 2] for a in got)), want[first_invalid_free:first_invalid_free + 2], what="planar")
     # P = 0
-    empty = _run(gpu_device, rr, rn, pr[:0], pn[:0])
+    empty = _run(gpu_device, (rr, rn), (pr[:0], pn[:0]))
     assert empty.rmsd.shape == (0,) and empty.map.shape == (0, SM.W)
-    assert _run(gpu_device, rr[:0], rn[:0], pr[:0], pn[:0]).exact.shape == (0,)
+    assert _run(gpu_device, (rr[:0], rn[:0]), (pr[:0], pn[:0])).exact.shape == (0,)
     # ref_index: K candidates share one ground-truth row; a row outside the table is an invalid pair, not a read
     K, S = 4, 25
     idx = np.repeat(np.arange(S), K)
     cand = np.stack([prb_rec[(s + k * 7) % 100] if k else prb_rec[s] for s in range(S) for k in range(K)])
     cand_n = np.array([prb_n[(s + k * 7) % 100] if k else prb_n[s] for s in range(S) for k in range(K)], np.int32)
-    got = _run(gpu_device, ref_rec[:S], ref_n[:S], cand, cand_n, ref_index=idx)
+    got = _run(gpu_device, (ref_rec[:S], ref_n[:S]), (cand, cand_n), ref_index=idx)
     want = SM.match_batch(cand, cand_n, ref_rec[:S], ref_n[:S], ref_index=idx, want_internals=True)
     # the same precondition as the parity test: a pair whose mirror map moves under a 1e-7 cost jitter sits on a tie and is left out (foreign
     # candidates are not derived from their ground truth, so the seeded recipe's check does not cover them); no tie allowance beyond that
@@ -176,7 +172,7 @@ def test_edge_cases(gpu_device, synthetic):
     _compare(PairMetrics(*(a[firm] for a in got)), [w for w, f in zip(want, firm) if f], tie_budget=0.0, what="ref_index")
     idx_bad = idx.copy()
     idx_bad[[3, 50]] = [S, -1]
-    bad = _run(gpu_device, ref_rec[:S], ref_n[:S], cand, cand_n, ref_index=idx_bad)
+    bad = _run(gpu_device, (ref_rec[:S], ref_n[:S]), (cand, cand_n), ref_index=idx_bad)
     assert np.isnan(bad.rmsd[[3, 50]]).all() and (bad.map[[3, 50]] == -1).all() and (bad.n_matched[[3, 50]] == 0).all()
     keep = np.ones(S * K, bool)
     keep[[3, 50]] = False
@@ -189,18 +185,18 @@ def test_batch_independence(gpu_device, synthetic):
     """A pair's outputs are bit-identical alone, first, last and among 10 000."""
     ref_rec, ref_n, prb_rec, prb_n = synthetic
     rep = np.arange(10000) % 3000
-    big = _run(gpu_device, ref_rec[rep], ref_n[rep], prb_rec[rep], prb_n[rep])
-    base = _run(gpu_device, ref_rec, ref_n, prb_rec, prb_n)
+    big = _run(gpu_device, (ref_rec[rep], ref_n[rep]), (prb_rec[rep], prb_n[rep]))
+    base = _run(gpu_device, (ref_rec, ref_n), (prb_rec, prb_n))
     for a, b in zip(big, base):
         for lo in range(0, 10000, 3000):
             part = a[lo:lo + 3000]
             assert np.array_equal(part.view(np.uint8) if part.dtype.kind == "f" else part, (b[:len(part)].view(np.uint8) if b.dtype.kind == "f" else b[:len(part)]))
     for p in (0, 17, 1234, 2999):
-        alone = _run(gpu_device, ref_rec[p:p + 1], ref_n[p:p + 1], prb_rec[p:p + 1], prb_n[p:p + 1])
+        alone = _run(gpu_device, (ref_rec[p:p + 1], ref_n[p:p + 1]), (prb_rec[p:p + 1], prb_n[p:p + 1]))
         order = np.r_[p, np.arange(200)]                              # first
-        first = _run(gpu_device, ref_rec[order], ref_n[order], prb_rec[order], prb_n[order])
+        first = _run(gpu_device, (ref_rec[order], ref_n[order]), (prb_rec[order], prb_n[order]))
         order = np.r_[np.arange(200), p]                              # last
-        last = _run(gpu_device, ref_rec[order], ref_n[order], prb_rec[order], prb_n[order])
+        last = _run(gpu_device, (ref_rec[order], ref_n[order]), (prb_rec[order], prb_n[order]))
         for x, f, l, b in zip(alone, first, last, base):
             bits = lambda v: np.ascontiguousarray(v).view(np.uint8).tobytes()
             assert bits(x[0]) == bits(f[0]) == bits(l[-1]) == bits(b[p])

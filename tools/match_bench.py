@@ -21,23 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from diffspectra_amd import engine as E                      # noqa: E402
-from diffspectra_amd.config import QM9_SECOND_HALF_N_NODES    # noqa: E402
 from tests import structure_mirror as SM                      # noqa: E402
-
-
-def kernel_ms(args, launches):
-    for _ in range(3):
-        E.match_records(*args)
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(launches):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        E.match_records(*args)
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return float(np.median(times)), float(min(times)), float(max(times))
+from record_bench import kernel_ms, qm9_sizes                 # noqa: E402  (this directory: the script's own)
 
 
 def main():
@@ -49,8 +34,7 @@ def main():
     import __graft_entry__ as g
     g.build()
     rng = np.random.default_rng(7)
-    sizes_, counts = zip(*sorted(QM9_SECOND_HALF_N_NODES.items()))
-    sizes = rng.choice(sizes_, size=a.pairs, p=np.array(counts) / sum(counts))
+    sizes = qm9_sizes(rng, a.pairs)
     t0 = time.time()
     ref_rec, ref_n, prb_rec, prb_n = SM.synthetic_pairs(a.pairs, 20261017, sizes=sizes)
     gen_s = time.time() - t0
@@ -59,8 +43,7 @@ def main():
     out = {"pairs": a.pairs, "mean_atoms": float(sizes.mean()), "generate_s": gen_s, "launches": a.launches}
     for rep in (1, 10):
         args = (t(prb_rec, rep), t(prb_n, rep), t(ref_rec, rep), t(ref_n, rep))
-        med, lo, hi = kernel_ms(args, a.launches)
-        out[f"kernel_ms_{a.pairs * rep}"] = {"median": med, "min": lo, "max": hi}
+        out[f"kernel_ms_{a.pairs * rep}"] = kernel_ms(E.match_records, args, a.launches)
     res = E.match_records(t(prb_rec), t(prb_n), t(ref_rec), t(ref_n))
     out["valid"] = int((~torch.isnan(res[0])).sum())
     out["exact"] = int(res[4].sum())

@@ -25,23 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from diffspectra_amd import engine as E                      # noqa: E402
-from diffspectra_amd.config import QM9_SECOND_HALF_N_NODES    # noqa: E402
-from tests import graph_mirror as GM, mces_mirror as MM       # noqa: E402
-
-
-def kernel_ms(fn, args, launches):
-    for _ in range(3):
-        fn(*args)
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(launches):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn(*args)
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return {"median": float(np.median(times)), "min": float(min(times)), "max": float(max(times))}
+from tests import graph_mirror as GM, mces_mirror as MM, structure_mirror as SM   # noqa: E402
+from record_bench import kernel_ms, qm9_sizes                 # noqa: E402  (this directory: the script's own)
 
 
 def molecule_of_size(rng, n_atoms):
@@ -64,12 +49,11 @@ def main():
     import __graft_entry__ as g
     g.build()
     rng = np.random.default_rng(7)
-    sizes_, counts = zip(*sorted(QM9_SECOND_HALF_N_NODES.items()))
-    sizes = rng.choice(sizes_, size=a.pairs, p=np.array(counts) / sum(counts))
+    sizes = qm9_sizes(rng, a.pairs)
     t0 = time.time()
     ref = [molecule_of_size(rng, int(s)) for s in sizes]
     prb = [MM.treated(m, (0, 1 + p // 3 % 4, 1 + (p // 3 + 2) % 4)[p % 3], rng, (1, 9), GM.W) for p, m in enumerate(ref)]
-    (ref_rec, ref_n), (prb_rec, prb_n) = GM.records(ref), GM.records(prb)
+    (ref_rec, ref_n), (prb_rec, prb_n) = SM.records(ref), SM.records(prb)
     gen_s = time.time() - t0
     dev = torch.device("cuda:0")
     t = lambda x, rep=1: torch.as_tensor(np.tile(x, (rep,) + (1,) * (x.ndim - 1))).to(dev)

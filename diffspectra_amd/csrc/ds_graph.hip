@@ -24,16 +24,11 @@ namespace {
 
 using ds_rec::MA;                         // 29 atoms: lanes 0..28 hold the generated molecule, lanes 32..60 the ground truth
 using ds_rec::uniform_i;
+using ds_rec::fmix;                       // the 64-bit finaliser and the pair mix of the header's hash formula
+using ds_rec::mix2;
 constexpr int FRESH = 63;                 // colour of an individualised atom: ranks stay below 2 * 29 = 58
 constexpr unsigned ALL = ~0u;             // keep mask of ds_rec::load_bonds: every atom (the kernels below mask by n where they read)
 
-// the 64-bit finaliser and the pair mix of the header's hash formula (wrap-around arithmetic)
-__device__ __forceinline__ uint64_t fmix(uint64_t x) {
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t mix2(uint64_t a, uint64_t b) { return fmix(a + 0x9e3779b97f4a7c15ull * (b + 1ull)); }
 
 struct Pair {                             // both molecules of a pair in LDS; arrays of 64 are indexed by lane
   unsigned char adj[2][MA * 32];

@@ -1,6 +1,6 @@
-// diffspectra_amd - what the per-pair evaluation kernels on result records share (ds_match.hip, ds_graph.hip, ds_mces.hip): the pair
-// prologue, the bond-matrix loader and the host-side argument check of the "record pairs" contract in include/diffspectra_hip.h.  The
-// record layout itself is the header's (DS_REC_*).
+// diffspectra_amd - what the per-pair evaluation kernels on result records share (ds_match.hip, ds_graph.hip, ds_mces.hip, ds_morgan.hip): the
+// pair prologue, the bond-matrix loader, the 64-bit mix of the hashes and the host-side argument check of the "record pairs" contract in
+// include/diffspectra_hip.h.  The record layout itself is the header's (DS_REC_*).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,7 +57,15 @@ __device__ __forceinline__ void load_bonds(unsigned char* __restrict__ adj, cons
   }
 }
 
-// Host side: the argument check of an entry point on one record table (ds_graph_hash_records) and on record pairs, in the order the header
+// the 64-bit finaliser and the pair mix of the header's hash formulas (ds_graph_hash_records, ds_morgan_records; wrap-around arithmetic)
+__device__ __forceinline__ uint64_t fmix(uint64_t x) {
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27; x *= 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint64_t mix2(uint64_t a, uint64_t b) { return fmix(a + 0x9e3779b97f4a7c15ull * (b + 1ull)); }
+
+// Host side: the argument check of an entry point on one record table (ds_graph_hash_records, ds_morgan_records) and on record pairs, in the order the header
 // states - `scalars_ok` (the entry point's own scalar arguments) and the sizes first, then P = 0, then the pointers.  Returns LAUNCH, or the
 // status to return at once: DS_ERR_ARG, or DS_OK when there is nothing to do.
 constexpr int LAUNCH = 1;

@@ -395,7 +395,7 @@ def _want(t, name, dtype, shape):
 
 
 def _record_call(name, tables, ref_index, scalars, outputs):
-    """The binding of an entry point on result records.  ``tables``: ``[(rec, n)]`` (``ds_graph_hash_records``; ``ref_index`` unused) or
+    """The binding of an entry point on result records.  ``tables``: ``[(rec, n)]`` (``ds_graph_hash_records``, ``ds_morgan_records``; ``ref_index`` unused) or
     ``[(prb_rec, prb_n), (ref_rec, ref_n)]`` with ``ref_index`` (the record pairs of the header).  Checks the tensors (never converts them),
     the pairing rule and the one-device rule, allocates ``outputs`` - ``[(dtype, trailing shape)]``, one row per pair - and issues ``ds_<name>``
     with the C ``scalars`` between the tables and the outputs, on the current stream of the tensors' device.  Returns the output tensors."""
@@ -500,6 +500,55 @@ def mces_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tens
         raise TypeError(f"drop_h must be a bool, got {type(drop_h).__name__}")
     return _record_call("mces_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [C.c_int32(int(drop_h)), _node_budget(max_nodes, MCES_MAX_NODES)],
                         [(torch.int32, ()), (torch.int32, ()), (torch.uint8, ()), (torch.int32, ()), _MAP])
+
+
+# ----------------------------------------------------------------------------------------- Morgan fingerprints
+
+MORGAN_MAX_RADIUS, MORGAN_MAX_FEATURES, MORGAN_MAX_BITS = (CONSTS["DS_MORGAN_MAX_" + k] for k in ("RADIUS", "FEATURES", "BITS"))
+MORGAN_OK, MORGAN_INVALID = CONSTS["DS_MORGAN_OK"], CONSTS["DS_MORGAN_INVALID"]
+
+
+def _morgan_shape(drop_h, radius):
+    if not isinstance(drop_h, bool):
+        raise TypeError(f"drop_h must be a bool, got {type(drop_h).__name__}")
+    if isinstance(radius, bool) or not isinstance(radius, int):
+        raise TypeError(f"radius must be an int, got {type(radius).__name__}")
+    if not 0 <= radius <= MORGAN_MAX_RADIUS:
+        raise ValueError(f"radius must lie in [0, {MORGAN_MAX_RADIUS}], got {radius}")
+    return [C.c_int32(int(drop_h)), C.c_int32(radius)]
+
+
+def morgan_records(rec: torch.Tensor, n: torch.Tensor, drop_h: bool = True, radius: int = 2):
+    """``ds_morgan_records``: the Morgan (ECFP-like) fingerprint of the labelled graph of every record as its set of 64-bit features -
+    atom invariant (type, charge, kept degree, hydrogen count, cycle flag), ``radius`` rounds over the kept neighbours, one feature per
+    distinct new bond environment (definition in the header; invariant under renaming atoms).  ``drop_h`` leaves the hydrogens out and
+    counts them in the invariant, as the reference's SMILES route does.  It is not RDKit's fingerprint bit for bit: Kekule orders 1..3
+    instead of aromatic bonds, and RDKit's own invariant hash is not reproduced.
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> ``(ids [P, 116] i64, count [P] i32)`` on the current stream: ``ids[p, :count[p]]`` are the distinct
+    features in ascending UNSIGNED order as int64 bit patterns (read them as unsigned with ``& (2**64 - 1)``), the remaining slots are 0.
+    The arguments are checked, never converted."""
+    return _record_call("morgan_records", [(rec, n)], None, _morgan_shape(drop_h, radius), [(torch.int64, (MORGAN_MAX_FEATURES,)), (torch.int32, ())])
+
+
+def morgan_similarity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                              ref_index: Optional[torch.Tensor] = None, drop_h: bool = True, radius: int = 2, n_bits: int = 2048):
+    """``ds_morgan_similarity_records``: the sizes behind the Tanimoto and the cosine similarity of the Morgan fingerprints
+    (``morgan_records``) of each of P (generated, ground-truth) pairs, folded to ``n_bits`` (0: unfolded; else a power of two in
+    [64, 4096]) - the reference's ``GetMorganFingerprintAsBitVect(mol, 2, nBits=2048)`` with ``TanimotoSimilarity`` / ``CosineSimilarity``
+    (``compute_metrics.py:246-253``), with the stated deviations: Kekule orders 1..3 instead of aromatic bonds (the two Kekule drawings of
+    o-xylene share 5 of 10 + 10 features), RDKit's own hash and fold are not reproduced, and ``drop_h`` is the reference's SMILES route.
+
+    The tensors are those of ``match_records``.  Returns the device tensors ``(common [P] i32, n_prb [P] i32, n_ref [P] i32, status [P] u8)``,
+    enqueued on the current stream without synchronising: the sizes of the intersection and of the two sets, status ``MORGAN_OK`` (0) or
+    ``MORGAN_INVALID`` (3: ``ref_index`` outside the table, the three counts are -1).  The arguments are checked, never converted."""
+    scalars = _morgan_shape(drop_h, radius)
+    if isinstance(n_bits, bool) or not isinstance(n_bits, int):
+        raise TypeError(f"n_bits must be an int, got {type(n_bits).__name__}")
+    if n_bits != 0 and not (64 <= n_bits <= MORGAN_MAX_BITS and n_bits & (n_bits - 1) == 0):
+        raise ValueError(f"n_bits must be 0 (unfolded) or a power of two in [64, {MORGAN_MAX_BITS}], got {n_bits}")
+    return _record_call("morgan_similarity_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, scalars + [C.c_int32(n_bits)],
+                        [(torch.int32, ()), (torch.int32, ()), (torch.int32, ()), (torch.uint8, ())])
 
 
 # ----------------------------------------------------------------------------------------- engine
@@ -652,6 +701,14 @@ class DmtEngine:
     def mces_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, drop_h: bool = True, max_nodes: int = 1 << 18):
         """``engine.mces_records`` on this engine's library (the MCES distance needs no weights)."""
         return mces_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, drop_h, max_nodes)
+
+    def morgan_records(self, rec, n, drop_h: bool = True, radius: int = 2):
+        """``engine.morgan_records`` on this engine's library."""
+        return morgan_records(rec, n, drop_h, radius)
+
+    def morgan_similarity_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, drop_h: bool = True, radius: int = 2, n_bits: int = 2048):
+        """``engine.morgan_similarity_records`` on this engine's library (the fingerprints need no weights)."""
+        return morgan_similarity_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, drop_h, radius, n_bits)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

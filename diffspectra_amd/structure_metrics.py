@@ -20,6 +20,12 @@ How far a wrong molecule is from the right one is ``mces_batch`` / ``topk_mces``
 pair).  It deviates from that number in two stated ways: Kekule bond orders 1..3 instead of RDKit's aromatic 1.5, and parity with the
 ``myopic_mces`` package itself is unpinned (it cannot be run here).
 
+How similar it is in the field's most quoted number is ``morgan_similarity_batch`` / ``topk_morgan``: Tanimoto and cosine similarity of
+radius-2 Morgan fingerprints (``ds_morgan_similarity_records``, ``csrc/ds_morgan.hip``), the reference's "Tanimoto (Morgan)" and "Cosine
+(Morgan)" (``compute_metrics.py:246-253``); ``morgan_fingerprints`` gives the per-molecule fingerprint.  Deviations from that number:
+Kekule orders instead of aromatic bonds, RDKit's own invariant hash and fold are not reproduced (bit-for-bit parity is unpinned), and
+``drop_h`` is the reference's SMILES route.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -256,3 +262,82 @@ def topk_mces(dist: torch.Tensor, status: torch.Tensor, top_k: int) -> Dict[str,
     arg = torch.where(none, torch.full_like(arg, -1), arg)
     mean_best = torch.where(none, torch.zeros_like(best), best).double().sum() / (~none).sum()      # 0 / 0 = NaN without any spectrum
     return dict(best=best, best_index=arg, mean_best=mean_best, undecided=(status == 2).sum())
+
+
+# ------------------------------------------------------------------------------------------------------------------ Morgan fingerprints
+
+class MorganSimilarity(NamedTuple):
+    """Per-pair device tensors of ``ds_morgan_similarity_records``."""
+    common: torch.Tensor      # [P] i32: size of the intersection of the two (folded) feature sets; -1 for an invalid row
+    n_prb: torch.Tensor       # [P] i32: size of the generated molecule's set; -1 for an invalid row
+    n_ref: torch.Tensor       # [P] i32: size of the ground truth's set; -1 for an invalid row
+    status: torch.Tensor      # [P] u8: 0 ok, 3 invalid row
+
+    @property
+    def valid(self) -> torch.Tensor:
+        return self.status == 0
+
+    @property
+    def tanimoto(self) -> torch.Tensor:
+        """``common / (n_prb + n_ref - common)`` as f64: 1.0 when both sets are empty, NaN for an invalid row."""
+        c, union = self.common.double(), (self.n_prb + self.n_ref - self.common).double()
+        out = torch.where(union == 0, torch.ones_like(c), c / union)
+        return torch.where(self.valid, out, torch.full_like(out, float("nan")))
+
+    @property
+    def cosine(self) -> torch.Tensor:
+        """``common / sqrt(n_prb * n_ref)`` as f64: 1.0 when both sets are empty, 0.0 when exactly one is, NaN for an invalid row."""
+        c, a, b = self.common.double(), self.n_prb.double(), self.n_ref.double()
+        none = (self.n_prb == 0) | (self.n_ref == 0)
+        out = torch.where(none, ((self.n_prb == 0) & (self.n_ref == 0)).double(), c / torch.sqrt(torch.where(none, torch.ones_like(a), a * b)))
+        return torch.where(self.valid, out, torch.full_like(out, float("nan")))
+
+
+def morgan_similarity_batch(ref, prb, ref_index=None, drop_h: bool = True, radius: int = 2, n_bits: int = 2048, engine=None) -> MorganSimilarity:
+    """Tanimoto / cosine similarity of the Morgan fingerprints of every generated molecule and its ground truth
+    (``ds_morgan_similarity_records``, ``csrc/ds_morgan.hip``): the set sizes, and ``.tanimoto`` / ``.cosine`` from them - the reference's
+    ``GetMorganFingerprintAsBitVect(mol, 2, nBits=2048)`` with ``TanimotoSimilarity`` / ``CosineSimilarity`` (``compute_metrics.py:246-253``).
+    Deviations from that number: the records hold Kekule orders 1..3 instead of aromatic bonds (the two Kekule drawings of o-xylene share 5 of
+    10 + 10 features at radius 2); RDKit's own invariant hash and fold are not reproduced, so values differ where 2048-bit collisions differ
+    (bit-for-bit parity is unpinned, RDKit cannot be run here); ``drop_h`` is the reference's SMILES route (heavy atoms, hydrogen count in the
+    invariant).  ``n_bits`` 0 compares the unfolded sets.  Arguments as ``graph_identity_batch``.  Device tensors, no synchronisation."""
+    return MorganSimilarity(*_pair_call("morgan_similarity_records", engine, ref, prb, ref_index, drop_h, radius, n_bits))
+
+
+def morgan_fingerprints(records: torch.Tensor, n_atoms, drop_h: bool = True, radius: int = 2, n_bits: Optional[int] = None, engine=None):
+    """The Morgan fingerprint of every record (``ds_morgan_records``; definition in the header).  ``n_bits=None``: ``(ids [P, 116] i64 bit
+    patterns in ascending unsigned order, count [P] i32)``.  Otherwise a ``[P, n_bits]`` bool tensor, bit ``f mod n_bits`` set for every
+    feature f (``n_bits`` a power of two in [64, 4096], as the pair entry point folds) - what diversity and nearest-neighbour analytics
+    take.  Plain torch ops on the records' device, no Python per molecule."""
+    from . import engine as E
+    if n_bits is not None and (isinstance(n_bits, bool) or not isinstance(n_bits, int)):
+        raise TypeError(f"n_bits must be an int or None, got {type(n_bits).__name__}")
+    if n_bits is not None and not (64 <= n_bits <= E.MORGAN_MAX_BITS and n_bits & (n_bits - 1) == 0):
+        raise ValueError(f"n_bits must be a power of two in [64, {E.MORGAN_MAX_BITS}], got {n_bits}")
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    ids, count = (engine if engine is not None else E).morgan_records(records, n, drop_h, radius)
+    if n_bits is None:
+        return ids, count
+    held = torch.arange(ids.shape[1], device=ids.device).unsqueeze(0) < count.unsqueeze(1)
+    bits = torch.zeros(ids.shape[0], n_bits + 1, dtype=torch.bool, device=ids.device)          # column n_bits takes the empty slots
+    bits.scatter_(1, torch.where(held, ids & (n_bits - 1), torch.full_like(ids, n_bits)), True)
+    return bits[:, :n_bits].contiguous()
+
+
+def topk_morgan(tanimoto: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:
+    """Best-of-K reductions of ``MorganSimilarity.tanimoto`` over the K consecutive candidates of every spectrum, NaN (an invalid pair)
+    treated as ``topk_summary`` treats it: ``best [S] f64`` (the largest similarity among the valid candidates, NaN when all K are invalid),
+    ``best_index [S] i64`` (the first candidate with it, -1 when all are invalid) and ``mean_best`` (mean of ``best`` over the spectra that
+    have one, a 0-dim f64 tensor; NaN without any).  Plain torch reductions on the tensor's device."""
+    if top_k < 1 or tanimoto.numel() % top_k:
+        raise ValueError(f"{tanimoto.numel()} pairs are not a whole number of top_k = {top_k} groups")
+    t = tanimoto.reshape(-1, top_k).to(torch.float64)
+    bad = torch.isnan(t)
+    filled = torch.where(bad, torch.full_like(t, float("-inf")), t)
+    best = filled.max(dim=1).values
+    arg = (filled == best.unsqueeze(1)).to(torch.uint8).argmax(dim=1)             # the first candidate that reaches the maximum
+    none = bad.all(dim=1)
+    mean_best = torch.where(none, torch.zeros_like(best), best).sum() / (~none).sum()             # 0 / 0 = NaN without any spectrum
+    best = torch.where(none, torch.full_like(best, float("nan")), best)
+    arg = torch.where(none, torch.full_like(arg, -1), arg)
+    return dict(best=best, best_index=arg, mean_best=mean_best)

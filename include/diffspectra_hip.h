@@ -26,6 +26,8 @@
  *   ds_graph_identity_records   the InChIKey comparison behind Top-K accuracy   compute_metrics.py:222-230, run_lib.py:141
  *   ds_graph_hash_records       the uniqueness count                           evaluation/rdkit_metric.py
  *   ds_mces_records             MCES (Average): one myopic_mces ILP per pair   compute_metrics.py:235-243, run_lib.py:149
+ *   ds_morgan_records /         Tanimoto / cosine similarity of radius-2 Morgan fingerprints   compute_metrics.py:246-253
+ *   ds_morgan_similarity_records
  *   ds_gemm / ds_spec_*   SpecFormer.forward                  models/specformer.py:77-120,167-200,279-309,345-425,457-470
  *
  * Data layout ("packed-ragged", symmetric pair storage — DESIGN.md §3):
@@ -122,8 +124,8 @@ static_assert(DS_REC_BOND_END <= DS_RECORD_BYTES && DS_RECORD_BYTES % 4 == 0, "a
 static_assert((DS_REC_BOND_END + 3) / 4 * 4 <= DS_RECORD_BYTES, "the dwords that cover the bond block stay inside the record");
 #endif
 
-/* Record pairs: the contract that ds_match_records, ds_graph_identity_records and ds_mces_records share (ds_graph_hash_records takes the
- * single-table part of it: one record table, n, alignment, P).
+/* Record pairs: the contract that ds_match_records, ds_graph_identity_records, ds_mces_records and ds_morgan_similarity_records share
+ * (ds_graph_hash_records and ds_morgan_records take the single-table part of it: one record table, n, alignment, P).
  *   Records   prb_rec [P] / ref_rec [M]: DS_RECORD_BYTES bytes each, fields at the DS_REC_* offsets above - fp32 positions [29][3], atom type
  *             bytes in decoder order H, C, N, O, F, formal-charge bytes (i8), the bond-order matrix [29][29] u8, pad.  Both tables must be
  *             4-byte aligned (records are read as dwords and hold fp32 positions).
@@ -408,6 +410,59 @@ int ds_graph_hash_records(const uint8_t* rec, const int32_t* n, int64_t P, uint6
 int ds_mces_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
                     const int64_t* ref_index, int32_t drop_h, int32_t max_nodes, int32_t* dist, int32_t* lower, uint8_t* status,
                     int32_t* nodes, int32_t* map, void* stream);
+
+/* Morgan (ECFP-like) fingerprints of the labelled graph of every record, and the sizes from which the Tanimoto and the cosine similarity of
+ * the fingerprints of (generated, ground-truth) pairs follow - the reference's "Tanimoto (Morgan)" and "Cosine (Morgan)"
+ * (compute_metrics.py:246-253: GetMorganFingerprintAsBitVect(mol, 2, nBits=2048), TanimotoSimilarity, CosineSimilarity) without RDKit.  One
+ * wave per molecule / per pair, integers only.  All arithmetic is unsigned 64-bit with wrap-around; fmix and mix(a, b) are those of
+ * ds_graph_hash_records above.  Records, counts, bonds, pairing and the argument check are those of "record pairs" above; coordinates are
+ * never read.
+ *   Kept atoms   the atoms i < n (n clamped to 0..29); with drop_h = 1 only those whose type byte is not 0.
+ *   Kept bonds   the unordered pairs of kept atoms whose bond byte (upper triangle) is > 0; the bond order is that byte.
+ *   Atom invariant of a kept atom i:
+ *     d_i  the number of kept bonded neighbours;
+ *     h_i  the number of bonded neighbours of type 0 when drop_h = 1, else 0;
+ *     c_i  1 if i lies on a cycle of the kept graph (i has a kept bond whose ends stay connected when that bond is removed), else 0;
+ *     id_0(i) = mix(mix(mix(mix(type_i, charge_i), d_i), h_i), c_i)      (type and charge as the unsigned bytes of the record)
+ *   Iteration, r = 1 .. R, for every kept atom in every round:
+ *     id_r(i) = mix(mix(id_{r-1}(i), r), sum over kept neighbours j of mix(id_{r-1}(j), bond_ij))
+ *   Environments: ball_0(i) = {i}, ball_r(i) = ball_{r-1}(i) plus its kept neighbours; E_r(i), r >= 1, is the set of kept bonds with an end
+ *     in ball_{r-1}(i).
+ *   Features: F_0 = { id_0(i) }.  For r >= 1 the environment (i, r) is NEW when E_r(i) is not empty and differs from E_s(j) for every kept j
+ *     and every 1 <= s < r; F_r holds one value per distinct bond set among the new environments of layer r, the smallest id_r(i) over the
+ *     environments that share the set.  The fingerprint is the SET F_0 u ... u F_R, at most 29 (R + 1) values.  It is invariant under
+ *     renaming atoms by construction: there is no atom order and no "dead atom" chain as in RDKit's sequential duplicate removal - this
+ *     is ECFP's duplicate-environment rule stated order-free.  Folded to n_bits the set is { f mod n_bits }.
+ * Deviations from the reference's number:
+ *   - the records hold Kekule orders 1..3 instead of aromatic bonds: the two Kekule drawings of o-xylene share 5 of their 10 + 10 features
+ *     at R = 2;
+ *   - RDKit's own invariant hash and fold are not reproduced (bit-for-bit parity is unpinned: RDKit cannot be run where this project
+ *     runs), so values differ where the collisions of a 2048-bit fold differ;
+ *   - drop_h = 1 is the reference's SMILES route: heavy atoms only, with the hydrogen count in the invariant.
+ * Method: an atom per lane, 32-bit atom masks.  c_i from the components of the kept graph without atom i (mask squaring): i is on a cycle
+ * iff two of its neighbours share a component.  E(B), the bonds with an end in the atom set B, is represented by the largest atom set with
+ * the same bonds, B plus every kept atom all of whose neighbours are in B, so two environments are compared as two masks.
+ *
+ * ds_morgan_records (one record table, as ds_graph_hash_records):
+ *   ids [P,116] u64  the distinct features of molecule p in ascending unsigned order, the remaining slots 0
+ *   count [P]   i32  how many there are
+ * ds_morgan_similarity_records (record pairs):
+ *   n_prb, n_ref i32  sizes of the two sets after folding to n_bits (n_bits = 0: unfolded)
+ *   common       i32  size of their intersection: Tanimoto = common / (n_prb + n_ref - common), cosine = common / sqrt(n_prb n_ref)
+ *   status       u8   DS_MORGAN_OK, or DS_MORGAN_INVALID: ref_index outside [0, M), nothing is read, the three counts are -1
+ * drop_h outside {0, 1}, radius outside [0, DS_MORGAN_MAX_RADIUS] and an n_bits that is neither 0 nor a power of two in
+ * [64, DS_MORGAN_MAX_BITS] are DS_ERR_ARG.  Every loop of the kernels is bounded by the atom count, the radius or the 116 slots: a malformed
+ * record (dense bond bytes, garbage in the lower triangle or beyond n) ends with the value the definition gives. */
+#define DS_MORGAN_MAX_RADIUS 3
+#define DS_MORGAN_MAX_FEATURES 116    /* 29 * (3 + 1) */
+#define DS_MORGAN_MAX_BITS 4096
+#define DS_MORGAN_OK 0
+#define DS_MORGAN_INVALID 3
+int ds_morgan_records(const uint8_t* rec, const int32_t* n, int64_t P, int32_t drop_h, int32_t radius, uint64_t* ids, int32_t* count,
+                      void* stream);
+int ds_morgan_similarity_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
+                                 const int64_t* ref_index, int32_t drop_h, int32_t radius, int32_t n_bits, int32_t* common, int32_t* n_prb,
+                                 int32_t* n_ref, uint8_t* status, void* stream);
 
 /* SpecFormer pieces that are not plain GEMMs (specformer.py:385-425 residual-score attention; :119 LayerNorm).
  * qkv [B,L,3*heads*dk]; out [B,L,heads*dk]; scores: B*heads*L*L floats of caller-owned scratch that carries the

@@ -1,4 +1,4 @@
-"""What the three record-pair bench tools (match_bench.py, graph_bench.py, mces_bench.py) share: the event-timed launch loop and the draw
+"""What the record bench tools (match_bench.py, graph_bench.py, mces_bench.py, morgan_bench.py) share: the event-timed launch loop and the draw
 of molecule sizes at the QM9 size mix.  Imported by them as scripts (their directory is on ``sys.path``), after the repository root has been added."""
 import numpy as np
 import torch

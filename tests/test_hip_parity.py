@@ -13,6 +13,7 @@ import oracle
 from oracle import dmt as odmt
 from tests.golden import cases
 from tests.helpers import procedural_state_dict, max_abs_diff
+from tests.helpers import checkpoint_like as _checkpoint_like, oracle_edge_maps as _oracle_edge_maps, oracle_forward_f64 as _oracle_forward_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -240,40 +241,6 @@ def test_split_fp16_range_saturates(gpu_device):
     assert torch.isfinite(o).all() and o[0, 0] == 65519.0 and o[2, 2] == sat and o[3, 3] == -sat
 
 
-def _oracle_forward_f64(sd, cfg, a):
-    """The oracle in fp64 (same code, default dtype switched): the truth both fp32 evaluations are measured against."""
-    torch.set_default_dtype(torch.float64)
-    try:
-        dd = lambda t: None if t is None else ([x.double() for x in t] if isinstance(t, (list, tuple)) else t.double())
-        sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
-        return oracle.dmt_forward(sd64, cfg, dd(a["xh"]), dd(a["node_mask"]), dd(a["edge_mask"]), dd(a["edge_x"]), dd(a["noise_level"]),
-                                  dd(a["cond_x"]), dd(a["cond_edge_x"]), context=dd(a["context"]))
-    finally:
-        torch.set_default_dtype(torch.float32)
-
-
-def _checkpoint_like(sd):
-    """Weight statistics a trained checkpoint can have and the U(+-1/sqrt(fan_in)) filler never does: adaLN scale / shift / gate
-    outputs 30x larger (every block's node / edge / equi / dist time_mlp), a few residual-stream channels at 1e4 magnitude,
-    weights with 1e-6 entries.  (The top-level 17 -> 1024 time MLP is left alone: scaling it as well makes the forward
-    ill-conditioned - the fp32 CPU oracle itself is then 10 % away from fp64.)"""
-    import re
-    out = dict(sd)
-    for key, v in sd.items():
-        k = key[7:] if key.startswith("module.") else key
-        if re.match(r"e_block_\d+\.(node_time_mlp|edge_time_mlp|equi_update\.time_mlp|dist_layer\.time_mlp)\.1\.", k):
-            out[key] = v * 30.0
-        elif k == "node_emb.weight":
-            w = v.clone()
-            w[[3, 77, 200]] *= 1e4                                      # three residual-stream channels ~1e4
-            out[key] = w
-        elif re.match(r"e_block_\d+\.(ff_linear1|ff_linear3|equi_update\.coord_mlp\.0)\.weight", k):
-            w = v.clone()
-            w[::3] *= 1e-5                                              # rows of ~1e-6 entries next to ordinary ones
-            out[key] = w
-    return out
-
-
 def test_forward_with_checkpoint_like_statistics(gpu_device):
     """Range-proofing of the split-fp16 path: a forward with checkpoint-like weight statistics stays finite and
     within 2e-5 (relative to the output scale) of the fp64 truth, or within 8x the fp32 CPU oracle's own distance from fp64 where
@@ -398,18 +365,6 @@ def test_spec_attention_vs_torch(gpu_device, L, has_prev):
 
 # ------------------------------------------------------------------------------------------------ stages
 
-def _oracle_edge_maps(L, N):
-    """Index of every packed pair (a<b) in the oracle's directed edge list (row-major nonzero order)."""
-    nd = L.t["node_dense"].cpu().long()
-    pa, pb = nd[L.t["pair_a"].cpu().long()], nd[L.t["pair_b"].cpu().long()]
-    valid = torch.from_numpy(L.valid)
-    adj = (valid.unsqueeze(1) & valid.unsqueeze(2)) & ~torch.eye(N, dtype=torch.bool).unsqueeze(0)
-    eid = torch.full(adj.shape, -1, dtype=torch.long)
-    eid[adj] = torch.arange(int(adj.sum()))
-    b = pa // N
-    return eid[b, pa % N, pb % N], eid[b, pb % N, pa % N], nd
-
-
 @pytest.mark.parametrize("first", [True, False])
 def test_stages_vs_oracle(gpu_device, first):
     """time/adaLN table, init, each of the 8 blocks (h, e, pos) and the readout, localising any mismatch."""
@@ -424,7 +379,7 @@ def test_stages_vs_oracle(gpu_device, first):
                                  a["cond_x"], a["cond_edge_x"], context_emb=ctx_cpu, return_debug=True)
     ref_xh, ref_edge, dbg = ref_out
     N = L.N
-    fwd, bwd, nd = _oracle_edge_maps(L, N)
+    fwd, bwd, nd = _oracle_edge_maps(L.valid, L.t["node_dense"], L.t["pair_a"], L.t["pair_b"])
     # --- time embedding + adaLN table
     xh, edge_x, nl = a["xh"].to(d), a["edge_x"].to(d), a["noise_level"].to(d)
     cx, ce = to_dev(a["cond_x"], d), to_dev(a["cond_edge_x"], d)

@@ -64,6 +64,14 @@ QM9_SECOND_HALF_N_NODES = {
     24: 267, 25: 754, 26: 17, 27: 132, 29: 15,
 }
 
+# The substructure classes of the bond-length / bond-angle / dihedral-angle MMD (reference ``datasets/datasets_config.py:30-33``,
+# ``qm9_second_half['top_bond_sym' | 'top_angle_sym' | 'top_dihedral_sym']``; ``qm9_with_h`` lists the same): element, bond order, element,
+# chained with '-' on a shared atom.  ``structure_metrics.geometry_classes`` parses them.
+QM9_ATOM_DECODER = ("H", "C", "N", "O", "F")
+QM9_TOP_BOND_SYM = ("C1H", "C1C", "C1O", "N1C", "N1H", "C2O", "O1H", "C2C")
+QM9_TOP_ANGLE_SYM = ("C1C-C1H", "C1C-C1C", "C1C-C1O", "C1C-C1N", "C1N-N1C", "C1O-O1C", "O1C-C1H", "C2C-C1C")
+QM9_TOP_DIHEDRAL_SYM = ("H1C-C1C-C1C", "C1C-C1C-C1C", "H1C-C1C-C1H", "H1C-C1C-C1O", "C1C-C1C-C1O", "C1N-N1C-C1C", "H1C-C1N-N1C", "H1C-C1C-C1N")
+
 SPECTRUM_LENGTHS = (701, 3501, 3501)  # uv, ir, raman (reference models/specformer.py:33)
 
 

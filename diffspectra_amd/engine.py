@@ -551,6 +551,119 @@ def morgan_similarity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_re
                         [(torch.int32, ()), (torch.int32, ()), (torch.int32, ()), (torch.uint8, ())])
 
 
+# ----------------------------------------------------------------------------------------- substructure geometry and its MMD
+
+GEOM_MAX_CLASSES = CONSTS["DS_GEOM_MAX_CLASSES"]
+MMD_TILE, MMD_MAX_SAMPLES, MMD_MAX_KERNELS, MMD_MAX_CLASSES = (CONSTS["DS_MMD_" + k] for k in ("TILE", "MAX_SAMPLES", "MAX_KERNELS", "MAX_CLASSES"))
+MMD_OK, MMD_EMPTY, MMD_INVALID = (CONSTS["DS_MMD_" + k] for k in ("OK", "EMPTY", "INVALID"))
+
+
+def _class_tables(rec, bond_cls, angle_cls, dihedral_cls):
+    """The three class tables as C arguments (pointer, count each): int32 device vectors of at most 32 codes on the records' device."""
+    args = []
+    for t, name in ((bond_cls, "bond_cls"), (angle_cls, "angle_cls"), (dihedral_cls, "dihedral_cls")):
+        _want(t, name, torch.int32, (None,))
+        if t.shape[0] > GEOM_MAX_CLASSES:
+            raise ValueError(f"{name} holds {t.shape[0]} classes, at most {GEOM_MAX_CLASSES} fit")
+        if torch.is_tensor(rec) and t.device != rec.device:
+            raise RuntimeError(f"{name} must be on the records' device {rec.device}, got {t.device}")
+        args += [_ptr(t) if t.shape[0] else None, C.c_int32(t.shape[0])]
+    return args
+
+
+def geometry_count_records(rec: torch.Tensor, n: torch.Tensor, bond_cls: torch.Tensor, angle_cls: torch.Tensor, dihedral_cls: torch.Tensor):
+    """``ds_geometry_count_records``: how many bond lengths, bond angles and dihedral angles of each record fall into the listed classes.
+
+    ``rec [P, 1248] u8``, ``n [P] i32``; the class tables are int32 device vectors of at most 32 codes each, the fields of a class in 4-bit
+    groups (first field in bits 0..3; ``structure_metrics.geometry_classes`` builds them from the reference's symbols).  Returns ``(counts
+    [P, 3] i32, skipped [P] i32)`` on the current stream without synchronising: entries emitted per kind, and entries of a listed class whose
+    value is undefined (coincident atoms, a collinear dihedral).  Every angle counts once - the reference counts it 0, 1 or 2 times depending
+    on the atom numbering - and parity with RDKit's angle functions is unpinned (see the header).  Checked, never converted."""
+    return _record_call("geometry_count_records", [(rec, n)], None, _class_tables(rec, bond_cls, angle_cls, dihedral_cls),
+                        [(torch.int32, (3,)), (torch.int32, ())])
+
+
+def geometry_fill_records(rec: torch.Tensor, n: torch.Tensor, bond_cls: torch.Tensor, angle_cls: torch.Tensor, dihedral_cls: torch.Tensor,
+                          offsets: torch.Tensor, totals):
+    """``ds_geometry_fill_records``: the values and classes that ``geometry_count_records`` counted.  ``offsets [P, 3] i64``: where each record's
+    entries of each kind start (the exclusive prefix sum of ``counts`` over the records); ``totals``: three ints, the length of each kind's
+    output.  Returns ``((bond_value [T0] f32, bond_class [T0] u8), (angle_value, angle_class), (dihedral_value, dihedral_class))`` on the current
+    stream without synchronising: lengths in the units of the record's positions, angles in degrees in [0, 180], dihedrals in degrees in
+    (-180, 180]; within a record in the header's fixed order, so bit-identical from run to run.  An index at or beyond a total is never
+    written.  The deviations from the reference are those of ``geometry_count_records``.  Checked, never converted."""
+    tables = _class_tables(rec, bond_cls, angle_cls, dihedral_cls)
+    totals = [int(t) for t in totals]
+    if len(totals) != 3 or min(totals) < 0:
+        raise ValueError(f"totals must be three non-negative ints, got {totals}")
+    _want(rec, "rec", torch.uint8, (None, RECORD_BYTES))
+    _want(offsets, "offsets", torch.int64, (rec.shape[0], 3))
+    if offsets.device != rec.device:
+        raise RuntimeError(f"offsets must be on the records' device {rec.device}, got {offsets.device}")
+    out = tuple((torch.empty(t, dtype=torch.float32, device=rec.device), torch.empty(t, dtype=torch.uint8, device=rec.device)) for t in totals)
+    _record_call("geometry_fill_records", [(rec, n)], None,
+                 tables + [C.c_int64(t) for t in totals] + [_ptr(offsets)] + [_ptr(t) if t.numel() else None for pair in out for t in pair], [])
+    return out
+
+
+def mmd_workspace_bytes(n_classes: int) -> int:
+    """``ds_mmd_1d_workspace_bytes``: the device bytes ``mmd_1d_segments`` needs for ``n_classes`` classes (a pure host function)."""
+    size = C.c_int64(0)
+    _check(load_library().ds_mmd_1d_workspace_bytes(C.c_int64(int(n_classes)), C.byref(size)), "ds_mmd_1d_workspace_bytes")
+    return int(size.value)
+
+
+def mmd_1d_segments(x: torch.Tensor, x_off: torch.Tensor, y: torch.Tensor, y_off: torch.Tensor, kernel_mul: float = 2.0, kernel_num: int = 5,
+                    fix_sigma: Optional[float] = None, workspace: Optional[torch.Tensor] = None):
+    """``ds_mmd_1d_segments``: the reference's ``compute_mmd`` (``evaluation/mmd.py:6-63``; a sum of ``kernel_num`` Gaussian kernels whose
+    bandwidths are ``kernel_mul`` apart around the mean squared distance of the pooled samples, or around ``fix_sigma``) of C classes of 1-D
+    samples in one launch sequence.  ``x [Nx] f32`` / ``y [Ny] f32``: source / target samples, class c in ``x[x_off[c]:x_off[c+1]]`` and
+    ``y[y_off[c]:y_off[c+1]]`` (``x_off``, ``y_off`` ``[C+1] i64`` on the device).  ``workspace``: a ``uint8`` device tensor of at least
+    ``mmd_workspace_bytes(C)`` bytes, allocated here when ``None``.
+
+    Returns ``(out [C, 5] f64 = (mmd, XX, YY, XY, bandwidth), status [C] u8)`` on the current stream without synchronising: status ``MMD_OK``,
+    ``MMD_EMPTY`` (no source or no target sample: NaN) or ``MMD_INVALID`` (unusable offsets, or more than 2^20 samples on a side: NaN).  All
+    samples identical gives NaN, as the reference does.  Bit-identical from run to run.  Checked, never converted; no CPU path."""
+    _want(x, "x", torch.float32, (None,))
+    _want(y, "y", torch.float32, (None,))
+    _want(x_off, "x_off", torch.int64, (None,))
+    _want(y_off, "y_off", torch.int64, (x_off.shape[0],))
+    if x_off.shape[0] < 1:
+        raise ValueError("x_off and y_off hold C + 1 offsets: at least one")
+    n_cls = x_off.shape[0] - 1
+    if n_cls > MMD_MAX_CLASSES:
+        raise ValueError(f"at most {MMD_MAX_CLASSES} classes per call, got {n_cls}")
+    if isinstance(kernel_num, bool) or not isinstance(kernel_num, int):
+        raise TypeError(f"kernel_num must be an int, got {type(kernel_num).__name__}")
+    if not 1 <= kernel_num <= MMD_MAX_KERNELS:
+        raise ValueError(f"kernel_num must lie in [1, {MMD_MAX_KERNELS}], got {kernel_num}")
+    kernel_mul, sigma = float(kernel_mul), float(fix_sigma) if fix_sigma else 0.0          # the reference's `if fix_sigma:`
+    if not (0.0 < kernel_mul < float("inf")):
+        raise ValueError(f"kernel_mul must be finite and > 0, got {kernel_mul}")
+    if not (0.0 <= sigma < float("inf")):
+        raise ValueError(f"fix_sigma must be finite and >= 0, got {fix_sigma}")
+    tensors = [x, x_off, y, y_off]
+    need = mmd_workspace_bytes(n_cls)
+    dev = x.device
+    if workspace is not None:
+        _want(workspace, "workspace", torch.uint8, (None,))
+        if workspace.shape[0] < need:
+            raise ValueError(f"workspace holds {workspace.shape[0]} bytes, {need} are needed for {n_cls} classes")
+        tensors.append(workspace)
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise RuntimeError("mmd_1d_segments needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    lib = load_library()
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    out = torch.empty(n_cls, 5, dtype=torch.float64, device=dev)
+    status = torch.empty(n_cls, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = lib.ds_mmd_1d_segments(_ptr(x) if x.numel() else None, _ptr(x_off), C.c_int64(x.shape[0]), _ptr(y) if y.numel() else None, _ptr(y_off),
+                                    C.c_int64(y.shape[0]), C.c_int64(n_cls), C.c_double(kernel_mul), C.c_int32(kernel_num), C.c_double(sigma),
+                                    _ptr(workspace), C.c_int64(workspace.shape[0]), _ptr(out), _ptr(status), _stream())
+    _check(st, "ds_mmd_1d_segments")
+    return out, status
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -709,6 +822,18 @@ class DmtEngine:
     def morgan_similarity_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, drop_h: bool = True, radius: int = 2, n_bits: int = 2048):
         """``engine.morgan_similarity_records`` on this engine's library (the fingerprints need no weights)."""
         return morgan_similarity_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, drop_h, radius, n_bits)
+
+    def geometry_count_records(self, rec, n, bond_cls, angle_cls, dihedral_cls):
+        """``engine.geometry_count_records`` on this engine's library."""
+        return geometry_count_records(rec, n, bond_cls, angle_cls, dihedral_cls)
+
+    def geometry_fill_records(self, rec, n, bond_cls, angle_cls, dihedral_cls, offsets, totals):
+        """``engine.geometry_fill_records`` on this engine's library."""
+        return geometry_fill_records(rec, n, bond_cls, angle_cls, dihedral_cls, offsets, totals)
+
+    def mmd_1d_segments(self, x, x_off, y, y_off, kernel_mul: float = 2.0, kernel_num: int = 5, fix_sigma=None, workspace=None):
+        """``engine.mmd_1d_segments`` on this engine's library (the MMD needs no weights)."""
+        return mmd_1d_segments(x, x_off, y, y_off, kernel_mul, kernel_num, fix_sigma, workspace)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

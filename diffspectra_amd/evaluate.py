@@ -133,6 +133,12 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     RDKit's own invariant hash and fold are not reproduced (values differ where 2048-bit collisions differ), and the hydrogens enter as a
     count in the atom invariant, the reference's SMILES route.
 
+    With ``config.eval.sub_geometry`` true (the reference's ``evaluate.sub_geometry``, ``configs/diffspectra_qm9s.py:145``)
+    ``metrics['structure']['sub_geometry']`` is the reference's "Metric-Align" dict (``run_lib.py:392-411``): the bond-length, bond-angle and
+    dihedral-angle MMD between the generated records and ALL records of the test table for every QM9 substructure symbol, and
+    ``bond_length_mean`` / ``bond_angle_mean`` / ``dihedral_angle_mean`` (``structure_metrics.get_sub_geometry_metric``, which states the
+    deviations: every angle counts once, RDKit parity unpinned, a seeded sample cap).  Without the flag the dict has no such key.
+
     ``test_ds=None`` reads the reference's processed files under ``config.data.root`` (``run_lib.py:313`` ->
     ``build_dataset.py:31-42``: the 'test' entry of ``split_dict_diffspectra_qm9.pt``) into the device-resident table of
     ``qm9s_reader.ProcessedQM9S.packed_table`` - no PyG, no per-molecule Python."""
@@ -155,6 +161,7 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     sampling_fn = get_cond_sampling_eval_fn(config, noise_scheduler, config.eval.batch_size, config.eval.num_samples,
                                             inverse_scaler, test_ds, top_k=top_k)
     results = {}
+    geometry_fn = None                            # the test side of the geometry MMD is extracted once, at the first checkpoint
     for ckpt in checkpoint_ids(config):
         ckpt_path = os.path.join(workdir, "checkpoints", "checkpoint_{}.pth".format(ckpt))
         if not os.path.exists(ckpt_path):
@@ -172,5 +179,10 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
         metrics = {name: fn(processed_mols, gt_pos, gt_rdmols) for name, fn in (metric_fns or {}).items()}
         if structure_metrics:
             metrics["structure"] = _structure_summary(run, test_ds, top_k)
+            if getattr(config.eval, "sub_geometry", False):
+                from .structure_metrics import get_sub_geometry_metric
+                if geometry_fn is None:
+                    geometry_fn = get_sub_geometry_metric((test_ds.gt_records.to(run.records_by_slot.device), test_ds.num_atom), engine=run.eng)
+                metrics["structure"]["sub_geometry"] = geometry_fn((run.records_by_slot, torch.tensor(run.n_atoms)))
         results[ckpt] = dict(processed_mols=processed_mols, gt_pos=gt_pos, gt_rdmols=gt_rdmols, metrics=metrics, step=state["step"])
     return results

@@ -26,6 +26,13 @@ radius-2 Morgan fingerprints (``ds_morgan_similarity_records``, ``csrc/ds_morgan
 Kekule orders instead of aromatic bonds, RDKit's own invariant hash and fold are not reproduced (bit-for-bit parity is unpinned), and
 ``drop_h`` is the reference's SMILES route.
 
+Whether the 3-D conformations are right as a DISTRIBUTION is ``get_sub_geometry_metric``: the reference's bond-length, bond-angle and
+dihedral-angle MMD between generated and test molecules per substructure symbol (``evaluation/cal_geometry.py``, ``evaluation/mmd.py``; its
+"Metric-Align" line).  ``sub_geometry`` extracts the samples (``ds_geometry_count_records`` / ``ds_geometry_fill_records``,
+``csrc/ds_subgeom.hip``), ``mmd_1d`` / ``ds_mmd_1d_segments`` (``csrc/ds_mmd.hip``) is ``compute_mmd``.  Deviations: every angle counts once
+(the reference counts it 0, 1 or 2 times depending on the atom numbering), parity with RDKit's angle functions is unpinned, and the
+20 000-sample cap is a seeded ``torch.randperm``.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -341,3 +348,157 @@ def topk_morgan(tanimoto: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:
     best = torch.where(none, torch.full_like(best, float("nan")), best)
     arg = torch.where(none, torch.full_like(arg, -1), arg)
     return dict(best=best, best_index=arg, mean_best=mean_best)
+
+
+# ------------------------------------------------------------------------------------------------------------------ substructure geometry MMD
+
+class GeometryClasses(NamedTuple):
+    """The substructure classes of the geometry metric: per kind (bonds, angles, dihedrals) the reference's symbols and their codes."""
+    symbols: tuple            # three tuples of symbols such as 'C1H', 'C1C-C1O', 'H1C-C1C-C1N'
+    codes: tuple              # three tuples of ints: the fields (type, order, type, ...) in 4-bit groups, first field lowest (the header's encoding)
+
+
+class SubGeometry(NamedTuple):
+    """What ``sub_geometry`` extracts from a record table."""
+    values: Dict[str, torch.Tensor]   # symbol -> device f32 tensor: lengths (units of the positions), angles [0, 180] or dihedrals (-180, 180] in degrees
+    skipped: torch.Tensor             # [P] i32: entries of a listed class whose value is undefined (coincident atoms, a collinear dihedral)
+    classes: GeometryClasses
+
+
+_GEOMETRY_KINDS = (("top_bond_sym", "bond_length_mean"), ("top_angle_sym", "bond_angle_mean"), ("top_dihedral_sym", "dihedral_angle_mean"))
+
+
+def _symbol_fields(symbol: str, parts: int, decoder) -> tuple:
+    """'H1C-C1N-N1C' -> (0, 1, 1, 1, 2, 1, 1): element, order, element of every part, adjacent parts chained on the shared atom."""
+    import re
+    pieces = symbol.split("-")
+    if len(pieces) != parts:
+        raise ValueError(f"{symbol!r}: {parts} bond(s) expected, {len(pieces)} given")
+    fields = []
+    for k, piece in enumerate(pieces):
+        m = re.fullmatch(r"([A-Z][a-z]?)(\d+)([A-Z][a-z]?)", piece)
+        if m is None:
+            raise ValueError(f"{symbol!r}: {piece!r} is not <element><bond order><element>")
+        left, order, right = m.group(1), int(m.group(2)), m.group(3)
+        for el in (left, right):
+            if el not in decoder or decoder.index(el) > 15:
+                raise ValueError(f"{symbol!r}: element {el!r} is not one of the first 16 of the atom decoder {list(decoder)}")
+        if not 1 <= order <= 15:
+            raise ValueError(f"{symbol!r}: bond order {order} outside 1..15")
+        if k and decoder.index(left) != fields[-1]:
+            raise ValueError(f"{symbol!r}: {pieces[k - 1]!r} and {piece!r} do not chain on the same atom")
+        fields += ([decoder.index(left)] if not k else []) + [order, decoder.index(right)]
+    return tuple(fields)
+
+
+def geometry_classes(dataset_info: Optional[Dict] = None) -> GeometryClasses:
+    """The class tables of ``ds_geometry_*_records`` from the reference's symbol lists: ``dataset_info['top_bond_sym' | 'top_angle_sym' |
+    'top_dihedral_sym']`` and ``dataset_info['atom_decoder']`` (``datasets/datasets_config.py:19-35``); ``None``: the QM9 lists of ``config``.
+    A symbol is ``<element><order><element>``, chained with '-' on the shared atom ('H1C-C1N-N1C').  ``ValueError`` on an unknown element, on
+    parts that do not chain, on a list that names a class twice (a class equals its own reverse) and on more than 32 classes of a kind."""
+    from . import config as K
+    info = dataset_info or dict(atom_decoder=K.QM9_ATOM_DECODER, top_bond_sym=K.QM9_TOP_BOND_SYM, top_angle_sym=K.QM9_TOP_ANGLE_SYM,
+                                top_dihedral_sym=K.QM9_TOP_DIHEDRAL_SYM)
+    decoder = list(info["atom_decoder"])
+    symbols, codes = [], []
+    for parts, (key, _) in enumerate(_GEOMETRY_KINDS, start=1):
+        names = tuple(info[key])
+        if len(names) > 32:
+            raise ValueError(f"{key}: {len(names)} classes, at most 32 fit a table")
+        seen, row = {}, []
+        for name in names:
+            fields = _symbol_fields(name, parts, decoder)
+            canon = min(fields, fields[::-1])
+            if canon in seen:
+                raise ValueError(f"{key}: {name!r} names the class of {seen[canon]!r} again (a class is its symbol read in either direction)")
+            seen[canon] = name
+            row.append(sum(f << (4 * k) for k, f in enumerate(fields)))
+        symbols.append(names)
+        codes.append(tuple(row))
+    return GeometryClasses(tuple(symbols), tuple(codes))
+
+
+def sub_geometry(records: torch.Tensor, n_atoms, classes: Optional[GeometryClasses] = None, engine=None) -> SubGeometry:
+    """Bond lengths, bond angles and dihedral angles of every record of ``records [P, 1248] u8`` (GPU), by substructure symbol - the sample
+    lists of ``cal_bond_distance`` / ``cal_bond_angle`` / ``cal_dihedral_angle`` (``evaluation/cal_geometry.py``) on the unsanitised molecules
+    of ``check_2D_stability``: every atom and fragment, bonds of any order > 0, positions as they are.  Two kernels
+    (``ds_geometry_count_records``, then ``ds_geometry_fill_records`` at the prefix sum of the counts; the totals cross to the host once, to
+    size the outputs), then a stable sort by class.  Two stated deviations from the reference: every angle counts once (the reference counts
+    it 0, 1 or 2 times depending on atom numbering and on RDKit's begin / end of a bond), and parity with RDKit's ``GetAngleDeg`` /
+    ``GetDihedralDeg`` is unpinned (RDKit cannot be run here; the dihedral's global sign cancels in the MMD)."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    classes = classes if classes is not None else geometry_classes()
+    dev = records.device
+    n = torch.as_tensor(n_atoms).to(device=dev, dtype=torch.int32).contiguous()
+    tables = [torch.tensor(list(c), dtype=torch.int32, device=dev) for c in classes.codes]
+    counts, skipped = eng.geometry_count_records(records, n, *tables)
+    ends = counts.to(torch.int64).cumsum(0)
+    totals = ends[-1].tolist() if ends.shape[0] else [0, 0, 0]
+    filled = eng.geometry_fill_records(records, n, *tables, (ends - counts).contiguous(), totals)
+    values = {}
+    for names, (value, cls) in zip(classes.symbols, filled):
+        by_class = torch.sort(cls, stable=True).indices
+        sizes = torch.bincount(cls.to(torch.int64), minlength=len(names))[:len(names)].tolist()
+        for name, part in zip(names, torch.split(value[by_class], sizes)):
+            values[name] = part
+    return SubGeometry(values, skipped, classes)
+
+
+def mmd_1d(source: torch.Tensor, target: torch.Tensor, kernel_mul: float = 2.0, kernel_num: int = 5, fix_sigma: Optional[float] = None,
+           engine=None) -> float:
+    """``compute_mmd`` of ``evaluation/mmd.py:6-63`` for two 1-D f32 sample tensors on the GPU (``ds_mmd_1d_segments`` with one class): a
+    Python float, NaN when a side is empty or all samples are identical.  At most 2^20 samples per side."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    for t, name in ((source, "source"), (target, "target")):
+        E._want(t, name, torch.float32, (None,))
+        if t.shape[0] > E.MMD_MAX_SAMPLES:
+            raise ValueError(f"{name} holds {t.shape[0]} samples, at most {E.MMD_MAX_SAMPLES} fit")
+    off = lambda t: torch.tensor([0, t.shape[0]], dtype=torch.int64, device=t.device)
+    out, _ = eng.mmd_1d_segments(source, off(source), target, off(target), kernel_mul, kernel_num, fix_sigma)
+    return float(out[0, 0])
+
+
+def _capped(t: torch.Tensor, max_samples: Optional[int], gen: torch.Generator) -> torch.Tensor:
+    if max_samples is None or t.shape[0] <= max_samples:
+        return t
+    return t[torch.randperm(t.shape[0], generator=gen)[:max_samples].to(t.device)]
+
+
+def get_sub_geometry_metric(test, dataset_info: Optional[Dict] = None, max_samples: Optional[int] = 20000, seed: int = 0, engine=None):
+    """``get_sub_geometry_metric`` of ``evaluation/cal_geometry.py:287-301`` on record tensors: ``test`` is ``(records [*, 1248] u8 on the
+    GPU, n_atoms [*])`` of the test molecules, whose geometry is extracted once, here.  Returns ``fn(generated)``, ``generated`` another such
+    pair, which gives the reference's dict: the MMD of every symbol of the three lists (NaN where a side has no sample,
+    ``cal_geometry.py:273-275``) and ``bond_length_mean``, ``bond_angle_mean``, ``dihedral_angle_mean``, the NaN-ignoring means of their
+    kinds - Python floats, all classes through one ``ds_mmd_1d_segments`` launch sequence.
+
+    Deviations from the reference: its ``random.sample`` cap of 20 000 samples per symbol and side is a seeded ``torch.randperm`` on the host
+    here (the target side drawn once with ``seed``, the generated side with ``seed + 1`` on every call, so a call is reproducible;
+    ``max_samples=None`` uses every sample, up to 2^20 per symbol and side); its ``target_geometry_stat.pk`` cache is not kept; and the two of
+    ``sub_geometry``: every angle counts once, parity with RDKit's angle functions is unpinned."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    classes = geometry_classes(dataset_info)
+    names = [s for kind in classes.symbols for s in kind]
+    target = sub_geometry(test[0], test[1], classes, engine).values
+    gen = torch.Generator().manual_seed(int(seed))
+    dev = test[0].device
+
+    def packed(values, gen):
+        parts = [_capped(values[s], max_samples, gen) for s in names]
+        sizes = torch.tensor([0] + [p.shape[0] for p in parts], dtype=torch.int64)
+        return torch.cat(parts).contiguous(), sizes.cumsum(0).to(dev)
+    y, y_off = packed(target, gen)
+
+    def sub_geometry_metric(generated):
+        x, x_off = packed(sub_geometry(generated[0], generated[1], classes, engine).values, torch.Generator().manual_seed(int(seed) + 1))
+        out, _ = eng.mmd_1d_segments(x, x_off, y, y_off)
+        mmd = dict(zip(names, out[:, 0].tolist()))
+        result = {}
+        for kind, (_, mean_name) in zip(classes.symbols, _GEOMETRY_KINDS):
+            seen = [mmd[s] for s in kind if mmd[s] == mmd[s]]
+            result.update({s: mmd[s] for s in kind})
+            result[mean_name] = sum(seen) / len(seen) if seen else float("nan")
+        return result
+    return sub_geometry_metric

@@ -28,6 +28,9 @@
  *   ds_mces_records             MCES (Average): one myopic_mces ILP per pair   compute_metrics.py:235-243, run_lib.py:149
  *   ds_morgan_records /         Tanimoto / cosine similarity of radius-2 Morgan fingerprints   compute_metrics.py:246-253
  *   ds_morgan_similarity_records
+ *   ds_geometry_count_records / cal_bond_distance, cal_bond_angle, cal_dihedral_angle          evaluation/cal_geometry.py:14-216
+ *   ds_geometry_fill_records
+ *   ds_mmd_1d_segments          compute_mmd                                                    evaluation/mmd.py:6-63
  *   ds_gemm / ds_spec_*   SpecFormer.forward                  models/specformer.py:77-120,167-200,279-309,345-425,457-470
  *
  * Data layout ("packed-ragged", symmetric pair storage — DESIGN.md §3):
@@ -463,6 +466,88 @@ int ds_morgan_records(const uint8_t* rec, const int32_t* n, int64_t P, int32_t d
 int ds_morgan_similarity_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, const uint8_t* ref_rec, const int32_t* ref_n, int64_t M,
                                  const int64_t* ref_index, int32_t drop_h, int32_t radius, int32_t n_bits, int32_t* common, int32_t* n_prb,
                                  int32_t* n_ref, uint8_t* status, void* stream);
+
+/* Bond lengths, bond angles and dihedral angles of every record, sorted into caller-listed substructure classes: the sample lists behind the
+ * reference's "Metric-Align" line (evaluation/cal_geometry.py:14-216 on the unsanitised molecules of evaluation/stability.py:86-120, without
+ * RDKit).  One wave per record, an atom per lane; record table, counts, bonds, alignment and P are those of "record pairs" above.  A bond is
+ * an atom pair i < j below n whose bond byte o is > 0; N(i) are the atoms bonded to i; type_i is the type byte.  All n atoms count, hydrogens
+ * included; the formal charge plays no part; all fragments count.
+ *   Bonds      every bond i < j.  Value |x_i - x_j|, in the units of the record's positions.  Fields (type_i, o, type_j).
+ *   Angles     every centre c and unordered pair {a, b} of N(c), each once.  With u = x_a - x_c, v = x_b - x_c the value is
+ *              acos(clamp(u.v / sqrt(|u|^2 |v|^2), -1, 1)) in degrees, in [0, 180].  Fields (type_a, o_ac, type_c, o_cb, type_b).
+ *   Dihedrals  every bond i < j as the middle, every a in N(i) \ {j}, every b in N(j) \ {i}, each (a, i, j, b) once; a == b (a three-ring) is
+ *              included, as the reference's loops include it (cal_geometry.py:116-142).  With b1 = x_i - x_a, b2 = x_j - x_i, b3 = x_b - x_j,
+ *              n1 = b1 x b2, n2 = b2 x b3 the value is atan2(((n1 x n2).b2) / |b2|, n1.n2) in degrees; rounded to fp32, a value <= -180 becomes
+ *              +180, so the range is (-180, 180].  Fields (type_a, o_ai, type_i, o_ij, type_j, o_jb, type_b).
+ *   Classes    one int32 per class and at most DS_GEOM_MAX_CLASSES per kind: the fields in 4-bit groups, the first field in bits 0..3, the
+ *              next in bits 4..7 and so on (3, 5 or 7 groups; the bits above them 0).  An entry belongs to the first class of its kind's
+ *              table whose code equals its fields read forwards or backwards ("up to reversal"); an entry of no class is dropped.  A type
+ *              byte or a bond byte above 15 has no code and matches nothing.
+ *   Values     fp64 inside (positions widened to fp64, every product and sum rounded on its own: no fused multiply-add, so a value does not
+ *              depend on the direction an entry is read in), rounded once to fp32.  An entry of a listed class whose value is undefined or
+ *              not finite - coincident atoms, |u|^2 |v|^2 = 0, a zero n1 or n2 at a collinear dihedral, a non-finite coordinate - is not
+ *              emitted; `skipped` counts these.
+ *   Order      within a record: by lane - the lower atom i of a bond, the centre c of an angle, the lower middle atom i of a dihedral - then
+ *              lexicographic in (j), (a, b), (j, a, b); a lane's position comes from a wave prefix sum: the output is bit-identical run to run.
+ * The output size depends on the data (29 fully bonded atoms: 406 bonds, 10 962 angles, 295 974 dihedrals), so two entry points walk the same
+ * enumeration:
+ *   ds_geometry_count_records   counts [P,3] i32 (bonds, angles, dihedrals emitted by record p), skipped [P] i32
+ *   ds_geometry_fill_records    offsets [P,3] i64: where record p's entries of each kind start (the caller's exclusive prefix sum of counts
+ *                               over p); total_* : the length of each kind's output; per kind value [total] f32 and cls [total] u8 (the class's
+ *                               position in its table).  An index at or beyond `total` is never written.  A kind with total 0 takes NULLs.
+ * DS_ERR_ARG in the order of "record pairs": a class count outside [0, DS_GEOM_MAX_CLASSES] or a negative total with the sizes; then, for
+ * P > 0, a NULL table with a non-zero class count, a NULL output (counts, skipped; offsets, value / cls of a kind with total > 0).
+ * Two deviations from the reference's number:
+ *   - Angle multiplicity.  The reference counts an angle once per bond whose END atom is the centre (get_bond_pairs, cal_geometry.py:46-59):
+ *     0, 1 or 2 times, depending on the atom numbering and on RDKit's begin / end of each bond, which a record does not hold for the test
+ *     molecules.  Here every angle counts once, which makes the sample lists invariant under renaming atoms.
+ *   - Parity with RDKit's GetAngleDeg / GetDihedralDeg is unpinned: RDKit cannot be run where this project runs.  The global sign convention
+ *     of the dihedral cancels in the metric, because both sides go through the same kernel. */
+#define DS_GEOM_MAX_CLASSES 32
+int ds_geometry_count_records(const uint8_t* rec, const int32_t* n, int64_t P, const int32_t* bond_cls, int32_t n_bond_cls,
+                              const int32_t* angle_cls, int32_t n_angle_cls, const int32_t* dihedral_cls, int32_t n_dihedral_cls,
+                              int32_t* counts, int32_t* skipped, void* stream);
+int ds_geometry_fill_records(const uint8_t* rec, const int32_t* n, int64_t P, const int32_t* bond_cls, int32_t n_bond_cls,
+                             const int32_t* angle_cls, int32_t n_angle_cls, const int32_t* dihedral_cls, int32_t n_dihedral_cls,
+                             int64_t total_bond, int64_t total_angle, int64_t total_dihedral, const int64_t* offsets,
+                             float* bond_value, uint8_t* bond_class, float* angle_value, uint8_t* angle_class,
+                             float* dihedral_value, uint8_t* dihedral_class, void* stream);
+
+/* Maximum mean discrepancy of 1-D sample sets with a sum of Gaussian kernels, many (source, target) pairs per call: compute_mmd of
+ * evaluation/mmd.py:6-63.  Class c compares x[x_off[c] .. x_off[c+1]) (ns source samples) with y[y_off[c] .. y_off[c+1]) (nt target samples);
+ * z is their concatenation, N = ns + nt.
+ *   bandwidth = sum over all i, j of (z_i - z_j)^2 / (N^2 - N), or fix_sigma when that is not 0.  In one dimension the sum is 2 N times the
+ *               centred second moment, so bandwidth = 2 sum_i (z_i - mean)^2 / (N - 1), taken in fp64 (two passes: mean, then the moment);
+ *   bw_k      = bandwidth / kernel_mul^(kernel_num / 2, rounded down) * kernel_mul^k,  k = 0 .. kernel_num - 1;
+ *   XX = sum_k sum over i, j in the source (the diagonal included) of exp(-(x_i - x_j)^2 / bw_k) / ns^2, YY alike over the target / nt^2,
+ *   XY over source x target / (ns nt);  mmd = XX + YY - 2 XY.
+ * out [C,5] f64 = (mmd, XX, YY, XY, bandwidth); status [C] u8:
+ *   DS_MMD_OK       a bandwidth that is 0 (all samples identical) or not finite gives NaN in mmd, XX, YY and XY, as the reference does;
+ *   DS_MMD_EMPTY    ns = 0 or nt = 0: the five outputs are NaN;
+ *   DS_MMD_INVALID  offsets that decrease or leave [0, Nx] / [0, Ny], or more than DS_MMD_MAX_SAMPLES samples on a side: nothing of the class
+ *                   is read, the five outputs are NaN.
+ * Pairs are evaluated in fp32 (d = x_i - y_j, exp2(d^2 * (-log2 e / bw_k)) on v_exp_f32), summed per lane and bandwidth in fp32 over 64
+ * terms, then in fp64.  With kernel_mul = 2 and kernel_num <= 5 one exponential serves every bandwidth (exp(-d^2 / bw_k) is the square of
+ * exp(-d^2 / bw_(k+1)); at most four squarings, each of which doubles the relative error).
+ * XX and YY visit the upper triangle of DS_MMD_TILE x DS_MMD_TILE tiles and double the tiles off the diagonal.  Workgroup g of a class and term
+ * takes tiles g, g + DS_MMD_CHUNKS, ... and leaves one fp64 partial in the workspace; a last kernel adds the partials in index order: no
+ * floating-point atomics, bit-identical from run to run.  Stream-ordered, never synchronises.
+ * workspace: caller-owned device memory, 8-byte aligned, at least ds_mmd_1d_workspace_bytes(C) bytes (a pure host function), private layout.
+ * DS_ERR_ARG: C outside [0, DS_MMD_MAX_CLASSES], Nx or Ny outside [0, 2^31 - 1], kernel_num outside [1, DS_MMD_MAX_KERNELS], a kernel_mul that
+ * is not finite and > 0, a fix_sigma that is not finite and >= 0; then, for C > 0 (C = 0 launches nothing): a NULL x_off, y_off, out, status or
+ * workspace, a NULL x with Nx > 0 or y with Ny > 0, a workspace that is too small or not 8-byte aligned. */
+#define DS_MMD_TILE 256
+#define DS_MMD_CHUNKS 128
+#define DS_MMD_MAX_SAMPLES 1048576    /* 1 << 20 per side and class */
+#define DS_MMD_MAX_KERNELS 8
+#define DS_MMD_MAX_CLASSES 65535
+#define DS_MMD_OK 0
+#define DS_MMD_EMPTY 1
+#define DS_MMD_INVALID 2
+int ds_mmd_1d_workspace_bytes(int64_t n_classes, int64_t* bytes);
+int ds_mmd_1d_segments(const float* x, const int64_t* x_off, int64_t Nx, const float* y, const int64_t* y_off, int64_t Ny, int64_t n_classes,
+                       double kernel_mul, int32_t kernel_num, double fix_sigma, void* workspace, int64_t workspace_bytes, double* out,
+                       uint8_t* status, void* stream);
 
 /* SpecFormer pieces that are not plain GEMMs (specformer.py:385-425 residual-score attention; :119 LayerNorm).
  * qkv [B,L,3*heads*dk]; out [B,L,heads*dk]; scores: B*heads*L*L floats of caller-owned scratch that carries the

@@ -1,10 +1,10 @@
-// gfx950 kernels + C-ABI for the DMT denoiser evaluation, the ancestral update and post-processing.
+// gfx950 kernels + C-ABI for the DMT denoiser forward: prologue, init, the block kernels, the readouts; their launch sites, the
+// stage API, the two-stream schedule and the event profiler.  (Generic GEMMs: ds_gemm.hip; sampler side: ds_sampler.hip.)
 // Reference arithmetic being reproduced: models/dmt.py:306-412 and the files cited in include/diffspectra_hip.h.
 // Layout and fusion plan: DESIGN.md §3-§4.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include <atomic>
@@ -14,7 +14,7 @@
 
 #include "../../include/diffspectra_hip.h"
 #include "ds_device.h"
-#include "ds_train_common.h"   // DST_CHECK_LAUNCH: the one launch-status rule of the library
+#include "ds_host.h"
 
 #define ADAC DS_ADA_COLS
 // k-blocks of weights in flight per wave in the 16-block GEMMs (ds_device.h, wave_mma_h_deep); measured 4 / 8 / 12: 8
@@ -54,6 +54,10 @@ constexpr int DS_TWO_STREAM_MAX_PAIRS = 400000;   // ds_forward: side stream for
 #endif
 
 namespace {
+
+using dst::clear;
+using dst::record;
+using dst::wait;
 
 struct Ctx {  // by-value kernel argument: everything a stage needs
   ds_layout L;
@@ -1798,454 +1802,6 @@ __global__ void k_temb_finish(Ctx c, const float* __restrict__ tm3, int tm3_rows
   split_store1(reinterpret_cast<_Float16*>(c.ws.temb_silu) + b * 2048, 1024, (int)col, ds_silu(v));
 }
 
-// The per-step adaLN table GEMM ada[M, N] = temb_silu[M, 1024] * W + bias on the f16 matrix pipe with split operands
-// (ds_device.h).  A arrives pre-split from k_temb_finish (halves [M][2][K]); 64 x 128 output tile per workgroup, each wave 64
-// rows x 32 columns (a weight fragment feeds 6 MFMAs; 128-row tiles spilled their staging registers), A chunks of 64 k
-// double-buffered in LDS with the next chunk fetched into registers while the current one is multiplied.
-__global__ __launch_bounds__(256) void k_gemm_ada(const _Float16* __restrict__ A, const float* __restrict__ Wh, const float* __restrict__ bias,
-                                                  float* __restrict__ C, int ldc, int M, int K, int N) {
-  ds_fp16_saturate();
-  constexpr int T = 64, KC = 64, LDH = 2 * KC + 8, MT = T / 32;
-  __shared__ __attribute__((aligned(16))) _Float16 X[2][T][LDH];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int row0 = blockIdx.x * T;
-  const int col0 = (blockIdx.y * 4 + wave) * 32;
-  const bool active = col0 < N;
-  const int nchunks = K / KC;
-  // staging registers as four named values (an array here ended up in scratch memory)
-  float4 st0, st1, st2, st3;
-  const int srow = tid >> 4, spiece = tid & 15;               // thread's piece of rows srow, srow + 16, srow + 32, srow + 48
-  const size_t scol = (size_t)(spiece >> 3) * K + (spiece & 7) * 8;
-  auto fetch = [&](int kc) {
-    const _Float16* base = A + scol + kc * KC;
-    st0 = *reinterpret_cast<const float4*>(base + (size_t)min(row0 + srow, M - 1) * 2 * K);
-    st1 = *reinterpret_cast<const float4*>(base + (size_t)min(row0 + srow + 16, M - 1) * 2 * K);
-    st2 = *reinterpret_cast<const float4*>(base + (size_t)min(row0 + srow + 32, M - 1) * 2 * K);
-    st3 = *reinterpret_cast<const float4*>(base + (size_t)min(row0 + srow + 48, M - 1) * 2 * K);
-  };
-  auto stash = [&](int buf) {   // planes are adjacent in a tile row: piece 0..7 plane 0, 8..15 plane 1
-    *reinterpret_cast<float4*>(&X[buf][srow][spiece * 8]) = st0;
-    *reinterpret_cast<float4*>(&X[buf][srow + 16][spiece * 8]) = st1;
-    *reinterpret_cast<float4*>(&X[buf][srow + 32][spiece * 8]) = st2;
-    *reinterpret_cast<float4*>(&X[buf][srow + 48][spiece * 8]) = st3;
-  };
-  f32x16 acc[MT], lo[MT];
-  acc_zero<MT>(acc);
-  acc_zero<MT>(lo);
-  // weights: a chunk's four k-blocks sit in a register ring that is re-requested for the NEXT chunk as soon as this chunk's
-  // MFMAs are issued - their L2 round trip flies under the A staging and the barrier (ds_device.h, wave_mma_h_deep)
-  const WStreamH wsw = wstream_h(Wh, N, K, active ? col0 : 0);
-  WRingH<4> ring;
-  wring_h<4>(ring, wsw, 0);
-  fetch(0);
-  stash(0);
-  __syncthreads();
-  for (int kc = 0; kc < nchunks; ++kc) {
-    const int cur = kc & 1;
-    if (kc + 1 < nchunks) fetch(kc + 1);
-    if (active) wave_mma_h_deep<MT, false, 4, 4>(&X[cur][0][0], KC, wsw, ring, kc * 4, acc, lo, kc * 4);
-    if (kc + 1 < nchunks) { wring_h<4>(ring, wsw, kc * 4 + 4); stash(cur ^ 1); }
-    __syncthreads();
-  }
-  if (!active) return;
-  split_finish<MT>(acc, lo);
-  const int lane = tid & 63, r = lane & 31, hh = lane >> 5, col = col0 + r;
-  const float bcol = bias ? bias[col] : 0.0f;
-  const unsigned long long pw = reinterpret_cast<unsigned long long>(C + (size_t)row0 * ldc + col0);
-  const unsigned long long pu = (static_cast<unsigned long long>(__builtin_amdgcn_readfirstlane(static_cast<int>(pw >> 32))) << 32) |
-                                static_cast<unsigned int>(__builtin_amdgcn_readfirstlane(static_cast<int>(pw)));
-  const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(pu), 0, 0x7fffffff, 0x00020000);
-  const int voff = (4 * hh * ldc + r) * 4, rowb = ldc * 4;
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = m * 32 + (i & 3) + 8 * (i >> 2);
-      if (row0 + row + 4 * hh < M) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[m][i] + bcol), rc, voff, row * rowb, 0);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Generic GEMM (see header).  64x128 output tile per workgroup, A staged through LDS in K-chunks of 64.
-// Row-group addressing lets A be an unfold view (SpecFormer patches), C a slice of a [B, L, D] token buffer and
-// R a per-position table broadcast over molecules, without any host-side copy.
-struct GemmArgs {
-  const float* A; int64_t lda; int a_grp_rows; int64_t a_grp_stride;
-  const float* Wp; const float* bias;
-  float* C; int64_t ldc; int c_grp_rows; int64_t c_grp_stride;
-  int M, K, N, Npad;
-  const float* R; int64_t ldr; int r_grp_rows;
-  const float* cs; const float* csh;
-  int a_silu;
-};
-
-__device__ __forceinline__ size_t grp_off(int row, int64_t ld, int grp_rows, int64_t grp_stride) {
-  if (grp_rows <= 0) return (size_t)row * ld;
-  const int g = row / grp_rows;
-  return (size_t)g * grp_stride + (size_t)(row - g * grp_rows) * ld;
-}
-
-template <int ACT>
-__global__ __launch_bounds__(256) void k_gemm(GemmArgs g) {
-  constexpr int T = 64, KC = 64;
-  __shared__ __attribute__((aligned(16))) float X[T][KC + DS_LDP];
-  __shared__ size_t arow[T];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int row0 = blockIdx.x * T;
-  const int col0 = (blockIdx.y * 4 + wave) * 32;
-  const bool active = col0 < g.Npad;
-  if (tid < T) arow[tid] = (row0 + tid < g.M) ? grp_off(row0 + tid, g.lda, g.a_grp_rows, g.a_grp_stride) : 0;
-  f32x16 acc[2];
-  acc_zero<2>(acc);
-  const int Kpad = (g.K + 7) & ~7;
-  for (int k0 = 0; k0 < Kpad; k0 += KC) {
-    __syncthreads();
-    for (int idx = tid; idx < T * KC; idx += 256) {
-      const int row = idx >> 6, k = idx & 63;
-      float v = 0.0f;
-      if (row0 + row < g.M && k0 + k < g.K) {
-        v = g.A[arow[row] + k0 + k];
-        if (g.a_silu) v = ds_silu(v);
-      }
-      X[row][k] = v;
-    }
-    __syncthreads();
-    if (active) {
-      const int kgs = min(KC, Kpad - k0) >> 3;
-      wave_mma<2>(&X[0][0], KC + DS_LDP, g.Wp + (size_t)(k0 >> 3) * 2 * g.Npad * 4, g.Npad, col0, 0, kgs, acc);
-    }
-  }
-  if (!active) return;
-  acc_foreach<2>(acc, 0, col0, [&](int row, int col, float v) {
-    const int gr = row0 + row;
-    if (gr < g.M && col < g.N) {
-      if (g.bias) v += g.bias[col];
-      v = ds_act<ACT>(v);
-      if (g.R) v += g.R[(size_t)(g.r_grp_rows > 0 ? gr % g.r_grp_rows : gr) * g.ldr + col];
-      if (g.cs) v = v * g.cs[col] + g.csh[col];
-      g.C[grp_off(gr, g.ldc, g.c_grp_rows, g.c_grp_stride) + col] = v;
-    }
-  });
-}
-
-// ------------------------------------------------------------------------------------------------
-// Ancestral update, one workgroup per molecule (sampling.py:604-624; models/utils.py:38-45,67-106).
-__global__ __launch_bounds__(256) void k_sampler_step(ds_layout L, float c_x, float c_pred, float sigma, float temp,
-                                                      float* __restrict__ x, float* __restrict__ edge_x,
-                                                      const float* __restrict__ pred, const float* __restrict__ edge_pred,
-                                                      const float* __restrict__ raw_pos, const float* __restrict__ raw_feat,
-                                                      const float* __restrict__ raw_edge, float* __restrict__ x_mean,
-                                                      float* __restrict__ edge_mean) {
-  __shared__ __attribute__((aligned(16))) float mean[3];
-  __shared__ int dn[32];
-  const int m = blockIdx.x, tid = threadIdx.x;
-  const int n0 = L.node_off[m], n = L.node_off[m + 1] - n0;
-  if (n <= 0) return;
-  if (tid < n) dn[tid] = L.node_dense[n0 + tid];
-  __syncthreads();
-  if (tid < 3) {
-    float s = 0.0f;
-    for (int a = 0; a < n; ++a) s += raw_pos[(size_t)dn[a] * 3 + tid];
-    mean[tid] = s / (float)n;
-  }
-  __syncthreads();
-  for (int idx = tid; idx < n * 9; idx += 256) {
-    const int a = idx / 9, ch = idx - a * 9;
-    const size_t d = (size_t)dn[a];
-    const float nz = ch < 3 ? raw_pos[d * 3 + ch] - mean[ch] : raw_feat[d * 6 + (ch - 3)];
-    const float xm = c_x * x[d * 9 + ch] + c_pred * pred[d * 9 + ch];
-    x_mean[d * 9 + ch] = xm;
-    x[d * 9 + ch] = xm + (sigma * nz) * temp;
-  }
-  const int N = L.N;
-  for (int idx = tid; idx < n * n * 2; idx += 256) {
-    const int ch = idx & 1, ij = idx >> 1;
-    const int a = ij / n, b = ij - a * n;
-    if (a == b) continue;
-    const int la = dn[a] - m * N, lb = dn[b] - m * N;
-    const int hi = la > lb ? la : lb, lo = la > lb ? lb : la;
-    const float nz = raw_edge[(((size_t)m * 2 + ch) * N + hi) * N + lo];   // tril(-1) + transpose
-    const size_t o = ((size_t)dn[a] * N + lb) * 2 + ch;
-    const float em = c_x * edge_x[o] + c_pred * edge_pred[o];
-    edge_mean[o] = em;
-    edge_x[o] = em + (sigma * nz) * temp;
-  }
-}
-
-// ---- in-kernel noise: Philox4x32-10 (Salmon et al., SC'11; the generator torch/curand use) + Box-Muller ----
-struct Philox4 { unsigned int x, y, z, w; };
-__device__ __forceinline__ Philox4 philox4x32_10(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3,
-                                                 unsigned int k0, unsigned int k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned int hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned int hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const unsigned int n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return Philox4{c0, c1, c2, c3};
-}
-// u = (x + 0.5) / 2^32 in (0, 1]; (z0, z1) = sqrt(-2 ln u0) * (cos, sin)(2 pi u1)
-__device__ __forceinline__ float2 box_muller(unsigned int a, unsigned int b) {
-  const float u0 = __fmaf_rn((float)a, 2.3283064365386963e-10f, 1.1641532182693481e-10f);
-  const float u1 = __fmaf_rn((float)b, 2.3283064365386963e-10f, 1.1641532182693481e-10f);
-  const float r = sqrtf(-2.0f * logf(u0));
-  const float th = 6.283185307179586f * u1;
-  return make_float2(r * cosf(th), r * sinf(th));
-}
-__device__ __forceinline__ float4 philox_normal4(unsigned int elem, unsigned int draw, unsigned long long mol, unsigned int kind,
-                                                 unsigned long long seed) {
-  // counter words: (element, draw, mol_id low 32 bits, kind | mol_id high bits << 1)
-  const Philox4 p = philox4x32_10(elem, draw, (unsigned int)mol, kind | ((unsigned int)(mol >> 32) << 1),
-                                  (unsigned int)seed, (unsigned int)(seed >> 32));
-  const float2 a = box_muller(p.x, p.y), b = box_muller(p.z, p.w);
-  return make_float4(a.x, a.y, b.x, b.y);
-}
-
-// One workgroup per molecule.  MODE 0: initial noise (x, edge_x := noise; masked entries were zeroed by the caller's
-// memset).  MODE 1: ancestral update with in-kernel noise (the Philox twin of k_sampler_step).
-// MODE 2: as MODE 1 with (c_x, c_pred, sigma) and the draw index read from device memory (graph replay).
-template <int MODE>
-__global__ __launch_bounds__(256) void k_noise_step(ds_layout L, float c_x, float c_pred, float sigma, float temp,
-                                                    unsigned long long seed, unsigned int draw, const int64_t* __restrict__ mol_id,
-                                                    float* __restrict__ x, float* __restrict__ edge_x,
-                                                    const float* __restrict__ pred, const float* __restrict__ edge_pred,
-                                                    float* __restrict__ x_mean, float* __restrict__ edge_mean,
-                                                    const float* __restrict__ table, const int32_t* __restrict__ step) {
-  __shared__ __attribute__((aligned(16))) float nz[32][12];
-  __shared__ float mean[3];
-  __shared__ int dn[32];
-  const int m = blockIdx.x, tid = threadIdx.x;
-  const int n0 = L.node_off[m], n = L.node_off[m + 1] - n0;
-  if (n <= 0) return;
-  if (MODE == 2) {
-    const int i = *step;
-    c_x = table[4 * i]; c_pred = table[4 * i + 1]; sigma = table[4 * i + 2];
-    draw = (unsigned int)i + 1u;
-  }
-  const unsigned long long mol = (unsigned long long)mol_id[m];
-  if (tid < n) dn[tid] = L.node_dense[n0 + tid];
-  if (tid < n * 3) {
-    const int a = tid / 3, j = tid - a * 3;
-    const float4 v = philox_normal4((unsigned int)tid, draw, mol, 0u, seed);
-    reinterpret_cast<float4*>(&nz[a][4 * j])[0] = v;
-  }
-  __syncthreads();
-  if (tid < 3) {   // CoM projection of the position noise (models/utils.py:38-45,88-93), atoms in ascending order
-    float s = 0.0f;
-    for (int a = 0; a < n; ++a) s += nz[a][tid];
-    mean[tid] = s / (float)n;
-  }
-  __syncthreads();
-  for (int idx = tid; idx < n * 9; idx += 256) {
-    const int a = idx / 9, ch = idx - a * 9;
-    const size_t d = (size_t)dn[a];
-    const float v = ch < 3 ? nz[a][ch] - mean[ch] : nz[a][ch];
-    if (MODE == 0) {
-      x[d * 9 + ch] = v;
-    } else {   // MODE 1, 2
-      const float xm = c_x * x[d * 9 + ch] + c_pred * pred[d * 9 + ch];
-      x_mean[d * 9 + ch] = xm;
-      x[d * 9 + ch] = xm + (sigma * v) * temp;
-    }
-  }
-  const int N = L.N, P = n * (n - 1) / 2;
-  for (int p = tid; p < P; p += 256) {   // unordered pair lo < hi: p = hi(hi-1)/2 + lo, independent of n and of padding
-    int hi = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-    while (hi * (hi - 1) / 2 > p) --hi;
-    while ((hi + 1) * hi / 2 <= p) ++hi;
-    const int lo = p - hi * (hi - 1) / 2;
-    const float4 v = philox_normal4((unsigned int)p, draw, mol, 1u, seed);
-    const int la = dn[lo] - m * N, lb = dn[hi] - m * N;
-    const size_t o1 = ((size_t)dn[lo] * N + lb) * 2, o2 = ((size_t)dn[hi] * N + la) * 2;
-#pragma unroll
-    for (int ch = 0; ch < 2; ++ch) {
-      const float nzv = ch ? v.y : v.x;
-      if (MODE == 0) {
-        edge_x[o1 + ch] = nzv; edge_x[o2 + ch] = nzv;
-      } else {
-        const float em1 = c_x * edge_x[o1 + ch] + c_pred * edge_pred[o1 + ch];
-        const float em2 = c_x * edge_x[o2 + ch] + c_pred * edge_pred[o2 + ch];
-        edge_mean[o1 + ch] = em1; edge_mean[o2 + ch] = em2;
-        edge_x[o1 + ch] = em1 + (sigma * nzv) * temp; edge_x[o2 + ch] = em2 + (sigma * nzv) * temp;
-      }
-    }
-  }
-}
-
-// Opens a graph-replayable denoise iteration: ++*step, noise_level[b] = table[*step][3] (one workgroup).
-__global__ __launch_bounds__(256) void k_step_begin(const float* __restrict__ table, int n_steps, int32_t* __restrict__ step, int B,
-                                                    float* __restrict__ noise_level) {
-  __shared__ int cur;
-  if (threadIdx.x == 0) {
-    const int i = min(*step + 1, n_steps - 1);
-    *step = i;
-    cur = i;
-  }
-  __syncthreads();
-  const float nl = table[4 * cur + 3];
-  for (int b = threadIdx.x; b < B; b += 256) noise_level[b] = nl;
-}
-
-// post_process (sampling.py:53-97) with the inverse scaler of utils.py:88-103 (norms 1,4,4,1; centered).
-__global__ void k_post_process(ds_layout L, const float* __restrict__ xh, const float* __restrict__ edge_x,
-                               float* __restrict__ pos_out, int32_t* __restrict__ atom_type, int32_t* __restrict__ fc,
-                               float* __restrict__ edge_type) {
-  const int m = blockIdx.x, tid = threadIdx.x;
-  const int n0 = L.node_off[m], n = L.node_off[m + 1] - n0;
-  const int N = L.N;
-  for (int a = tid; a < n; a += blockDim.x) {
-    const size_t d = (size_t)L.node_dense[n0 + a];
-    const float* r = xh + d * 9;
-    pos_out[d * 3 + 0] = r[0] * 1.0f; pos_out[d * 3 + 1] = r[1] * 1.0f; pos_out[d * 3 + 2] = r[2] * 1.0f;
-    int best = 0;
-    float bv = (r[3] * 4.0f + 1.0f) / 2.0f;
-    for (int t = 1; t < 5; ++t) {
-      const float v = (r[3 + t] * 4.0f + 1.0f) / 2.0f;
-      if (v > bv) { bv = v; best = t; }
-    }
-    atom_type[d] = best;
-    fc[d] = (int32_t)rintf(r[8] * 4.0f);
-  }
-  for (int idx = tid; idx < n * n; idx += blockDim.x) {
-    const int a = idx / n, b = idx - a * n;
-    if (a == b) continue;
-    const int da = L.node_dense[n0 + a], lb = L.node_dense[n0 + b] - m * N;
-    const size_t o = (size_t)da * N + lb;
-    const float ex = (edge_x[o * 2 + 0] * 1.0f + 1.0f) / 2.0f;
-    const float t = ((edge_x[o * 2 + 1] * 1.0f + 1.0f) / 2.0f) * 3.0f;
-    float et = 0.0f;
-    if (t >= 2.5f) et = 3.0f; else if (t >= 1.5f) et = 2.0f; else if (t >= 0.5f) et = 1.0f;
-    edge_type[o] = (ex >= 0.5f ? 1.0f : 0.0f) * et;
-  }
-}
-
-// Stability check, one workgroup per molecule (evaluation/stability.py:40-73; tables of evaluation/bond_analyze.py:5-45 for
-// H, C, N, O, F; 0 = no such bond).  Thread a walks the other atoms of its molecule.
-__constant__ int c_bond1[5][5] = {{74, 109, 101, 96, 92}, {109, 154, 147, 143, 135}, {101, 147, 145, 140, 136},
-                                  {96, 143, 140, 148, 142}, {92, 135, 136, 142, 142}};
-__constant__ int c_bond2[5][5] = {{0, 0, 0, 0, 0}, {0, 134, 129, 120, 0}, {0, 129, 125, 121, 0}, {0, 120, 121, 121, 0}, {0, 0, 0, 0, 0}};
-__constant__ int c_bond3[5][5] = {{0, 0, 0, 0, 0}, {0, 120, 116, 113, 0}, {0, 116, 110, 0, 0}, {0, 113, 0, 0, 0}, {0, 0, 0, 0, 0}};
-__constant__ int c_valence[5] = {1, 4, 3, 2, 1};
-__global__ __launch_bounds__(64) void k_check_stability(ds_layout L, const float* __restrict__ pos, const int32_t* __restrict__ atom_type,
-                                                        int32_t* __restrict__ bond_order, int32_t* __restrict__ nr_stable,
-                                                        int32_t* __restrict__ mol_stable) {
-  __shared__ float px[32], py[32], pz[32];
-  __shared__ int ty[32], dn[32];
-  const int m = blockIdx.x, a = threadIdx.x;
-  const int n0 = L.node_off[m], n = L.node_off[m + 1] - n0;
-  if (n <= 0) { if (a == 0) { nr_stable[m] = 0; mol_stable[m] = 1; } return; }
-  if (a < n) {
-    const int d = L.node_dense[n0 + a];
-    dn[a] = d;
-    px[a] = pos[(size_t)d * 3]; py[a] = pos[(size_t)d * 3 + 1]; pz[a] = pos[(size_t)d * 3 + 2];
-    ty[a] = min(max(atom_type[d], 0), 4);
-  }
-  __syncthreads();
-  int ok = 0;
-  if (a < n) {
-    int bonds = 0;
-    const int ta = ty[a], N = L.N;
-    for (int b = 0; b < n; ++b) {
-      if (b == a) continue;
-      const float dx = px[a] - px[b], dy = py[a] - py[b], dz = pz[a] - pz[b];
-      const float d = __fmul_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), 100.0f);
-      const int tb = ty[b];
-      int order = 0;
-      if (d < (float)(c_bond1[ta][tb] + 10)) {
-        order = 1;
-        if (c_bond2[ta][tb] != 0 && d < (float)(c_bond2[ta][tb] + 5)) {
-          order = 2;
-          if (c_bond3[ta][tb] != 0 && d < (float)(c_bond3[ta][tb] + 3)) order = 3;
-        }
-      }
-      bonds += order;
-      if (bond_order) bond_order[(size_t)dn[a] * N + (dn[b] - m * N)] = order;
-    }
-    ok = bonds == c_valence[ta] ? 1 : 0;
-  }
-  const int cnt = __popcll(__ballot(ok != 0));
-  if (a == 0) { nr_stable[m] = cnt; mol_stable[m] = cnt == n ? 1 : 0; }
-}
-
-// SpecFormer residual-score attention (specformer.py:401-424): one workgroup per (molecule, head) and up to 1024 queries - one
-// query per thread, K / V of the head staged in LDS once for all of them.
-// qkv [B, L, 3*heads*dk] (q | k | v); scores [B, heads, L, L] holds prev on entry (if has_prev) and the new
-// pre-softmax scores on exit; out [B, L, heads*dk].
-__global__ __launch_bounds__(1024) void k_spec_attention(const float* __restrict__ qkv, float* __restrict__ scores,
-                                                       float* __restrict__ out, int B, int L, int heads, float scale,
-                                                       int has_prev) {
-  constexpr int DK = 8;
-  extern __shared__ __attribute__((aligned(16))) float kv[];   // K [L][8] then V [L][8]
-  const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * blockDim.x, tid = threadIdx.x;
-  const int D = heads * DK;
-  float* Ks = kv;
-  float* Vs = kv + (size_t)L * DK;
-  for (int idx = tid; idx < L * DK; idx += blockDim.x) {
-    const int j = idx / DK, d = idx - j * DK;
-    const float* base = qkv + ((size_t)b * L + j) * 3 * D + h * DK + d;
-    Ks[idx] = base[D];
-    Vs[idx] = base[2 * D];
-  }
-  __syncthreads();
-  const int i = q0 + tid;
-  if (i >= L) return;
-  float q[DK];
-  for (int d = 0; d < DK; ++d) q[d] = qkv[((size_t)b * L + i) * 3 * D + h * DK + d];
-  // residual scores are kept TRANSPOSED, [b][h][key j][query i]: the lanes of a wave are consecutive queries, so every
-  // access below is one contiguous 256-byte segment (query-major rows made each lane touch its own cache line)
-  float* scol = scores + ((size_t)b * heads + h) * L * L + i;
-  // One pass with a running maximum (the scores are written for the next layer and never read back here: the [B, heads, L, L]
-  // tensor is this kernel's whole HBM bill - 4.1 GB per launch with the two-pass form).  Blocks of 8 keys: one rescale per block.
-  float mx = -INFINITY, den = 0.0f, o[DK];
-  for (int d = 0; d < DK; ++d) o[d] = 0.0f;
-  for (int j0 = 0; j0 < L; j0 += 8) {
-    float sv[8];
-    float bm = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int j = min(j0 + u, L - 1);
-      float s = 0.0f;
-#pragma unroll
-      for (int d = 0; d < DK; ++d) s += q[d] * Ks[j * DK + d];
-      s *= scale;
-      if (has_prev) s += scol[(size_t)j * L];
-      sv[u] = s;
-      if (j0 + u < L) { scol[(size_t)j * L] = s; bm = fmaxf(bm, s); }
-    }
-    const float nm = fmaxf(mx, bm), r = expf(mx - nm);   // mx = -inf on the first block: r = 0
-    den *= r;
-#pragma unroll
-    for (int d = 0; d < DK; ++d) o[d] *= r;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (j0 + u < L) {
-        const float p = expf(sv[u] - nm);
-        den += p;
-#pragma unroll
-        for (int d = 0; d < DK; ++d) o[d] += p * Vs[(j0 + u) * DK + d];
-      }
-    }
-    mx = nm;
-  }
-  for (int d = 0; d < DK; ++d) out[((size_t)b * L + i) * D + h * DK + d] = o[d] / den;
-}
-
-__global__ void k_layernorm_affine(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bt,
-                                   float* __restrict__ y, int rows, int cols, float eps) {
-  const int row = blockIdx.x, lane = threadIdx.x;   // one wave per row
-  if (row >= rows) return;
-  const float* xr = x + (size_t)row * cols;
-  float s = 0.0f;
-  for (int k = lane; k < cols; k += 64) s += xr[k];
-  const float mean = wave_sum(s) / (float)cols;
-  float v = 0.0f;
-  for (int k = lane; k < cols; k += 64) { const float d = xr[k] - mean; v += d * d; }
-  const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)cols + eps);
-  for (int k = lane; k < cols; k += 64) y[(size_t)row * cols + k] = (xr[k] - mean) * rstd * g[k] + bt[k];
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 bool make_ctx(Ctx& c, const ds_weights* w, const ds_layout* L, const ds_workspace* ws) {
   if (!w || !L || !ws || !w->base || !w->off_dev) return false;
@@ -2255,12 +1811,6 @@ bool make_ctx(Ctx& c, const ds_weights* w, const ds_layout* L, const ds_workspac
   return true;
 }
 
-// What the entry points that take a bare layout require of it (their kernels stage <= 32 node indices of a molecule in LDS)
-inline bool layout_ok(const ds_layout* L) { return L && L->B > 0 && L->max_n <= DS_MAX_ATOMS && L->max_n <= L->N; }
-
-inline bool clear(void* p, size_t bytes, hipStream_t s) { return hipMemsetAsync(p, 0, bytes, s) == hipSuccess; }
-inline bool record(hipEvent_t ev, hipStream_t s) { return hipEventRecord(ev, s) == hipSuccess; }
-inline bool wait(hipStream_t s, hipEvent_t ev) { return hipStreamWaitEvent(s, ev, 0) == hipSuccess; }
 constexpr int MAX_DEVICES = 16;   // per-device host state (CU counts, side streams) is kept for devices below this index
 
 // Compute units of the current device (256 on a full MI355X; fewer in a partitioned mode): the persistent
@@ -2273,102 +1823,6 @@ inline int device_cus() {
   if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
   cus[dev].store(n, std::memory_order_relaxed);
   return n;
-}
-
-// Large plain GEMMs (the per-step adaLN table [B,1024] x [1024,19744] is 6 % of a denoising step): 128x128 output tile,
-// MT = 4 (each B fragment feeds 16 MFMAs), A double-buffered in LDS with the next K-chunk fetched into registers while
-// the current one is multiplied (one barrier per chunk), the next chunk's first B group requested ahead of that barrier.
-// Requires contiguous rows (no row groups), K % 64 == 0 and 16-byte aligned rows.
-template <int ACT>
-__global__ __launch_bounds__(256, 2) void k_gemm_big(GemmArgs g) {
-  constexpr int T = 128, KC = 64, LD = KC + DS_LDP;
-  __shared__ __attribute__((aligned(16))) float X[2][T][LD];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int row0 = blockIdx.x * T;
-  const int col0 = (blockIdx.y * 4 + wave) * 32;
-  const bool active = col0 < g.Npad;
-  const int nchunks = g.K / KC;
-  float4 st[8];
-  auto fetch = [&](int kc) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int idx = tid + u * 256, row = idx >> 4, k4 = idx & 15;
-      const size_t gr = (size_t)min(row0 + row, g.M - 1);
-      st[u] = reinterpret_cast<const float4*>(g.A + gr * g.lda + (size_t)kc * KC)[k4];
-    }
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int idx = tid + u * 256, row = idx >> 4, k4 = idx & 15;
-      float4 v = st[u];
-      if (g.a_silu) { v.x = ds_silu(v.x); v.y = ds_silu(v.y); v.z = ds_silu(v.z); v.w = ds_silu(v.w); }
-      if (row0 + row >= g.M) v = make_float4(0, 0, 0, 0);
-      reinterpret_cast<float4*>(&X[buf][row][0])[k4] = v;
-    }
-  };
-  f32x16 acc[4];
-  acc_zero<4>(acc);
-  fetch(0);
-  stash(0);
-  BFrag bf = bfrag_load(g.Wp, g.Npad, active ? col0 : 0, 0, 8);
-  __syncthreads();
-  for (int kc = 0; kc < nchunks; ++kc) {
-    const int cur = kc & 1;
-    if (kc + 1 < nchunks) fetch(kc + 1);
-    const float* wp = g.Wp + (size_t)(kc * (KC / 8)) * 2 * g.Npad * 4;
-    if (active) wave_mma<4>(&X[cur][0][0], LD, wp, g.Npad, col0, 0, KC / 8, acc, 0, &bf);
-    if (kc + 1 < nchunks) {
-      stash(cur ^ 1);
-      bf = bfrag_load(wp + (size_t)(KC / 8) * 2 * g.Npad * 4, g.Npad, active ? col0 : 0, 0, 8);
-    }
-    __syncthreads();
-  }
-  if (!active) return;
-  {   // epilogue: the lane's column constants are fetched once, rows go out as buffer stores with SGPR row offsets
-    const int lane = tid & 63, r = lane & 31, hh = lane >> 5, col = col0 + r;
-    const bool colok = col < g.N;
-    const float bcol = (g.bias && colok) ? g.bias[col] : 0.0f;
-    const float csc = (g.cs && colok) ? g.cs[col] : 1.0f, csh = (g.cs && colok) ? g.csh[col] : 0.0f;
-    const unsigned long long pw = reinterpret_cast<unsigned long long>(g.C + (size_t)row0 * g.ldc + col0);
-    const unsigned long long pu = (static_cast<unsigned long long>(__builtin_amdgcn_readfirstlane(static_cast<int>(pw >> 32))) << 32) |
-                                  static_cast<unsigned int>(__builtin_amdgcn_readfirstlane(static_cast<int>(pw)));
-    const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(pu), 0, 0x7fffffff, 0x00020000);
-    const int voff = (4 * hh * g.ldc + r) * 4, rowb = g.ldc * 4;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = m * 32 + (i & 3) + 8 * (i >> 2), gr = row0 + row + 4 * hh;
-        if (gr < g.M && colok) {
-          float v = ds_act<ACT>(acc[m][i] + bcol);
-          if (g.R) v += g.R[(size_t)(g.r_grp_rows > 0 ? gr % g.r_grp_rows : gr) * g.ldr + col];
-          if (g.cs) v = v * csc + csh;
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rc, voff, row * rowb, 0);
-        }
-      }
-  }
-}
-
-int gemm_dispatch(const GemmArgs& g, int act, hipStream_t s) {
-  if (!g.A || !g.Wp || !g.C || g.M <= 0 || g.K <= 0 || g.N <= 0 || (g.cs && !g.csh)) return DS_ERR_ARG;
-  const bool big = g.M >= 512 && g.a_grp_rows <= 0 && g.c_grp_rows <= 0 && g.K % 64 == 0 && g.lda % 4 == 0 &&
-                   (reinterpret_cast<uintptr_t>(g.A) & 15) == 0;
-  using Kernel = void (*)(GemmArgs);   // one instantiation per activation code: 128-row tiles when big, else 64-row tiles
-  static constexpr Kernel tile128[4] = {k_gemm_big<0>, k_gemm_big<1>, k_gemm_big<2>, k_gemm_big<3>};
-  static constexpr Kernel tile64[4] = {k_gemm<0>, k_gemm<1>, k_gemm<2>, k_gemm<3>};
-  if (act < 0 || act > 3) return DS_ERR_ARG;
-  const int rows = big ? 128 : 64;
-  hipLaunchKernelGGL(big ? tile128[act] : tile64[act], dim3((g.M + rows - 1) / rows, (g.Npad + 127) / 128), dim3(256), 0, s, g);
-  return DST_CHECK_LAUNCH();
-}
-
-int gemm_simple(const float* A, int64_t lda, const float* Wp, const float* bias, float* C, int64_t ldc, int M, int K, int N,
-                int act, int a_silu, hipStream_t s) {
-  GemmArgs g{};
-  g.A = A; g.lda = lda; g.Wp = Wp; g.bias = bias; g.C = C; g.ldc = ldc; g.M = M; g.K = K; g.N = N;
-  g.Npad = (N + 31) & ~31; g.a_silu = a_silu;
-  return gemm_dispatch(g, act, s);
 }
 
 // ---- optional HIP-event timing of one block-stage kernel (bench.py's live roofline measurement) ----
@@ -2440,26 +1894,6 @@ void ds_struct_sizes(int64_t* out) {
   out[3] = sizeof(ds_gemm_args);
 }
 
-int ds_gemm(const ds_gemm_args* a, void* stream) {
-  if (!a) return DS_ERR_ARG;
-  GemmArgs g{};
-  g.A = a->A; g.lda = a->lda; g.a_grp_rows = a->a_grp_rows; g.a_grp_stride = a->a_grp_stride;
-  g.Wp = a->Wp; g.bias = a->bias;
-  g.C = a->C; g.ldc = a->ldc; g.c_grp_rows = a->c_grp_rows; g.c_grp_stride = a->c_grp_stride;
-  g.M = a->M; g.K = a->K; g.N = a->N; g.Npad = (a->N + 31) & ~31;
-  g.R = a->R; g.ldr = a->ldr; g.r_grp_rows = a->r_grp_rows;
-  g.cs = a->col_scale; g.csh = a->col_shift; g.a_silu = a->a_silu;
-  return gemm_dispatch(g, a->act, (hipStream_t)stream);
-}
-
-int ds_gemm_split(const void* A_split, const float* W_split, const float* bias, float* C, int64_t ldc, int32_t M, int32_t K,
-                  int32_t N, void* stream) {
-  if (!A_split || !W_split || !C || M <= 0 || K <= 0 || N <= 0 || K % 64 != 0 || N % 32 != 0 || ldc < N) return DS_ERR_ARG;
-  hipLaunchKernelGGL(k_gemm_ada, dim3((M + 63) / 64, (N + 127) / 128), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<const _Float16*>(A_split), W_split, bias, C, (int)ldc, M, K, N);
-  return DST_CHECK_LAUNCH();
-}
-
 int ds_stage_time(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* noise_level, const float* ctx_emb,
                   void* stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -2469,10 +1903,15 @@ int ds_stage_time(const ds_weights* w, const ds_layout* L, ds_workspace* ws, con
   const int64_t* off = w->off + DS_NBLOCKS * DS_W_BLOCK_SLOTS;
   hipLaunchKernelGGL(k_time_feat, dim3((B + 63) / 64), dim3(64), 0, s, c, noise_level);
   // time_mlp: Linear(17,1024) -> GELU -> Linear(1024,1024)  (dmt.py:252-257); tmid reuses ws->tmid, output in ws->ada scratch
-  int st = gemm_simple(ws->tfeat, 24, w->base + off[DS_GW_TM1_W], w->base + off[DS_GW_TM1_B], ws->tmid, 1024, B, 24, 1024, 2, 0, s);
+  ds_gemm_args g{};
+  g.A = ws->tfeat; g.lda = 24; g.Wp = w->base + off[DS_GW_TM1_W]; g.bias = w->base + off[DS_GW_TM1_B];
+  g.C = ws->tmid; g.ldc = 1024; g.M = B; g.K = 24; g.N = 1024; g.act = 2;
+  int st = ds_gemm(&g, stream);
   if (st) return st;
   float* tm3 = ws->ada;   // [B,1024] scratch inside the (larger) ada buffer, consumed before ada is produced
-  st = gemm_simple(ws->tmid, 1024, w->base + off[DS_GW_TM3_W], w->base + off[DS_GW_TM3_B], tm3, 1024, B, 1024, 1024, 0, 0, s);
+  g.A = ws->tmid; g.lda = 1024; g.Wp = w->base + off[DS_GW_TM3_W]; g.bias = w->base + off[DS_GW_TM3_B];
+  g.C = tm3; g.K = 1024; g.act = 0;
+  st = ds_gemm(&g, stream);
   if (st) return st;
   const size_t tot = (size_t)B * 1024;
   hipLaunchKernelGGL(k_temb_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, c, (const float*)tm3, B, ctx_emb);
@@ -2610,82 +2049,6 @@ int ds_forward(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const 
   return ds_stage_readout(w, L, ws, out_xh, out_edge, stream);
 }
 
-int ds_sampler_step(const ds_layout* L, float c_x, float c_pred, float sigma, float temperature, float* x, float* edge_x,
-                     const float* pred, const float* edge_pred, const float* raw_pos, const float* raw_feat,
-                     const float* raw_edge, float* x_mean, float* edge_mean, void* stream) {
-  if (!layout_ok(L) || !x || !edge_x || !pred || !edge_pred || !raw_pos || !raw_feat || !raw_edge || !x_mean || !edge_mean) return DS_ERR_ARG;
-  hipLaunchKernelGGL(k_sampler_step, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, c_x, c_pred, sigma, temperature, x,
-                     edge_x, pred, edge_pred, raw_pos, raw_feat, raw_edge, x_mean, edge_mean);
-  return DST_CHECK_LAUNCH();
-}
-
-int ds_initial_noise(const ds_layout* L, uint64_t seed, const int64_t* mol_id, float* x, float* edge_x, void* stream) {
-  if (!layout_ok(L) || !mol_id || !x || !edge_x) return DS_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t nb = (size_t)L->B * L->N;
-  if (!clear(x, nb * 9 * sizeof(float), s) || !clear(edge_x, nb * L->N * 2 * sizeof(float), s)) return DS_ERR_LAUNCH;
-  hipLaunchKernelGGL(k_noise_step<0>, dim3(L->B), dim3(256), 0, s, *L, 0.0f, 0.0f, 0.0f, 0.0f, (unsigned long long)seed, 0u, mol_id,
-                     x, edge_x, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr,
-                     (const float*)nullptr, (const int32_t*)nullptr);
-  return DST_CHECK_LAUNCH();
-}
-
-int ds_sampler_step_philox(const ds_layout* L, float c_x, float c_pred, float sigma, float temperature, uint64_t seed, int32_t step,
-                           const int64_t* mol_id, float* x, float* edge_x, const float* pred, const float* edge_pred,
-                           float* x_mean, float* edge_mean, void* stream) {
-  if (!layout_ok(L) || !mol_id || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean || step < 0) return DS_ERR_ARG;
-  hipLaunchKernelGGL(k_noise_step<1>, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, c_x, c_pred, sigma, temperature,
-                     (unsigned long long)seed, (unsigned int)step + 1u, mol_id, x, edge_x, pred, edge_pred, x_mean, edge_mean,
-                     (const float*)nullptr, (const int32_t*)nullptr);
-  return DST_CHECK_LAUNCH();
-}
-
-int ds_step_begin(const float* table, int32_t n_steps, int32_t* step, int32_t B, float* noise_level, void* stream) {
-  if (!table || !step || !noise_level || B <= 0 || n_steps <= 0) return DS_ERR_ARG;
-  hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(256), 0, (hipStream_t)stream, table, n_steps, step, B, noise_level);
-  return DST_CHECK_LAUNCH();
-}
-
-int ds_sampler_step_philox_dev(const ds_layout* L, const float* table, const int32_t* step, float temperature, uint64_t seed,
-                               const int64_t* mol_id, float* x, float* edge_x, const float* pred, const float* edge_pred,
-                               float* x_mean, float* edge_mean, void* stream) {
-  if (!layout_ok(L) || !table || !step || !mol_id || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean) return DS_ERR_ARG;
-  hipLaunchKernelGGL(k_noise_step<2>, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, 0.0f, 0.0f, 0.0f, temperature,
-                     (unsigned long long)seed, 0u, mol_id, x, edge_x, pred, edge_pred, x_mean, edge_mean, table, step);
-  return DST_CHECK_LAUNCH();
-}
-
-int ds_post_process(const ds_layout* L, const float* xh, const float* edge_x, float* pos_out, int32_t* atom_type, int32_t* fc,
-                    float* edge_type, void* stream) {
-  if (!layout_ok(L) || !xh || !edge_x || !pos_out || !atom_type || !fc || !edge_type) return DS_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t nb = (size_t)L->B * L->N;
-  if (!clear(pos_out, nb * 3 * sizeof(float), s) || !clear(atom_type, nb * sizeof(int32_t), s) || !clear(fc, nb * sizeof(int32_t), s) ||
-      !clear(edge_type, nb * L->N * sizeof(float), s))
-    return DS_ERR_LAUNCH;
-  hipLaunchKernelGGL(k_post_process, dim3(L->B), dim3(128), 0, s, *L, xh, edge_x, pos_out, atom_type, fc, edge_type);
-  return DST_CHECK_LAUNCH();
-}
-
-int ds_check_stability(const ds_layout* L, const float* pos, const int32_t* atom_type, int32_t* bond_order, int32_t* nr_stable,
-                       int32_t* mol_stable, void* stream) {
-  if (!layout_ok(L) || !pos || !atom_type || !nr_stable || !mol_stable) return DS_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (bond_order && !clear(bond_order, (size_t)L->B * L->N * L->N * sizeof(int32_t), s)) return DS_ERR_LAUNCH;
-  hipLaunchKernelGGL(k_check_stability, dim3(L->B), dim3(64), 0, s, *L, pos, atom_type, bond_order, nr_stable, mol_stable);
-  return DST_CHECK_LAUNCH();
-}
-
-int ds_spec_attention(const float* qkv, float* scores, float* out, int B, int L, int heads, int dk, float scale, int has_prev,
-                      void* stream) {
-  if (!qkv || !scores || !out || dk != 8 || B <= 0 || L <= 0) return DS_ERR_ARG;
-  const int threads = min(1024, (L + 63) / 64 * 64);
-  dim3 grid((L + threads - 1) / threads, heads, B);
-  hipLaunchKernelGGL(k_spec_attention, grid, dim3(threads), (size_t)L * 8 * 2 * sizeof(float), (hipStream_t)stream, qkv, scores, out, B,
-                     L, heads, scale, has_prev);
-  return DST_CHECK_LAUNCH();
-}
-
 int ds_profile_config(int kernel, int every, int max_samples) {
   for (auto& e : g_prof.pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   g_prof.pool.clear();
@@ -2711,13 +2074,6 @@ int ds_profile_read(double* total_ms, int64_t* samples) {
   *total_ms = tot; *samples = (int64_t)g_prof.used;
   g_prof.used = 0; g_prof.seen = 0;
   return DS_OK;
-}
-
-int ds_layernorm_affine(const float* x, const float* gamma, const float* beta, float* y, int rows, int cols, float eps,
-                        void* stream) {
-  if (!x || !gamma || !beta || !y || rows <= 0 || cols <= 0) return DS_ERR_ARG;
-  hipLaunchKernelGGL(k_layernorm_affine, dim3(rows), dim3(64), 0, (hipStream_t)stream, x, gamma, beta, y, rows, cols, eps);
-  return DST_CHECK_LAUNCH();
 }
 
 }  // extern "C"

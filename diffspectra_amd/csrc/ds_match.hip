@@ -8,7 +8,7 @@
 #include "../../include/diffspectra_hip.h"
 #include "ds_records.h"
 #include "ds_svd3.h"
-#include "ds_train_common.h"   // DST_CHECK_LAUNCH
+#include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 

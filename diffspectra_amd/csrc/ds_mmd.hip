@@ -19,7 +19,7 @@
 #include <cmath>
 
 #include "../../include/diffspectra_hip.h"
-#include "ds_train_common.h"   // DST_CHECK_LAUNCH
+#include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 

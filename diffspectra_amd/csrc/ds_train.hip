@@ -13,19 +13,12 @@
 #include "ds_svd3.h"
 #include "ds_train_common.h"
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
 namespace {
 
 #ifndef DST_SPEC_SLICES
 #define DST_SPEC_SLICES 2   // workgroups per (batch, head) in the SpecFormer attention kernels: each stages K and V of the head once
 #endif
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __device__ __forceinline__ int pair_index(int n, int lo, int hi) { return lo * (2 * n - lo - 1) / 2 + (hi - lo - 1); }
 
 // ------------------------------------------------------------------------------------------------------------------ colsum / sumsq
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(256) void k_sumsq_partial(const float* __restrict__
   } else {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += x[i] * x[i];
   }
-  s = wave_sum(s);
+  s = group_sum<64>(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -174,15 +167,6 @@ __global__ void k_dropout(const float* __restrict__ x, float* __restrict__ y, in
 // Round 3 ran these with 256 threads and 4-byte accesses: one workgroup per CU at four waves left the memory pipe idle (60 - 190 us
 // per launch on the directed rows; the rows of 256 molecules are 250 MB).
 constexpr int MOLW = 16;                                   // waves per molecule workgroup
-typedef float f4_t __attribute__((ext_vector_type(4)));
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {      // sum over aligned groups of G lanes
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ f4_t ld4(const float* p) { return *reinterpret_cast<const f4_t*>(p); }
-__device__ __forceinline__ void st4(float* p, f4_t v) { *reinterpret_cast<f4_t*>(p) = v; }
 
 template <int C>
 __global__ __launch_bounds__(1024) void k_lnmod_fwd(const float* __restrict__ x, const int32_t* __restrict__ seg_off, int seg_mul,
@@ -192,13 +176,13 @@ __global__ __launch_bounds__(1024) void k_lnmod_fwd(const float* __restrict__ x,
   const int m = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int sub = lane / LPR, cl = (lane % LPR) * 4;
   const int r0 = seg_off[m] * seg_mul, r1 = seg_off[m + 1] * seg_mul;
-  const f4_t sh = ld4(ada + (int64_t)m * ada_ld + shift_off + cl), sc = ld4(ada + (int64_t)m * ada_ld + scale_off + cl);
+  const f32x4_t sh = ld4(ada + (int64_t)m * ada_ld + shift_off + cl), sc = ld4(ada + (int64_t)m * ada_ld + scale_off + cl);
   // gridDim.y workgroups share a molecule's rows (interleaved passes): one workgroup per molecule lasts as long as the largest molecule
   // (812 directed rows against a mean of ~310), four per molecule let the dispatcher even the CUs out
   for (int r = r0 + (blockIdx.y * MOLW + wave) * RPW + sub; r < r1; r += gridDim.y * MOLW * RPW) {
-    const f4_t v = ld4(x + (int64_t)r * C + cl);
+    const f32x4_t v = ld4(x + (int64_t)r * C + cl);
     const float mean = group_sum<LPR>((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / C);
-    const f4_t d = v - mean;
+    const f32x4_t d = v - mean;
     const float rstd = 1.0f / sqrtf(group_sum<LPR>((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * (1.0f / C) + 1e-6f);
     st4(y + (int64_t)r * C + cl, (d * rstd) * (1.0f + sc) + sh);
     if (lane % LPR == 0) { stats[(int64_t)r * 2] = mean; stats[(int64_t)r * 2 + 1] = rstd; }
@@ -215,29 +199,29 @@ __global__ __launch_bounds__(1024) void k_lnmod_bwd(const float* __restrict__ dy
   const int m = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int sub = lane / LPR, cl = (lane % LPR) * 4;
   const int r0 = seg_off[m] * seg_mul, r1 = seg_off[m + 1] * seg_mul;
-  const f4_t sc1 = ld4(ada + (int64_t)m * ada_ld + scale_off + cl) + 1.0f;
-  f4_t dsh = {0.0f, 0.0f, 0.0f, 0.0f}, dsc = {0.0f, 0.0f, 0.0f, 0.0f};
+  const f32x4_t sc1 = ld4(ada + (int64_t)m * ada_ld + scale_off + cl) + 1.0f;
+  f32x4_t dsh = {0.0f, 0.0f, 0.0f, 0.0f}, dsc = {0.0f, 0.0f, 0.0f, 0.0f};
   // the next row's operands are requested (from a clamped row index) before this row is worked on: one row per wave and pass is a chain of
   // dependent round trips otherwise
   const int rstep = gridDim.y * MOLW * RPW;
   int r = r0 + (blockIdx.y * MOLW + wave) * RPW + sub;
   int rc = min(r, r1 - 1);
   float mean_n = 0.0f, rstd_n = 0.0f;
-  f4_t g_n = {0.0f, 0.0f, 0.0f, 0.0f}, x_n = g_n;
+  f32x4_t g_n = {0.0f, 0.0f, 0.0f, 0.0f}, x_n = g_n;
   if (r1 > r0) { mean_n = stats[(int64_t)rc * 2]; rstd_n = stats[(int64_t)rc * 2 + 1]; g_n = ld4(dy + (int64_t)rc * C + cl); x_n = ld4(x + (int64_t)rc * C + cl); }
   for (; r < r1; r += rstep) {
     const float mean = mean_n, rstd = rstd_n;
-    const f4_t g = g_n;
-    const f4_t xh = (x_n - mean) * rstd;
+    const f32x4_t g = g_n;
+    const f32x4_t xh = (x_n - mean) * rstd;
     rc = min(r + rstep, r1 - 1);
     mean_n = stats[(int64_t)rc * 2]; rstd_n = stats[(int64_t)rc * 2 + 1];
     g_n = ld4(dy + (int64_t)rc * C + cl); x_n = ld4(x + (int64_t)rc * C + cl);
     dsh += g;
     dsc += g * xh;
-    const f4_t gg = g * sc1, gx = gg * xh;
+    const f32x4_t gg = g * sc1, gx = gg * xh;
     const float m1 = group_sum<LPR>((gg[0] + gg[1]) + (gg[2] + gg[3])) * (1.0f / C);
     const float m2 = group_sum<LPR>((gx[0] + gx[1]) + (gx[2] + gx[3])) * (1.0f / C);
-    f4_t d = rstd * (gg - m1 - xh * m2);
+    f32x4_t d = rstd * (gg - m1 - xh * m2);
     float* o = dx + (int64_t)r * C + cl;
     if (accumulate) d += ld4(o);
     st4(o, d);
@@ -273,7 +257,7 @@ __global__ __launch_bounds__(1024) void k_gate_add_fwd(const float* __restrict__
   const int m = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int sub = lane / LPR, cl = (lane % LPR) * 4;
   const int r0 = seg_off[m] * seg_mul, r1 = seg_off[m + 1] * seg_mul;
-  const f4_t g = ld4(ada + (int64_t)m * ada_ld + gate_off + cl);
+  const f32x4_t g = ld4(ada + (int64_t)m * ada_ld + gate_off + cl);
   for (int r = r0 + wave * RPW + sub; r < r1; r += MOLW * RPW) {
     const int64_t i = (int64_t)r * C + cl;
     st4(out + i, ld4(r_ + i) + g * ld4(z + i));
@@ -291,15 +275,15 @@ __global__ __launch_bounds__(1024) void k_gate_add_bwd(const float* __restrict__
   const int m = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int sub = lane / LPR, cl = (lane % LPR) * 4;
   const int r0 = seg_off[m] * seg_mul, r1 = seg_off[m + 1] * seg_mul;
-  const f4_t g = ld4(ada + (int64_t)m * ada_ld + gate_off + cl);
+  const f32x4_t g = ld4(ada + (int64_t)m * ada_ld + gate_off + cl);
   const unsigned int thr = dst::dropout_threshold(drop_p);
   const float keep_scale = 1.0f / (1.0f - drop_p);
-  f4_t dg = {0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4_t dg = {0.0f, 0.0f, 0.0f, 0.0f};
   for (int r = r0 + wave * RPW + sub; r < r1; r += MOLW * RPW) {
     const int64_t i = (int64_t)r * C + cl;
-    const f4_t d = ld4(dout + i);
+    const f32x4_t d = ld4(dout + i);
     dg += d * ld4(z + i);
-    f4_t o = g * d;
+    f32x4_t o = g * d;
     if (drop_p > 0.0f) {
       unsigned int w[4];
       dst::dropout_block(drop_seed, drop_stream, i >> 2, w);
@@ -397,7 +381,7 @@ __global__ __launch_bounds__(GEOM_NT) void k_geom_bwd(dst_layout L, const float*
       dmu += t * u / sd;
       dsd += t * (u * u - 1.0f) / sd;
     }
-    const float dx = wave_sum(dxl);
+    const float dx = group_sum<64>(dxl);
     if (lane == 0) {
       const float d2 = d2s[p0 + p];
       a_dsc += dx * d2;
@@ -495,7 +479,7 @@ __global__ __launch_bounds__(1024) void k_attn_fwd(dst_layout L, const float* __
   // aggregation onto the target, ascending source order
   for (int it = threadIdx.x; it < n * 64; it += blockDim.x) {      // four columns (one head) per thread
     const int t = it >> 6, col = (it & 63) * 4, hd = col >> 4;
-    f4_t s = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4_t s = {0.0f, 0.0f, 0.0f, 0.0f};
     // sources below and above the target as two branch-free ranges (same ascending order): a `continue` in the loop kept the compiler
     // from putting more than one iteration's loads in flight
 #pragma unroll 4
@@ -550,7 +534,7 @@ __global__ __launch_bounds__(1024) void k_attn_bwd(dst_layout L, const float* __
     float s = 0.0f;
 #pragma unroll
     for (int c = 0; c < 16; c += 4) {
-      const f4_t a = ld4(go + c) * ld4(v + c) * ld4(e + c);
+      const f32x4_t a = ld4(go + c) * ld4(v + c) * ld4(e + c);
       s += a[0]; s += a[1]; s += a[2]; s += a[3];
     }
     dl[it] = s;
@@ -574,7 +558,7 @@ __global__ __launch_bounds__(1024) void k_attn_bwd(dst_layout L, const float* __
   // node-side gradients: thread per (node, four columns of the 768-wide q|k|v row) - 16-byte accesses, a quarter of the index arithmetic
   for (int it = tid0; it < n * 192; it += tstep) {
     const int i = it / 192, col = (it % 192) * 4;
-    f4_t s = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4_t s = {0.0f, 0.0f, 0.0f, 0.0f};
     if (col < 252) {                                   // dq[i]: i is the target (252 = 4 * 63: a quad never straddles the padding)
       int hd[4];
 #pragma unroll
@@ -583,13 +567,13 @@ __global__ __launch_bounds__(1024) void k_attn_bwd(dst_layout L, const float* __
 #pragma unroll 4
       for (int j = 0; j < i; ++j) {
         const int p = pair_index(n, j, i), d = 2 * p;  // source j -> target i
-        const f4_t w = {dl[d * 16 + hd[0]], dl[d * 16 + hd[1]], dl[d * 16 + hd[2]], dl[d * 16 + hd[3]]};
+        const f32x4_t w = {dl[d * 16 + hd[0]], dl[d * 16 + hd[1]], dl[d * 16 + hd[2]], dl[d * 16 + hd[3]]};
         s += w * ld4(qkv + (int64_t)(n0 + j) * 768 + 256 + col) * ld4(te0 + (int64_t)(p0 + p) * ldt + col);
       }
 #pragma unroll 4
       for (int j = i + 1; j < n; ++j) {
         const int p = pair_index(n, i, j), d = 2 * p + 1;
-        const f4_t w = {dl[d * 16 + hd[0]], dl[d * 16 + hd[1]], dl[d * 16 + hd[2]], dl[d * 16 + hd[3]]};
+        const f32x4_t w = {dl[d * 16 + hd[0]], dl[d * 16 + hd[1]], dl[d * 16 + hd[2]], dl[d * 16 + hd[3]]};
         s += w * ld4(qkv + (int64_t)(n0 + j) * 768 + 256 + col) * ld4(te0 + (int64_t)(p0 + p) * ldt + col);
       }
       s *= 0.25f;
@@ -601,13 +585,13 @@ __global__ __launch_bounds__(1024) void k_attn_bwd(dst_layout L, const float* __
 #pragma unroll 4
       for (int t = 0; t < i; ++t) {
         const int p = pair_index(n, t, i), d = 2 * p + 1;   // source i -> target t
-        const f4_t w = {dl[d * 16 + hd[0]], dl[d * 16 + hd[1]], dl[d * 16 + hd[2]], dl[d * 16 + hd[3]]};
+        const f32x4_t w = {dl[d * 16 + hd[0]], dl[d * 16 + hd[1]], dl[d * 16 + hd[2]], dl[d * 16 + hd[3]]};
         s += w * ld4(qkv + (int64_t)(n0 + t) * 768 + c) * ld4(te0 + (int64_t)(p0 + p) * ldt + c);
       }
 #pragma unroll 4
       for (int t = i + 1; t < n; ++t) {
         const int p = pair_index(n, i, t), d = 2 * p;
-        const f4_t w = {dl[d * 16 + hd[0]], dl[d * 16 + hd[1]], dl[d * 16 + hd[2]], dl[d * 16 + hd[3]]};
+        const f32x4_t w = {dl[d * 16 + hd[0]], dl[d * 16 + hd[1]], dl[d * 16 + hd[2]], dl[d * 16 + hd[3]]};
         s += w * ld4(qkv + (int64_t)(n0 + t) * 768 + c) * ld4(te0 + (int64_t)(p0 + p) * ldt + c);
       }
       s *= 0.25f;
@@ -632,19 +616,19 @@ __global__ __launch_bounds__(1024) void k_attn_bwd(dst_layout L, const float* __
     const int a = pa[p], b = pb[p];
     {
       const int hd = col >> 4;
-      const f4_t va = ld4(qkv + (int64_t)(n0 + a) * 768 + 512 + col), vb = ld4(qkv + (int64_t)(n0 + b) * 768 + 512 + col);
-      f4_t g1 = ld4(dout + (int64_t)(n0 + b) * 256 + col) * va * al[(2 * p) * 16 + hd] + ld4(dout + (int64_t)(n0 + a) * 256 + col) * vb * al[(2 * p + 1) * 16 + hd];
+      const f32x4_t va = ld4(qkv + (int64_t)(n0 + a) * 768 + 512 + col), vb = ld4(qkv + (int64_t)(n0 + b) * 768 + 512 + col);
+      f32x4_t g1 = ld4(dout + (int64_t)(n0 + b) * 256 + col) * va * al[(2 * p) * 16 + hd] + ld4(dout + (int64_t)(n0 + a) * 256 + col) * vb * al[(2 * p + 1) * 16 + hd];
       if (te_tanh) {                                   // te1 = tanh(lin_edge1 e): hand back the gradient in front of the tanh (1 - te^2)
-        const f4_t t1 = ld4(te1 + (int64_t)(p0 + p) * ldt + col);
+        const f32x4_t t1 = ld4(te1 + (int64_t)(p0 + p) * ldt + col);
         g1 = g1 * (1.0f - t1 * t1);
       }
       st4(dte1 + (int64_t)(p0 + p) * ldt + col, g1);
     }
-    f4_t g0 = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4_t g0 = {0.0f, 0.0f, 0.0f, 0.0f};
     if (col < 252) {
-      const f4_t qa = ld4(qkv + (int64_t)(n0 + a) * 768 + col), qb = ld4(qkv + (int64_t)(n0 + b) * 768 + col);
-      const f4_t ka = ld4(qkv + (int64_t)(n0 + a) * 768 + 256 + col), kb = ld4(qkv + (int64_t)(n0 + b) * 768 + 256 + col);
-      f4_t w0, w1;
+      const f32x4_t qa = ld4(qkv + (int64_t)(n0 + a) * 768 + col), qb = ld4(qkv + (int64_t)(n0 + b) * 768 + col);
+      const f32x4_t ka = ld4(qkv + (int64_t)(n0 + a) * 768 + 256 + col), kb = ld4(qkv + (int64_t)(n0 + b) * 768 + 256 + col);
+      f32x4_t w0, w1;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int hd = (col + e) / 18 + 2;
@@ -653,7 +637,7 @@ __global__ __launch_bounds__(1024) void k_attn_bwd(dst_layout L, const float* __
       }
       g0 = 0.25f * (w0 * qb * ka + w1 * qa * kb);
       if (te_tanh) {
-        const f4_t t0 = ld4(te0 + (int64_t)(p0 + p) * ldt + col);
+        const f32x4_t t0 = ld4(te0 + (int64_t)(p0 + p) * ldt + col);
         g0 = g0 * (1.0f - t0 * t0);
       }
     }
@@ -711,7 +695,7 @@ __global__ __launch_bounds__(256) void k_zbuild_bwd(dst_layout L, const float* _
   }
   for (int it = threadIdx.x + 256 * blockIdx.y; it < n * 128; it += 256 * gridDim.y) {
     const int i = it >> 7, c = (it & 127) * 4, as_col = c >> 8, cc = c & 255;
-    f4_t s = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4_t s = {0.0f, 0.0f, 0.0f, 0.0f};
     // directed edge with row = i (as_col 0) or col = i (as_col 1): dir 0 has row = lo, dir 1 has row = hi.  Partners below and above i as
     // two branch-free ranges in ascending order (several loads in flight)
 #pragma unroll 4
@@ -811,7 +795,7 @@ __global__ __launch_bounds__(256) void k_coord_bwd(dst_layout L, const float* __
     }
     dcd[d][0] = ex; dcd[d][1] = ey; dcd[d][2] = ez;
   }
-  dscale = wave_sum(dscale);
+  dscale = group_sum<64>(dscale);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dscale;
   __syncthreads();
   if (threadIdx.x == 0) dscale_part[m] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -850,7 +834,7 @@ __global__ __launch_bounds__(64) void k_time_feat_bwd(const float* __restrict__ 
     const float fr = ((x * w[i]) * 2.0f) * 3.14159265358979323846f;
     s += (df[(int64_t)b * 17 + 1 + i] * cosf(fr) - df[(int64_t)b * 17 + 9 + i] * sinf(fr)) * (x * 2.0f * 3.14159265358979323846f);
   }
-  s = wave_sum(s);
+  s = group_sum<64>(s);
   if (threadIdx.x == 0) dw[i] = s;
 }
 
@@ -879,7 +863,7 @@ __global__ __launch_bounds__(256) void k_loss(dst_layout L, const float* __restr
     le += d * d;                                            // every pair sits in two cells of the dense edge tensor
     dedge[(int64_t)p0 * 2 + it] = w * w_edge * 2.0f * d;    // 2 cells * (1/2 channel mean) * 2 d
   }
-  lp = wave_sum(lp); lt = wave_sum(lt); le = wave_sum(le);
+  lp = group_sum<64>(lp); lt = group_sum<64>(lt); le = group_sum<64>(le);
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = lp; red[1][threadIdx.x >> 6] = lt; red[2][threadIdx.x >> 6] = le; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1139,7 +1123,7 @@ __global__ __launch_bounds__(256) void k_spec_attn_fwd(const float* __restrict__
       ev[j] = (lane + 64 * j < Lq) ? expf(sv[j] - mx) : 0.0f;
       den += ev[j];
     }
-    den = wave_sum(den);
+    den = group_sum<64>(den);
     float acc[DK];
 #pragma unroll
     for (int c = 0; c < DK; ++c) acc[c] = 0.0f;
@@ -1153,7 +1137,7 @@ __global__ __launch_bounds__(256) void k_spec_attn_fwd(const float* __restrict__
       }
     }
 #pragma unroll
-    for (int c = 0; c < DK; ++c) acc[c] = wave_sum(acc[c]);
+    for (int c = 0; c < DK; ++c) acc[c] = group_sum<64>(acc[c]);
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j)
       if (lane + 64 * j < Lq) scores[rowbase + lane + 64 * j] = sv[j];
@@ -1226,7 +1210,7 @@ __global__ __launch_bounds__(256) void k_spec_attn_bwd_q(const float* __restrict
         dot += av[j] * da;
       }
     }
-    dot = wave_sum(dot);
+    dot = group_sum<64>(dot);
     float dq[DK];
 #pragma unroll
     for (int c = 0; c < DK; ++c) dq[c] = 0.0f;
@@ -1241,7 +1225,7 @@ __global__ __launch_bounds__(256) void k_spec_attn_bwd_q(const float* __restrict
       }
     }
 #pragma unroll
-    for (int c = 0; c < DK; ++c) dq[c] = wave_sum(dq[c]) * scale;
+    for (int c = 0; c < DK; ++c) dq[c] = group_sum<64>(dq[c]) * scale;
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j)
       if (lane + 64 * j < Lq) dscores[rowbase + lane + 64 * j] = av[j];
@@ -1301,10 +1285,10 @@ __global__ __launch_bounds__(64) void k_ln_affine_fwd(const float* __restrict__ 
   const int r = blockIdx.x, lane = threadIdx.x;
   float s = 0.0f;
   for (int c = lane; c < C; c += 64) s += x[(int64_t)r * C + c];
-  const float mean = wave_sum(s) / (float)C;
+  const float mean = group_sum<64>(s) / (float)C;
   float q = 0.0f;
   for (int c = lane; c < C; c += 64) { const float d = x[(int64_t)r * C + c] - mean; q += d * d; }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
+  const float rstd = 1.0f / sqrtf(group_sum<64>(q) / (float)C + eps);
   for (int c = lane; c < C; c += 64) y[(int64_t)r * C + c] = (x[(int64_t)r * C + c] - mean) * rstd * gamma[c] + beta[c];
   if (lane == 0) { stats[(int64_t)r * 2] = mean; stats[(int64_t)r * 2 + 1] = rstd; }
 }
@@ -1318,7 +1302,7 @@ __global__ __launch_bounds__(64) void k_ln_affine_bwd(const float* __restrict__ 
     s1 += g;
     s2 += g * xh;
   }
-  const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+  const float m1 = group_sum<64>(s1) / (float)C, m2 = group_sum<64>(s2) / (float)C;
   for (int c = lane; c < C; c += 64) {
     const float g = dy[(int64_t)r * C + c] * gamma[c], xh = (x[(int64_t)r * C + c] - mean) * rstd;
     dx[(int64_t)r * C + c] = rstd * (g - m1 - xh * m2);

@@ -21,11 +21,9 @@
 
 #include "../../include/diffspectra_hip.h"
 #include "../../include/diffspectra_train.h"
+#include "ds_device.h"   // acc_row
 #include "ds_train_common.h"
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8_t __attribute__((ext_vector_type(8)));
 
 namespace {
@@ -90,7 +88,6 @@ __device__ __forceinline__ bf16x8_t acc8(const f32x16_t& x, int s) {            
   for (int j = 0; j < 8; ++j) r[j] = (__bf16)x[8 * s + j];
   return r;
 }
-__device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }   // row of register i in a 32 x 32 accumulator
 // position of (row r of a 32-row tile, column c) in a fragment table [tile][s][hh][C][8]: the k-permuted A operand of a product over r
 __device__ __forceinline__ int perm_index(int tile, int r, int c, int C) {
   const int s = r >> 4, r16 = r & 15, hh = (r16 >> 2) & 1, j = (r16 >> 3) * 4 + (r16 & 3);

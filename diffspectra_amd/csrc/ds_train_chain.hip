@@ -30,11 +30,6 @@
 #include "../../include/diffspectra_train.h"
 #include "ds_train_common.h"
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int CH_NW = 4, CH_NT = CH_NW * 64;      // waves per workgroup
@@ -48,15 +43,9 @@ struct ChainLds {
   __bf16 eb[32][LD_S];           // [e_out | features], bf16: A operand of input_lin's edge part and of the read-out slice
 };
 
-__device__ __forceinline__ f4_t ld4(const float* p) { return *reinterpret_cast<const f4_t*>(p); }
-__device__ __forceinline__ void st4(float* p, f4_t v) { *reinterpret_cast<f4_t*>(p) = v; }
-__device__ __forceinline__ float sum16(float v) {          // sum over aligned groups of 16 lanes
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// The same sum with DPP row rotations (a DPP row IS 16 lanes): no LDS-crossbar traffic.  The fused BACKWARD kernels use this form: with
-// ds_bpermute shuffles in flight next to their LDS reads, two executions inside a step differed in single rows (profiles/HISTORY.md, round 5).
+// The sum over aligned groups of 16 lanes (group_sum<16>) with DPP row rotations (a DPP row IS 16 lanes): no LDS-crossbar traffic.
+// The fused BACKWARD kernels use this form: with ds_bpermute shuffles in flight next to their LDS reads, two executions inside a
+// step differed in single rows (profiles/HISTORY.md, round 5).
 __device__ __forceinline__ float sum16_dpp(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));   // row_ror:8
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));   // row_ror:4
@@ -72,7 +61,7 @@ __device__ __forceinline__ float sum64_dpp(float v) {
   const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
   return ((r0 + r1) + r2) + r3;
 }
-__device__ __forceinline__ bf16x4_t to_bf4(f4_t v) {
+__device__ __forceinline__ bf16x4_t to_bf4(f32x4_t v) {
   bf16x4_t r;
 #pragma unroll
   for (int j = 0; j < 4; ++j) r[j] = (__bf16)v[j];
@@ -159,10 +148,10 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_chain_fwd(dst_layout L, dst_p
   const float keep_scale = a.drop_p > 0.0f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
   const int sub = lane >> 4, cl = (lane & 15) * 4;          // row layout of stage 1: a row = 16 lanes x float4
   const int er = lane >> 3, ec = (lane & 7) * 4;            // row layout of the GEMM epilogues: a 32-column chunk row = 8 lanes x float4
-  const f4_t bias = ld4(a.n2e_bias + cl);
+  const f32x4_t bias = ld4(a.n2e_bias + cl);
   const float b3c = a.b3[wave * 32 + (lane & 31)], b4c = a.b4[(wave & 1) * 32 + (lane & 31)];
   // edge_gate_mlp of the rows this lane finishes in the ff_linear4 epilogue (waves 0, 1: row it * 8 + er, columns wave * 32 + ec ..)
-  f4_t g2c[4];
+  f32x4_t g2c[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it)
     g2c[it] = ld4(a.ada + (int64_t)pair_mol[min(t0 + it * 8 + er, Pp - 1)] * a.ada_ld + a.gate2_off + (wave & 1) * 32 + ec);
@@ -176,7 +165,7 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_chain_fwd(dst_layout L, dst_p
       const int gp = min(t0 + (2 * wave + q) * 4 + sub, Pp - 1);
       ia[q] = pair_a[gp]; ib[q] = pair_b[gp]; im[q] = pair_mol[gp];
     }
-    f4_t ua[2], ub[2], ev[2], fv[2], g1v[2], shv[2], scv[2];
+    f32x4_t ua[2], ub[2], ev[2], fv[2], g1v[2], shv[2], scv[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int64_t gp = min(t0 + (2 * wave + q) * 4 + sub, Pp - 1);
@@ -192,13 +181,13 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_chain_fwd(dst_layout L, dst_p
     for (int q = 0; q < 2; ++q) {
       const int row = (2 * wave + q) * 4 + sub;
       const int64_t gp = min(t0 + row, Pp - 1);
-      const f4_t he = (ua[q] + ub[q]) + bias;
-      const f4_t x = ev[q] + g1v[q] * he;
-      f4_t ft = fv[q];
-      const float mean = sum16((x[0] + x[1]) + (x[2] + x[3])) * (1.0f / 64.0f);
-      const f4_t d = x - mean;
-      const float rstd = 1.0f / sqrtf(sum16((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * (1.0f / 64.0f) + 1e-6f);
-      f4_t y = (d * rstd) * (1.0f + scv[q]) + shv[q];
+      const f32x4_t he = (ua[q] + ub[q]) + bias;
+      const f32x4_t x = ev[q] + g1v[q] * he;
+      f32x4_t ft = fv[q];
+      const float mean = group_sum<16>((x[0] + x[1]) + (x[2] + x[3])) * (1.0f / 64.0f);
+      const f32x4_t d = x - mean;
+      const float rstd = 1.0f / sqrtf(group_sum<16>((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * (1.0f / 64.0f) + 1e-6f);
+      f32x4_t y = (d * rstd) * (1.0f + scv[q]) + shv[q];
       if (row < valid) {
         if (a.he) st4(a.he + gp * 64 + cl, he);
         if (a.xe1) st4(a.xe1 + gp * 64 + cl, x);
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_chain_fwd(dst_layout L, dst_p
         if (a.ye1) st4(a.ye1 + gp * 64 + cl, y);
         if (a.X2) st4(a.X2 + gp * 128 + 64 + cl, ft);
       } else {
-        y = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        y = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
         ft = y;
       }
       st4(&w.yf[row][cl], y);
@@ -233,8 +222,8 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_chain_fwd(dst_layout L, dst_p
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er, col = ch * 32 + ec;
       const int64_t gr = g0 + row;
-      const f4_t v = ld4(&stage[row][ec]);
-      f4_t sv;
+      const f32x4_t v = ld4(&stage[row][ec]);
+      f32x4_t sv;
 #pragma unroll
       for (int e = 0; e < 4; ++e) sv[e] = fast_silu(v[e]);
       if (a.drop_p > 0.0f) {
@@ -247,7 +236,7 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_chain_fwd(dst_layout L, dst_p
         if (a.f3) st4(a.f3 + gr * 128 + col, v);
         if (a.s3) st4(a.s3 + gr * 128 + col, sv);
       } else {
-        sv = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        sv = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       }
       *reinterpret_cast<bf16x4_t*>(&w.sb[row][col]) = to_bf4(sv);
     }
@@ -267,20 +256,20 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_chain_fwd(dst_layout L, dst_p
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er, col = ch * 32 + ec;
       const int64_t gr = g0 + row;
-      f4_t v = ld4(&stage[row][ec]);
+      f32x4_t v = ld4(&stage[row][ec]);
       if (a.drop_p > 0.0f) {
         unsigned int c[4];
         dst::dropout_block(a.seed, a.stream4, (gr * 64 + col) >> 2, c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = c[e] >= thr ? v[e] * keep_scale : 0.0f;
       }
-      f4_t eo = ld4(&w.yf[row][col]) + g2c[it] * v;
+      f32x4_t eo = ld4(&w.yf[row][col]) + g2c[it] * v;
       if (row < valid) {
         if (a.f4) st4(a.f4 + gr * 64 + col, v);
         st4(a.e_out + gr * 64 + col, eo);
         if (a.X2) st4(a.X2 + gr * 128 + col, eo);
       } else {
-        eo = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        eo = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       }
       *reinterpret_cast<bf16x4_t*>(&w.eb[row][col]) = to_bf4(eo);
     }
@@ -308,7 +297,7 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_chain_fwd(dst_layout L, dst_p
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er;
       const int64_t gr = g0 + row;
-      const f4_t v = ld4(&stage[row][ec]);
+      const f32x4_t v = ld4(&stage[row][ec]);
       if (row < valid) {
         if (!ro) st4(a.ed + gr * 256 + ch * 32 + ec, v);
         else if (ec < 16) st4(a.ro + gr * 16 + ec, v);
@@ -363,7 +352,7 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_front_fwd(dst_layout L, dst_p
     const int gp = min(t0 + (2 * wave + q) * 4 + sub, Pp - 1);
     ia[q] = pair_a[gp]; ib[q] = pair_b[gp]; im[q] = pair_mol[gp];
   }
-  f4_t evs[2], shs[2], scs[2];
+  f32x4_t evs[2], shs[2], scs[2];
   float d2v[2], dscv[2], dshv[2];
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -384,14 +373,14 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_front_fwd(dst_layout L, dst_p
     const int64_t gp = min(t0 + row, Pp - 1);
     const float d2 = d2v[q];
     const float x = d2 * (dscv[q] + 1.0f) + dshv[q];
-    f4_t ft;
+    f32x4_t ft;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float u = (x - mu[j]) / sd[j];
       ft[j] = expf(-0.5f * (u * u)) / nrm[j];
     }
     if (cl == 0) ft[0] = x;
-    f4_t ev = evs[q];
+    f32x4_t ev = evs[q];
     if (row < valid) {
       st4(a.X1 + gp * 128 + cl, ft);
       st4(a.X1 + gp * 128 + 64 + cl, ev);
@@ -400,7 +389,7 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_front_fwd(dst_layout L, dst_p
         if (a.d2) a.d2[gp] = d2;
       }
     } else {
-      ft = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+      ft = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       ev = ft;
     }
     *reinterpret_cast<bf16x4_t*>(&w.xb[row][cl]) = to_bf4(ft);
@@ -423,17 +412,17 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_front_fwd(dst_layout L, dst_p
   for (int q = 0; q < 2; ++q) {
     const int row = (2 * wave + q) * 4 + sub;
     const int64_t gp = g0 + row;
-    const f4_t x = ld4(&w.ef[row][cl]);
-    const float mean = sum16((x[0] + x[1]) + (x[2] + x[3])) * (1.0f / 64.0f);
-    const f4_t d = x - mean;
-    const float rstd = 1.0f / sqrtf(sum16((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * (1.0f / 64.0f) + 1e-6f);
-    f4_t y = (d * rstd) * (1.0f + scs[q]) + shs[q];
+    const f32x4_t x = ld4(&w.ef[row][cl]);
+    const float mean = group_sum<16>((x[0] + x[1]) + (x[2] + x[3])) * (1.0f / 64.0f);
+    const f32x4_t d = x - mean;
+    const float rstd = 1.0f / sqrtf(group_sum<16>((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * (1.0f / 64.0f) + 1e-6f);
+    f32x4_t y = (d * rstd) * (1.0f + scs[q]) + shs[q];
     if (row < valid) {
       if (a.e1) st4(a.e1 + gp * 64 + cl, x);
       if (a.st && (lane & 15) == 0) { a.st[gp * 2] = mean; a.st[gp * 2 + 1] = rstd; }
       if (a.en) st4(a.en + gp * 64 + cl, y);
     } else {
-      y = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+      y = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
     }
     *reinterpret_cast<bf16x4_t*>(&w.nb[row][cl]) = to_bf4(y);
   }
@@ -452,7 +441,7 @@ __global__ __launch_bounds__(CH_NT, 3) void k_pair_front_fwd(dst_layout L, dst_p
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er;
-      f4_t v = ld4(&stage[row][ec]);
+      f32x4_t v = ld4(&stage[row][ec]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = fast_tanh(v[e]);
       if (row < valid) st4(a.te + (g0 + row) * 512 + ch * 32 + ec, v);
@@ -508,39 +497,39 @@ __global__ __launch_bounds__(CH_NT, 3) void k_dir_chain_fwd(dst_layout L, dst_di
     const float* pc = a.ac + (int64_t)cb_[q] * 512 + 256 + 4 * j16;
     const float* pe = a.ed + (int64_t)pl * 256 + 4 * j16;
     const float* adm = a.ada + (int64_t)im[q] * a.ada_ld + 4 * j16;
-    f4_t xr[4], xc[4], xe[4], shq[4], scq[4];
+    f32x4_t xr[4], xc[4], xe[4], shq[4], scq[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       xr[u] = ld4(pr + 64 * u); xc[u] = ld4(pc + 64 * u); xe[u] = ld4(pe + 64 * u);
       shq[u] = ld4(adm + a.shift_off + 64 * u); scq[u] = ld4(adm + a.scale_off + 64 * u);
     }
     __builtin_amdgcn_sched_barrier(0);                       // the pass's loads above its first store
-    f4_t x[4];
+    f32x4_t x[4];
     float s1 = 0.0f;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       x[u] = (xr[u] + xc[u]) + xe[u];
       s1 += (x[u][0] + x[u][1]) + (x[u][2] + x[u][3]);
     }
-    const float mean = sum16(s1) * (1.0f / 256.0f);
+    const float mean = group_sum<16>(s1) * (1.0f / 256.0f);
     float s2 = 0.0f;
-    f4_t dv[4];
+    f32x4_t dv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       dv[u] = x[u] - mean;
       s2 += (dv[u][0] * dv[u][0] + dv[u][1] * dv[u][1]) + (dv[u][2] * dv[u][2] + dv[u][3] * dv[u][3]);
     }
-    const float rstd = 1.0f / sqrtf(sum16(s2) * (1.0f / 256.0f) + 1e-6f);
+    const float rstd = 1.0f / sqrtf(group_sum<16>(s2) * (1.0f / 256.0f) + 1e-6f);
     const bool live = row < valid;
     if (live && a.st && j16 == 0) { a.st[gd * 2] = mean; a.st[gd * 2 + 1] = rstd; }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      f4_t y = (dv[u] * rstd) * (1.0f + scq[u]) + shq[u];
+      f32x4_t y = (dv[u] * rstd) * (1.0f + scq[u]) + shq[u];
       if (live) {
         if (a.zz) st4(a.zz + gd * 256 + 64 * u + 4 * j16, x[u]);
         if (a.zn) st4(a.zn + gd * 256 + 64 * u + 4 * j16, y);
       } else {
-        y = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        y = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       }
       *reinterpret_cast<bf16x4_t*>(&w.zb[row][64 * u + 4 * j16]) = to_bf4(y);
     }
@@ -575,15 +564,15 @@ __global__ __launch_bounds__(CH_NT, 3) void k_dir_chain_fwd(dst_layout L, dst_di
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er, col = ch * 32 + ec;
       const int64_t gr = g0 + row;
-      const f4_t v = ld4(&stage[row][ec]);
-      f4_t sv;
+      const f32x4_t v = ld4(&stage[row][ec]);
+      f32x4_t sv;
 #pragma unroll
       for (int e = 0; e < 4; ++e) sv[e] = fast_silu(v[e]);
       if (row < valid) {
         if (a.c0) st4(a.c0 + gr * 256 + col, v);
         if (a.sc0) st4(a.sc0 + gr * 256 + col, sv);
       } else {
-        sv = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        sv = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       }
       *reinterpret_cast<bf16x4_t*>(&cb[row][ec]) = to_bf4(sv);
     }
@@ -625,11 +614,6 @@ struct NodeLds {
   __bf16 yb[32][LD_Z];             // y1, then h_out, bf16: A operand of ff_linear1, then of input_lin / the read-out slice
   __bf16 sb[32][LD_S2];            // s1, bf16: A operand of ff_linear2
 };
-__device__ __forceinline__ float sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(NC_NT) void k_node_chain_fwd(dst_layout L, dst_node_chain_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -649,7 +633,7 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_fwd(dst_layout L, dst_node
   float bcur = a.b1[wave * 32 + (lane & 31)];
   // ---- stage 1: gated residual, LayerNorm + modulate; wave w takes rows 4 w .. 4 w + 3 (a row = 64 lanes x float4), loads first
   {
-    f4_t hv[4], av[4], g1v[4], shv[4], scv[4];
+    f32x4_t hv[4], av[4], g1v[4], shv[4], scv[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int64_t gr = min(t0 + 4 * wave + q, Nn - 1);
@@ -662,17 +646,17 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_fwd(dst_layout L, dst_node
     for (int q = 0; q < 4; ++q) {
       const int row = 4 * wave + q;
       const int64_t gr = min(t0 + row, Nn - 1);
-      const f4_t x = hv[q] + g1v[q] * av[q];
-      const float mean = sum64((x[0] + x[1]) + (x[2] + x[3])) * (1.0f / 256.0f);
-      const f4_t d = x - mean;
-      const float rstd = 1.0f / sqrtf(sum64((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * (1.0f / 256.0f) + 1e-6f);
-      f4_t y = (d * rstd) * (1.0f + scv[q]) + shv[q];
+      const f32x4_t x = hv[q] + g1v[q] * av[q];
+      const float mean = group_sum<64>((x[0] + x[1]) + (x[2] + x[3])) * (1.0f / 256.0f);
+      const f32x4_t d = x - mean;
+      const float rstd = 1.0f / sqrtf(group_sum<64>((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * (1.0f / 256.0f) + 1e-6f);
+      f32x4_t y = (d * rstd) * (1.0f + scv[q]) + shv[q];
       if (row < valid) {
         if (a.x1) st4(a.x1 + gr * 256 + cl, x);
         if (a.st && lane == 0) { a.st[gr * 2] = mean; a.st[gr * 2 + 1] = rstd; }
         if (a.y1) st4(a.y1 + gr * 256 + cl, y);
       } else {
-        y = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        y = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       }
       st4(&w.yf[row][cl], y);
       *reinterpret_cast<bf16x4_t*>(&w.yb[row][cl]) = to_bf4(y);
@@ -697,8 +681,8 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_fwd(dst_layout L, dst_node
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er, col = ch * 32 + ec;
       const int64_t gr = g0 + row;
-      const f4_t v = ld4(&stage[row][ec]);
-      f4_t sv;
+      const f32x4_t v = ld4(&stage[row][ec]);
+      f32x4_t sv;
 #pragma unroll
       for (int e = 0; e < 4; ++e) sv[e] = fast_silu(v[e]);
       if (a.drop_p > 0.0f) {
@@ -711,14 +695,14 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_fwd(dst_layout L, dst_node
         if (a.f1) st4(a.f1 + gr * 512 + col, v);
         if (a.s1) st4(a.s1 + gr * 512 + col, sv);
       } else {
-        sv = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        sv = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       }
       *reinterpret_cast<bf16x4_t*>(&w.sb[row][col]) = to_bf4(sv);
     }
     wave_lds_sync();
   }
   // the gate rows of the ff_linear2 epilogue (row it * 8 + er, columns wave * 32 + ec ..): requested before the barrier
-  f4_t g2c[4];
+  f32x4_t g2c[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it)
     g2c[it] = ld4(a.ada + (int64_t)a.node_mol[min(t0 + it * 8 + er, Nn - 1)] * a.ada_ld + a.gate2_off + wave * 32 + ec);
@@ -739,12 +723,12 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_fwd(dst_layout L, dst_node
     mma_apply<8>(&w.sb[0][0], LD_S2, 384, fb, acc);
     acc_to_stage(acc, stage);
     wave_lds_sync();
-    f4_t ho[4];
+    f32x4_t ho[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er, col = ch * 32 + ec;
       const int64_t gr = g0 + row;
-      f4_t v = ld4(&stage[row][ec]);
+      f32x4_t v = ld4(&stage[row][ec]);
       if (a.drop_p > 0.0f) {
         unsigned int c[4];
         dst::dropout_block(a.seed, a.stream2, (gr * 256 + col) >> 2, c);
@@ -756,7 +740,7 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_fwd(dst_layout L, dst_node
         if (a.f2) st4(a.f2 + gr * 256 + col, v);
         st4(a.h_out + gr * 256 + col, ho[it]);
       } else {
-        ho[it] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        ho[it] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       }
     }
     // h_out takes y1's bf16 tile (its last readers, ff_linear1's MFMAs, finished before the barrier above; a wave writes its own 32 columns)
@@ -787,7 +771,7 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_fwd(dst_layout L, dst_node
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er;
       const int64_t gr = g0 + row;
-      const f4_t v = ld4(&stage[row][ec]);
+      const f32x4_t v = ld4(&stage[row][ec]);
       if (row < valid) {
         if (!ro) st4(a.ac + gr * 512 + ch * 32 + ec, v);
         else st4(a.rn + gr * 64 + ch * 32 + ec, v);
@@ -830,7 +814,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_dir_chain_bwd(dst_layout L, dst_di
     w.d2[row][o] = row < valid ? a.dc2[(g0 + row) * 3 + o] : 0.0f;
   }
   // ---- dc0 = (dc2 W2) SiLU'(c0): chunks wave, wave + 4; a chunk row = 8 lanes x float4; every load of the phase before its first store
-  f4_t cv[2][4], w2v[2][3];
+  f32x4_t cv[2][4], w2v[2][3];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int col = (wave + 4 * k) * 32 + ec;
@@ -847,7 +831,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_dir_chain_bwd(dst_layout L, dst_di
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er;
       const float d0 = w.d2[row][0], d1 = w.d2[row][1], d2_ = w.d2[row][2];
-      f4_t v;
+      f32x4_t v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t = d0 * w2v[k][0][e];
@@ -856,7 +840,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_dir_chain_bwd(dst_layout L, dst_di
         v[e] = t * fast_silu_deriv(cv[k][it][e]);
       }
       if (row < valid) st4(a.dc0 + (g0 + row) * 256 + col, v);
-      else v = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+      else v = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       *reinterpret_cast<bf16x4_t*>(&w.db[row][col]) = to_bf4(v);
     }
   }
@@ -878,7 +862,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_dir_chain_bwd(dst_layout L, dst_di
   }
   // the LayerNorm backward's operands (wave w: rows 8 w .. 8 w + 7 as two passes of four; a row = 16 lanes, lane j the float4s at columns
   // 4 j + 64 u): requested before the barrier
-  f4_t zv[2][4], sc1[4];
+  f32x4_t zv[2][4], sc1[4];
   float mean[2], rstd[2];
   {
     const float* adm = a.ada + (int64_t)mol * a.ada_ld + a.scale_off + 4 * j16;
@@ -893,22 +877,22 @@ __global__ __launch_bounds__(CH_NT, 2) void k_dir_chain_bwd(dst_layout L, dst_di
     }
   }
   __syncthreads();
-  f4_t psh[4], psc[4];
+  f32x4_t psh[4], psc[4];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) { psh[u] = f4_t{0.0f, 0.0f, 0.0f, 0.0f}; psc[u] = psh[u]; }
+  for (int u = 0; u < 4; ++u) { psh[u] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f}; psc[u] = psh[u]; }
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int row = 8 * wave + 4 * q + sub;
-    f4_t g[4], xh[4];
+    f32x4_t g[4], xh[4];
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const f4_t dzn = ld4(&w.zf[row][64 * u + 4 * j16]);     // (rows beyond the tile: dc0 = 0 -> dzn = 0)
+      const f32x4_t dzn = ld4(&w.zf[row][64 * u + 4 * j16]);     // (rows beyond the tile: dc0 = 0 -> dzn = 0)
       xh[u] = (zv[q][u] - mean[q]) * rstd[q];
       psh[u] += dzn;
       psc[u] += dzn * xh[u];
       g[u] = dzn * sc1[u];
-      const f4_t gx = g[u] * xh[u];
+      const f32x4_t gx = g[u] * xh[u];
       s1 += (g[u][0] + g[u][1]) + (g[u][2] + g[u][3]);
       s2 += (gx[0] + gx[1]) + (gx[2] + gx[3]);
     }
@@ -985,16 +969,16 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
   wfetch<8>(fa, a.WedT, 256, 0, wave * 32, 128);
   // ---- ded (32 x 256) and dro (32 x 16) as bf16 tiles: wave w rows 8 w .. 8 w + 7, a ded row = 64 lanes x float4
   {
-    f4_t dv[8];
+    f32x4_t dv[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) dv[q] = ld4(a.ded + min(g0 + 8 * wave + q, glast) * 256 + lane * 4);
-    f4_t rv = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4_t rv = {0.0f, 0.0f, 0.0f, 0.0f};
     const int rrow = threadIdx.x >> 2, rc = (threadIdx.x & 3) * 4;              // 128 threads: (row, four of the 16 columns)
     if (threadIdx.x < 128 && rrow < valid) rv = ld4(a.dro + (g0 + rrow) * a.ld_dro + rc);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int row = 8 * wave + q;
-      if (row >= valid) dv[q] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+      if (row >= valid) dv[q] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       *reinterpret_cast<bf16x4_t*>(&w.eb[row][lane * 4]) = to_bf4(dv[q]);
     }
     if (threadIdx.x < 128) *reinterpret_cast<bf16x4_t*>(&w.rb[rrow][rc]) = to_bf4(rv);
@@ -1012,7 +996,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
     mma_apply<8>(&w.eb[0][0], LD_Z, 0, fa, acc);
     mma_apply<8>(&w.eb[0][0], LD_Z, 128, fb, acc);
     if (wave < 2) mma_apply<1>(&w.rb[0][0], 24, 0, fr, acc);
-    f4_t dein[4];
+    f32x4_t dein[4];
     if (wave < 2) {
 #pragma unroll
       for (int it = 0; it < 4; ++it) dein[it] = ld4(a.de + min(g0 + it * 8 + er, glast) * 64 + ch * 32 + ec);
@@ -1022,27 +1006,27 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er;
-      const f4_t v = ld4(&stage[row][ec]);
-      if (wave < 2) st4(&w.yf[row][ch * 32 + ec], row < valid ? v + dein[it] : f4_t{0.0f, 0.0f, 0.0f, 0.0f});
+      const f32x4_t v = ld4(&stage[row][ec]);
+      if (wave < 2) st4(&w.yf[row][ch * 32 + ec], row < valid ? v + dein[it] : f32x4_t{0.0f, 0.0f, 0.0f, 0.0f});
       else if (row < valid) st4(a.dfeat + (g0 + row) * 64 + (ch - 2) * 32 + ec, v);
     }
   }
   // operands of the gated-residual stage (wave w: rows 8 w .. 8 w + 7 as two passes of four; a row = 16 lanes x float4): before the barrier
-  const f4_t g2 = ld4(adm + a.gate2_off + cl);
-  f4_t f4v[2];
+  const f32x4_t g2 = ld4(adm + a.gate2_off + cl);
+  f32x4_t f4v[2];
 #pragma unroll
   for (int q = 0; q < 2; ++q) f4v[q] = ld4(a.f4 + min(g0 + 8 * wave + 4 * q + sub, glast) * 64 + cl);
   WFrag<4> f4w;
   wfetch<4>(f4w, a.W4T, 64, 0, wave * 32, 128);
   __syncthreads();
-  f4_t pg2 = {0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4_t pg2 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int row = 8 * wave + 4 * q + sub;
     const int64_t gr = g0 + row;
-    const f4_t d = ld4(&w.yf[row][cl]);                        // (zero beyond the tile)
+    const f32x4_t d = ld4(&w.yf[row][cl]);                        // (zero beyond the tile)
     pg2 += d * f4v[q];
-    f4_t o = g2 * d;
+    f32x4_t o = g2 * d;
     if (a.drop_p > 0.0f) {
       unsigned int c[4];
       dst::dropout_block(a.seed, a.stream4, (gr * 64 + cl) >> 2, c);
@@ -1050,7 +1034,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
       for (int e = 0; e < 4; ++e) o[e] = c[e] >= thr ? o[e] * keep_scale : 0.0f;
     }
     if (row < valid) st4(a.df4 + gr * 64 + cl, o);
-    else o = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+    else o = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
     *reinterpret_cast<bf16x4_t*>(&w.fb[row][cl]) = to_bf4(o);
   }
   __syncthreads();
@@ -1061,7 +1045,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
     mma_apply<4>(&w.fb[0][0], LD_Y, 0, f4w, acc);
-    f4_t f3v[4];
+    f32x4_t f3v[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) f3v[it] = ld4(a.f3 + min(g0 + it * 8 + er, glast) * 128 + ch * 32 + ec);
     wfetch<4>(f4w, a.W3T, 128, 64 * (wave >> 1), (wave & 1) * 32, 64);          // ff_linear3's input gradient: chunk wave & 1, k-half wave >> 1
@@ -1071,7 +1055,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er, col = ch * 32 + ec;
       const int64_t gr = g0 + row;
-      f4_t v = ld4(&stage[row][ec]);
+      f32x4_t v = ld4(&stage[row][ec]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] *= fast_silu_deriv(f3v[it][e]);
       if (a.drop_p > 0.0f) {
@@ -1081,7 +1065,7 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
         for (int e = 0; e < 4; ++e) v[e] = c[e] >= thr ? v[e] * keep_scale : 0.0f;
       }
       if (row < valid) st4(a.df3 + gr * 128 + col, v);
-      else v = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+      else v = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       *reinterpret_cast<bf16x4_t*>(&w.gb[row][col]) = to_bf4(v);
     }
   }
@@ -1095,8 +1079,8 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
     acc_to_stage(acc, stage);
   }
   // operands of the LayerNorm / gate stage: before the barrier
-  const f4_t sc1 = ld4(adm + a.scale_off + cl) + 1.0f, g1 = ld4(adm + a.gate1_off + cl);
-  f4_t xv[2], hv[2];
+  const f32x4_t sc1 = ld4(adm + a.scale_off + cl) + 1.0f, g1 = ld4(adm + a.gate1_off + cl);
+  f32x4_t xv[2], hv[2];
   float mean[2], rstd[2];
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -1105,20 +1089,20 @@ __global__ __launch_bounds__(CH_NT, 2) void k_pair_chain_bwd(dst_layout L, dst_p
     mean[q] = a.st[gr * 2]; rstd[q] = a.st[gr * 2 + 1];
   }
   __syncthreads();
-  f4_t psh = {0.0f, 0.0f, 0.0f, 0.0f}, psc = psh, pg1 = psh;
+  f32x4_t psh = {0.0f, 0.0f, 0.0f, 0.0f}, psc = psh, pg1 = psh;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int row = 8 * wave + 4 * q + sub;
     const int64_t gr = g0 + row;
     const int chn = j16 >> 3, ecn = (j16 & 7) * 4;
-    const f4_t dy = (ld4(&w.yf[row][cl]) + ld4(&w.stage[chn][row][ecn])) + ld4(&w.stage[2 + chn][row][ecn]);   // (zero beyond the tile)
-    const f4_t xh = (xv[q] - mean[q]) * rstd[q];
+    const f32x4_t dy = (ld4(&w.yf[row][cl]) + ld4(&w.stage[chn][row][ecn])) + ld4(&w.stage[2 + chn][row][ecn]);   // (zero beyond the tile)
+    const f32x4_t xh = (xv[q] - mean[q]) * rstd[q];
     psh += dy;
     psc += dy * xh;
-    const f4_t gg = dy * sc1, gx = gg * xh;
+    const f32x4_t gg = dy * sc1, gx = gg * xh;
     const float m1 = sum16_dpp((gg[0] + gg[1]) + (gg[2] + gg[3])) * (1.0f / 64.0f);
     const float m2 = sum16_dpp((gx[0] + gx[1]) + (gx[2] + gx[3])) * (1.0f / 64.0f);
-    const f4_t dx = rstd[q] * (gg - m1 - xh * m2);
+    const f32x4_t dx = rstd[q] * (gg - m1 - xh * m2);
     if (row < valid) {
       pg1 += dx * hv[q];
       st4(a.de_in + gr * 64 + cl, dx);
@@ -1183,17 +1167,17 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
   wfetch<8>(fa, a.WacT, 512, 0, wave * 32, 256);
   // ---- dac (32 x 512) and drn (32 x 64) as bf16 tiles: wave w rows 4 w .. 4 w + 3
   {
-    f4_t dv[4][2], rv[4];
+    f32x4_t dv[4][2], rv[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int64_t gr = min(g0 + 4 * wave + q, glast);
       dv[q][0] = ld4(a.dac + gr * 512 + cl); dv[q][1] = ld4(a.dac + gr * 512 + 256 + cl);
-      rv[q] = lane < 16 ? ld4(a.drn + gr * a.ld_drn + cl) : f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+      rv[q] = lane < 16 ? ld4(a.drn + gr * a.ld_drn + cl) : f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int row = 4 * wave + q;
-      if (row >= valid) { dv[q][0] = f4_t{0.0f, 0.0f, 0.0f, 0.0f}; dv[q][1] = dv[q][0]; rv[q] = dv[q][0]; }
+      if (row >= valid) { dv[q][0] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f}; dv[q][1] = dv[q][0]; rv[q] = dv[q][0]; }
       *reinterpret_cast<bf16x4_t*>(&w.ab[row][cl]) = to_bf4(dv[q][0]);
       *reinterpret_cast<bf16x4_t*>(&w.ab[row][256 + cl]) = to_bf4(dv[q][1]);
       if (lane < 16) *reinterpret_cast<bf16x4_t*>(&w.rb[row][cl]) = to_bf4(rv[q]);
@@ -1214,7 +1198,7 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
     mma_apply<8>(&w.ab[0][0], LD_S2, 128, fb, acc);
     wfetch<8>(fb, a.WacT, 512, 384, ch * 32, 256);
     mma_apply<8>(&w.ab[0][0], LD_S2, 256, fa, acc);
-    f4_t dhv[4];
+    f32x4_t dhv[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) dhv[it] = ld4(a.dh + min(g0 + it * 8 + er, glast) * 256 + ch * 32 + ec);
     mma_apply<8>(&w.ab[0][0], LD_S2, 384, fb, acc);
@@ -1225,24 +1209,24 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er;
-      const f4_t v = ld4(&stage[row][ec]);
-      st4(&w.yf[row][ch * 32 + ec], row < valid ? v + dhv[it] : f4_t{0.0f, 0.0f, 0.0f, 0.0f});
+      const f32x4_t v = ld4(&stage[row][ec]);
+      st4(&w.yf[row][ch * 32 + ec], row < valid ? v + dhv[it] : f32x4_t{0.0f, 0.0f, 0.0f, 0.0f});
     }
   }
-  const f4_t g2 = ld4(adm + a.gate2_off + cl);
-  f4_t f2v[4];
+  const f32x4_t g2 = ld4(adm + a.gate2_off + cl);
+  f32x4_t f2v[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) f2v[q] = ld4(a.f2 + min(g0 + 4 * wave + q, glast) * 256 + cl);
   __syncthreads();
   // ---- gated residual of the FF: df2 = gate2 dh_tot (dropout mask 2); wave w rows 4 w .. 4 w + 3
-  f4_t pg2 = {0.0f, 0.0f, 0.0f, 0.0f};
+  f32x4_t pg2 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int row = 4 * wave + q;
     const int64_t gr = g0 + row;
-    const f4_t d = ld4(&w.yf[row][cl]);
+    const f32x4_t d = ld4(&w.yf[row][cl]);
     pg2 += d * f2v[q];
-    f4_t o = g2 * d;
+    f32x4_t o = g2 * d;
     if (a.drop_p > 0.0f) {
       unsigned int c[4];
       dst::dropout_block(a.seed, a.stream2, (gr * 256 + cl) >> 2, c);
@@ -1250,7 +1234,7 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
       for (int e = 0; e < 4; ++e) o[e] = c[e] >= thr ? o[e] * keep_scale : 0.0f;
     }
     if (row < valid) st4(a.df2 + gr * 256 + cl, o);
-    else o = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+    else o = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
     *reinterpret_cast<bf16x4_t*>(&w.fb[row][cl]) = to_bf4(o);
   }
   __syncthreads();
@@ -1264,7 +1248,7 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
     wfetch<8>(fb, a.W2T, 256, 128, ch * 32, 512);
     mma_apply<8>(&w.fb[0][0], LD_Z, 0, fa, acc);
     mma_apply<8>(&w.fb[0][0], LD_Z, 128, fb, acc);
-    f4_t f1v[4];
+    f32x4_t f1v[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) f1v[it] = ld4(a.f1 + min(g0 + it * 8 + er, glast) * 512 + ch * 32 + ec);
     if (k == 0) wfetch<8>(fa, a.W2T, 256, 0, (ch + 8) * 32, 512);
@@ -1275,7 +1259,7 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
     for (int it = 0; it < 4; ++it) {
       const int row = it * 8 + er, col = ch * 32 + ec;
       const int64_t gr = g0 + row;
-      f4_t v = ld4(&stage[row][ec]);
+      f32x4_t v = ld4(&stage[row][ec]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] *= fast_silu_deriv(f1v[it][e]);
       if (a.drop_p > 0.0f) {
@@ -1285,7 +1269,7 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
         for (int e = 0; e < 4; ++e) v[e] = c[e] >= thr ? v[e] * keep_scale : 0.0f;
       }
       if (row < valid) st4(a.df1 + gr * 512 + col, v);
-      else v = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
+      else v = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       *reinterpret_cast<bf16x4_t*>(&w.ab[row][col]) = to_bf4(v);
     }
     wave_lds_sync();
@@ -1314,8 +1298,8 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
     }
   }
   // operands of the LayerNorm / gate stage: before the barrier
-  const f4_t sc1 = ld4(adm + a.scale_off + cl) + 1.0f, g1 = ld4(adm + a.gate1_off + cl);
-  f4_t xv[4], av[4];
+  const f32x4_t sc1 = ld4(adm + a.scale_off + cl) + 1.0f, g1 = ld4(adm + a.gate1_off + cl);
+  f32x4_t xv[4], av[4];
   float mean[4], rstd[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -1324,19 +1308,19 @@ __global__ __launch_bounds__(NC_NT) void k_node_chain_bwd(dst_layout L, dst_node
     mean[q] = a.st[gr * 2]; rstd[q] = a.st[gr * 2 + 1];
   }
   __syncthreads();
-  f4_t psh = {0.0f, 0.0f, 0.0f, 0.0f}, psc = psh, pg1 = psh;
+  f32x4_t psh = {0.0f, 0.0f, 0.0f, 0.0f}, psc = psh, pg1 = psh;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int row = 4 * wave + q;
     const int64_t gr = g0 + row;
-    const f4_t dy = ld4(&w.yf[row][cl]);                       // (zero beyond the tile)
-    const f4_t xh = (xv[q] - mean[q]) * rstd[q];
+    const f32x4_t dy = ld4(&w.yf[row][cl]);                       // (zero beyond the tile)
+    const f32x4_t xh = (xv[q] - mean[q]) * rstd[q];
     psh += dy;
     psc += dy * xh;
-    const f4_t gg = dy * sc1, gx = gg * xh;
+    const f32x4_t gg = dy * sc1, gx = gg * xh;
     const float m1 = sum64_dpp((gg[0] + gg[1]) + (gg[2] + gg[3])) * (1.0f / 256.0f);
     const float m2 = sum64_dpp((gx[0] + gx[1]) + (gx[2] + gx[3])) * (1.0f / 256.0f);
-    const f4_t dx = rstd[q] * (gg - m1 - xh * m2);
+    const f32x4_t dx = rstd[q] * (gg - m1 - xh * m2);
     if (row < valid) {
       pg1 += dx * av[q];
       st4(a.dh_in + gr * 256 + cl, dx);

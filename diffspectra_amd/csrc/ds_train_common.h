@@ -1,15 +1,25 @@
-// diffspectra_amd - small helpers shared by the training sources (ds_train*.hip): device math, and the host side of a launch
-// (DST_CHECK_LAUNCH is the whole library's launch-status rule: ds_kernels.hip includes this header for it).
+// diffspectra_amd - small helpers shared by the training sources (ds_train*.hip): device math (the host side of a launch is ds_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-#include <initializer_list>
-
 #include "../../include/diffspectra_hip.h"
+#include "ds_host.h"
 
-#define DST_CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? DS_OK : DS_ERR_LAUNCH)
+typedef float f32x16_t __attribute__((ext_vector_type(16)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ f32x4_t ld4(const float* p) { return *reinterpret_cast<const f32x4_t*>(p); }
+__device__ __forceinline__ void st4(float* p, f32x4_t v) { *reinterpret_cast<f32x4_t*>(p) = v; }
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {      // sum over aligned groups of G lanes
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 namespace dst {
 
@@ -52,27 +62,6 @@ __device__ __forceinline__ bool dropout_keep(unsigned long long seed, unsigned i
   const int j = (int)(i & 3);
   const unsigned int w = j == 0 ? c[0] : j == 1 ? c[1] : j == 2 ? c[2] : c[3];
   return w >= thr;
-}
-
-// ------------------------------------------------------------------------------------------------------------------ host side
-// true when every pointer is 16-byte aligned (NULL counts as aligned: whether a pointer may be NULL is the caller's check)
-inline bool all_aligned16(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-  return true;
-}
-
-// Lets `kernel` request `bytes` of dynamic LDS on the current device.  The attribute is per device, so `done` (one static per call
-// site) remembers the devices it has been set on; two threads may both set it, which is harmless.  false: the runtime refused.
-template <typename Kernel>
-bool allow_dynamic_lds(std::atomic<uint64_t>& done, Kernel* kernel, size_t bytes) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  const uint64_t bit = dev >= 0 && dev < 64 ? uint64_t(1) << dev : 0;     // (beyond 64 devices: set on every launch)
-  if (done.load(std::memory_order_acquire) & bit) return true;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
-  done.fetch_or(bit, std::memory_order_release);
-  return true;
 }
 
 }  // namespace dst

@@ -27,10 +27,6 @@
 #include "../../include/diffspectra_train.h"
 #include "ds_train_common.h"
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 

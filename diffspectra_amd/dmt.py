@@ -3,7 +3,7 @@
 Mirror of reference ``models/dmt.py:178-412``: ``@register_model(name='DMT')``, one ``config`` constructor
 argument, the same parameter tree (``params.build_dmt_tree``) and
 ``forward(t, xh, node_mask, edge_mask, context=None, *args, edge_x=, noise_level=, cond_x=, cond_edge_x=)``
-→ ``(Tensor[B,N,9], Tensor[B,N,N,2])``.  The forward pass is ``ds_forward`` of ``csrc/ds_kernels.hip``;
+→ ``(Tensor[B,N,9], Tensor[B,N,N,2])``.  The forward pass is ``ds_forward`` of ``csrc/ds_forward.hip``;
 there is no PyTorch implementation of the arithmetic in this package.
 """
 from __future__ import annotations

@@ -1,6 +1,6 @@
 """ctypes binding to ``libdiffspectra_hip.so`` + the host plumbing around it.
 
-Everything arithmetic happens in the HIP library (``csrc/ds_kernels.hip``); this module packs the
+Everything arithmetic happens in the HIP library (``csrc/ds_forward.hip``, ``ds_gemm.hip``, ``ds_sampler.hip``, ``ds_spec.hip``); this module packs the
 reference-named parameters into the library's MFMA-operand layout once, builds the packed-ragged index
 tables from ``node_mask``, owns the (torch-allocated) device workspace and issues the C-ABI calls on
 torch's current HIP stream.  There is NO fallback: if the library is missing or no GPU is visible the

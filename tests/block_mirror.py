@@ -1,4 +1,4 @@
-"""Float64 yardstick of the sampling block kernels (csrc/ds_kernels.hip; buffers: ``ds_workspace`` in include/diffspectra_hip.h), plain
+"""Float64 yardstick of the sampling block kernels (csrc/ds_forward.hip; buffers: ``ds_workspace`` in include/diffspectra_hip.h), plain
 torch / numpy on the CPU.  TEST INFRASTRUCTURE ONLY; pinned without a GPU by tests/test_block_mirror_cpu.py, used by
 tests/test_block_stages_gpu.py.
 

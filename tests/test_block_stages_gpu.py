@@ -1,4 +1,4 @@
-"""Stage-by-stage fp64 parity of the sampling block kernels (csrc/ds_kernels.hip) against tests/block_mirror.py: every buffer a block's
+"""Stage-by-stage fp64 parity of the sampling block kernels (csrc/ds_forward.hip) against tests/block_mirror.py: every buffer a block's
 seven kernels hand each other through the workspace, plus init and readout.
 
 TEACHER FORCING.  h, e and pos are snapshotted before each ``ds_stage_block``; afterwards every stage's reference is evaluated from the

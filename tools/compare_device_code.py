@@ -1,9 +1,11 @@
 """Compare the gfx950 device code of two builds, kernel by kernel: `python tools/compare_device_code.py OLD_OBJ_DIR NEW_OBJ_DIR`.
 
-For every object present in both directories the gfx950 code object is unbundled and disassembled; for every kernel the instruction stream and
+The gfx950 code object of every object in either directory is unbundled and disassembled; for every kernel the instruction stream and
 the metadata that decides occupancy (VGPR / SGPR / AGPR counts, LDS and scratch sizes, workgroup size limit) must be identical; only the
-pc-relative distance from a kernel to a constant table in .rodata is left out, since it changes whenever kernels are emitted in another order.  Kernels are
-matched by their base name plus template arguments as the demangler prints them; a name that exists on one side only is reported as a
+pc-relative distance from a kernel to a constant table in .rodata is left out, since it changes whenever kernels are emitted in another order,
+and the "..." that the disassembler prints for the zero padding behind a kernel, which depends on what follows it in .text.  Kernels are
+matched by their base name plus template arguments as the demangler prints them, over all objects of a directory: a kernel may move to another
+object, and every report says which object it was found in on each side; a name that exists on one side only is reported as a
 difference.  Prints "N kernels compared, M differ" and exits non-zero when M > 0: what a refactor of the host code has to show."""
 import os
 import re
@@ -36,7 +38,7 @@ def kernels(obj, tmp):
         if m:
             cur = m.group(1)
             code[cur] = []
-        elif cur and line.strip():
+        elif cur and line.strip() and line.strip() != "...":
             insn = re.sub(r"\s*//.*$", "", line.strip())                  # the trailing comment holds the address
             if code[cur] and code[cur][-1].startswith("s_getpc_b64") and insn.startswith("s_add_u32"):
                 insn = re.sub(r"0x[0-9a-f]+$", "<pc-relative>", insn)    # distance to a constant table: moves with the order of the kernels in .text
@@ -47,22 +49,36 @@ def kernels(obj, tmp):
     return {s: (code[m], meta[m]) for s, m in zip(short, meta)}
 
 
+def build_kernels(obj_dir, tmp):
+    """{kernel name: (object, instructions, metadata)} over every object of a build directory."""
+    found = {}
+    for obj in sorted(f for f in os.listdir(obj_dir) if f.endswith(".o")):
+        for name, (code, meta) in kernels(os.path.join(obj_dir, obj), tmp).items():
+            name = re.sub(r"<.*$", "", name) if name.startswith("k_equi_pairs") else name
+            if name in found:
+                raise SystemExit(f"{obj_dir}: {name} is in {found[name][0]} and in {obj}")
+            found[name] = (obj, code, meta)
+    return found
+
+
 def main(old_dir, new_dir):
     total = differ = 0
     with tempfile.TemporaryDirectory() as t_old, tempfile.TemporaryDirectory() as t_new:
-        for obj in sorted(f for f in os.listdir(old_dir) if f.endswith(".o") and os.path.exists(os.path.join(new_dir, f))):
-            old, new = kernels(os.path.join(old_dir, obj), t_old), kernels(os.path.join(new_dir, obj), t_new)
-            base = lambda d: {re.sub(r"<.*$", "", k) if k.startswith("k_equi_pairs") else k: v for k, v in d.items()}
-            old, new = base(old), base(new)
-            for name in sorted(set(old) | set(new)):
-                total += 1
-                if name not in old or name not in new:
-                    differ += 1
-                    print(f"{obj}: {name}: only in the {'new' if name in new else 'old'} build")
-                elif old[name] != new[name]:
-                    differ += 1
-                    what = "metadata" if old[name][1] != new[name][1] else "instructions"
-                    print(f"{obj}: {name}: {what} differ ({len(old[name][0])} vs {len(new[name][0])} instructions; {old[name][1]} vs {new[name][1]})")
+        old, new = build_kernels(old_dir, t_old), build_kernels(new_dir, t_new)
+    for name in sorted(set(old) | set(new)):
+        total += 1
+        if name not in old or name not in new:
+            differ += 1
+            print(f"{name}: only in the {'new' if name in new else 'old'} build ({(new if name in new else old)[name][0]})")
+            continue
+        (o_obj, o_code, o_meta), (n_obj, n_code, n_meta) = old[name], new[name]
+        where = o_obj if o_obj == n_obj else f"{o_obj} -> {n_obj}"
+        if (o_code, o_meta) != (n_code, n_meta):
+            differ += 1
+            what = "metadata" if o_meta != n_meta else "instructions"
+            print(f"{where}: {name}: {what} differ ({len(o_code)} vs {len(n_code)} instructions; {o_meta} vs {n_meta})")
+        elif o_obj != n_obj:
+            print(f"{where}: {name}: identical")
     print(f"{total} kernels compared, {differ} differ")
     return 1 if differ else 0
 

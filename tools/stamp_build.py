@@ -5,11 +5,13 @@
 Counter index base follows the colon; shares print as P<base+i>.  Development tool, never part of the product build.
 """
 import os
+import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "diffspectra_amd", "csrc", "ds_kernels.hip")
+sys.path.insert(0, ROOT)
+import __graft_entry__ as g  # noqa: E402
 
 
 def stamp_kernel(s, name, base):
@@ -27,29 +29,39 @@ def stamp_kernel(s, name, base):
     return s[:a] + out + s[b:], len(parts)
 
 
-def main():
-    s = open(SRC).read()
-    import re
+def strip_stamps(s):
+    """Drop the in-tree stamps: they are re-inserted uniformly."""
     s = re.sub(r"\n\s*DS_STAMP(_W)?\(\d+\);", "", s)
-    s = re.sub(r"\n\s*DS_STAMP_FLUSH\([^)]*\);", "", s)           # drop the in-tree stamps, re-insert uniformly
-    s = s.replace("  DS_STAMP_INIT();\n", "")
+    s = re.sub(r"\n\s*DS_STAMP_FLUSH\([^)]*\);", "", s)
+    return s.replace("  DS_STAMP_INIT();\n", "")
+
+
+def main():
+    texts = {}                                  # source path -> stamped text, for the sources that hold a named kernel
     for spec in sys.argv[1:]:
         name, base = spec.split(":")
-        s, n = stamp_kernel(s, name, int(base))
-        print(name, "phases:", n, "-> P%d..P%d" % (int(base), int(base) + n - 1))
-    tmp = os.path.join(ROOT, "diffspectra_amd", "csrc", "_stamped.hip")
-    open(tmp, "w").write(s)
-    obj = os.path.join(ROOT, "build", "obj", "stamped.o")
-    others = [os.path.join(ROOT, "build", "obj", n) for n in ("ds_aux.o", "ds_train.o")]      # run build() first
+        holds = [p for p in g.HIP_SOURCES if "void %s(Ctx c" % name in (texts.get(p) or open(p).read())]
+        if len(holds) != 1:
+            sys.exit("%s: found in %d sources" % (name, len(holds)))
+        src = holds[0]
+        texts[src], n = stamp_kernel(texts.get(src) or strip_stamps(open(src).read()), name, int(base))
+        print(name, "(%s)" % os.path.basename(src), "phases:", n, "-> P%d..P%d" % (int(base), int(base) + n - 1))
+    objs = [os.path.join(g.OBJ_DIR, os.path.basename(p)[:-4] + ".o") for p in g.HIP_SOURCES]      # run build() first
+    made = []
     try:
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-mllvm", "-amdgpu-mfma-vgpr-form=1",
-                        "-DDS_STAMPS", "-c", tmp, "-o", obj], check=True)
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", obj, *others, "-o",
+        for src, text in texts.items():
+            tmp, obj = src[:-4] + "_stamped.hip", os.path.join(g.OBJ_DIR, os.path.basename(src)[:-4] + "_stamped.o")
+            made += [tmp, obj]
+            with open(tmp, "w") as f:
+                f.write(text)
+            subprocess.run(["/opt/rocm/bin/hipcc", *g.BASE_FLAGS, *g.OPT_FLAGS, "-DDS_STAMPS", "-c", tmp, "-o", obj], check=True, cwd=ROOT)
+            objs[g.HIP_SOURCES.index(src)] = obj
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o",
                         os.path.join(ROOT, "diffspectra_amd", "libdiffspectra_hip_stamps.so")], check=True)
     finally:
-        os.remove(tmp)
-        if os.path.exists(obj):
-            os.remove(obj)
+        for f in made:
+            if os.path.exists(f):
+                os.remove(f)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 
     python tools/variant_build.py NAME [-DFOO=1 ...]      ->  diffspectra_amd/libdiffspectra_hip_NAME.so
     DIFFSPECTRA_HIP_LIB=diffspectra_amd/libdiffspectra_hip_NAME.so python tools/time_forward.py ...
-Only ONE source (default ds_kernels.hip; `--source ds_train_attn.hip` picks another) is recompiled with the extra flags; the other objects come from build/obj (run build() first).
+Only ONE source (default ds_forward.hip; `--source ds_train_attn.hip` picks another) is recompiled with the extra flags; the other objects come from build/obj (run build() first).
 """
 import os
 import subprocess
@@ -15,7 +15,7 @@ import __graft_entry__ as g  # noqa: E402
 
 def main():
     name, extra = sys.argv[1], sys.argv[2:]
-    which = "ds_kernels.hip"
+    which = "ds_forward.hip"
     if "--source" in extra:
         k = extra.index("--source")
         which = extra[k + 1]

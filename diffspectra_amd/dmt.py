@@ -73,7 +73,6 @@ class DMT(nn.Module):
         ``Tensor._version`` is not enough: both EMA implementations write with ``p.data.copy_(...)`` (reference
         models/ema.py:55,77), which leaves the version counter untouched.  The checksum weights every element by a hash of
         its position, so sign flips, row / head permutations and copies from an equal-norm tensor all change it."""
-        import ctypes as C
         from .engine import load_library, _check, _stream
         ts = [t.detach() for t in list(self.parameters()) + list(self.buffers()) if t.is_floating_point()]
         dev = ts[0].device
@@ -90,8 +89,7 @@ class DMT(nn.Module):
             tab = (ptrs, torch.tensor(ptrs, dtype=torch.int64, device=dev), torch.tensor(prefix, dtype=torch.int64, device=dev),
                    torch.zeros(1, dtype=torch.int64, device=dev))
             self._fp_table = tab
-        _check(load_library().ds_fingerprint(C.c_void_p(tab[1].data_ptr()), C.c_void_p(tab[2].data_ptr()), C.c_int32(len(ts)),
-                                             C.c_void_p(tab[3].data_ptr()), _stream()), "ds_fingerprint")
+        _check(load_library().ds_fingerprint(tab[1].data_ptr(), tab[2].data_ptr(), len(ts), tab[3].data_ptr(), _stream()), "ds_fingerprint")
         return (str(dev), ptrs[:4], int(tab[3].item()))
 
     def invalidate_engine(self):

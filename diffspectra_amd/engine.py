@@ -16,6 +16,9 @@ import numpy as np
 import torch
 
 from . import abi
+from .abi import ptr
+
+_ptr = ptr      # the name under which the tests and tools that call the library directly know the pointer helper
 
 LIB_PATH = os.environ.get("DIFFSPECTRA_HIP_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdiffspectra_hip.so"))
 
@@ -49,14 +52,13 @@ def load_library() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`. "
                            "diffspectra_amd has no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
+    abi.SAMPLING.bind(lib)               # restype and argtypes of every export, as the headers declare them; AttributeError if the
+    abi.TRAINING.bind(lib)               # headers declare something the .so lacks
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
     mine = [C.sizeof(t) for t in (DsWeights, DsLayout, DsWorkspace, DsGemmArgs)]
     if list(sizes) != mine:
         raise RuntimeError(f"C-ABI struct layout mismatch: library {list(sizes)} vs binding {mine}")
-    for name in EXPORTS:
-        fn = getattr(lib, name)          # AttributeError if the header declares something the .so lacks
-        fn.restype = None if name == "ds_struct_sizes" else C.c_int
     _lib = lib
     return lib
 
@@ -67,12 +69,8 @@ def _check(status: int, what: str):
                            f"({ {-1: 'bad argument', -2: 'HIP launch error'}.get(status, 'unknown')})")
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _f32c(t: torch.Tensor, device) -> torch.Tensor:
@@ -153,8 +151,7 @@ def split_rows_f16(a: torch.Tensor) -> torch.Tensor:
 
 def gemm_split(lib, a_split: torch.Tensor, w_split: torch.Tensor, bias, out: torch.Tensor, M: int, K: int, N: int):
     """C = A W + bias through ``ds_gemm_split`` (operands prepared by ``split_rows_f16`` / ``pack_linear_f16_split``)."""
-    _check(lib.ds_gemm_split(_ptr(a_split), _ptr(w_split), _ptr(bias), _ptr(out), C.c_int64(out.stride(0)), C.c_int32(M), C.c_int32(K),
-                             C.c_int32(N), _stream()), "ds_gemm_split")
+    _check(lib.ds_gemm_split(ptr(a_split), ptr(w_split), ptr(bias), ptr(out), out.stride(0), M, K, N, _stream()), "ds_gemm_split")
 
 
 def pad_vec(v: torch.Tensor, to: int = 32) -> torch.Tensor:
@@ -405,7 +402,7 @@ def _record_call(name, tables, ref_index, scalars, outputs):
         _want(rec, rec_name, torch.uint8, (None, RECORD_BYTES))
         _want(n, n_name, torch.int32, (rec.shape[0],))
         tensors += [rec, n]
-        args += [_ptr(rec), _ptr(n), C.c_int64(rec.shape[0])]
+        args += [ptr(rec), ptr(n), rec.shape[0]]
     P = tensors[0].shape[0]
     if pairs:
         if ref_index is not None:
@@ -413,14 +410,14 @@ def _record_call(name, tables, ref_index, scalars, outputs):
             tensors.append(ref_index)
         elif tensors[2].shape[0] < P:
             raise ValueError(f"without ref_index pair p reads ground-truth row p: {tensors[2].shape[0]} rows for {P} pairs")
-        args.append(_ptr(ref_index))
+        args.append(ptr(ref_index))
     dev = tensors[0].device
     if dev.type != "cuda" or any(t.device != dev for t in tensors):
         raise RuntimeError(f"{name} needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
     lib = load_library()
     out = tuple(torch.empty(P, *shape, dtype=dtype, device=dev) for dtype, shape in outputs)
     with torch.cuda.device(dev):
-        st = getattr(lib, "ds_" + name)(*args, *scalars, *(_ptr(t) for t in out), _stream())
+        st = getattr(lib, "ds_" + name)(*args, *scalars, *(ptr(t) for t in out), _stream())
     _check(st, "ds_" + name)
     return out
 
@@ -430,7 +427,7 @@ def _node_budget(max_nodes, most):
         raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
     if not 0 <= max_nodes <= most:
         raise ValueError(f"max_nodes must lie in [0, {most}], got {max_nodes}")
-    return C.c_int32(max_nodes)
+    return max_nodes
 
 
 _MAP = (torch.int32, (MAX_ATOMS,))        # the atom map that every record-pair entry point returns last
@@ -447,7 +444,7 @@ def match_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Ten
     max_distance, min_atoms = float(max_distance), int(min_atoms)
     if max_distance != max_distance:
         raise ValueError("max_distance must not be NaN")
-    return _record_call("match_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [C.c_float(max_distance), C.c_int32(min_atoms)],
+    return _record_call("match_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [max_distance, min_atoms],
                         [(torch.float64, ()), (torch.int32, ()), (torch.float32, ()), (torch.float32, ()), (torch.uint8, ()), _MAP])
 
 
@@ -498,7 +495,7 @@ def mces_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tens
     or ``MCES_INVALID`` (3: ``ref_index`` outside the table, ``dist = lower = -1``).  The arguments are checked, never converted."""
     if not isinstance(drop_h, bool):
         raise TypeError(f"drop_h must be a bool, got {type(drop_h).__name__}")
-    return _record_call("mces_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [C.c_int32(int(drop_h)), _node_budget(max_nodes, MCES_MAX_NODES)],
+    return _record_call("mces_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [int(drop_h), _node_budget(max_nodes, MCES_MAX_NODES)],
                         [(torch.int32, ()), (torch.int32, ()), (torch.uint8, ()), (torch.int32, ()), _MAP])
 
 
@@ -515,7 +512,7 @@ def _morgan_shape(drop_h, radius):
         raise TypeError(f"radius must be an int, got {type(radius).__name__}")
     if not 0 <= radius <= MORGAN_MAX_RADIUS:
         raise ValueError(f"radius must lie in [0, {MORGAN_MAX_RADIUS}], got {radius}")
-    return [C.c_int32(int(drop_h)), C.c_int32(radius)]
+    return [int(drop_h), radius]
 
 
 def morgan_records(rec: torch.Tensor, n: torch.Tensor, drop_h: bool = True, radius: int = 2):
@@ -547,7 +544,7 @@ def morgan_similarity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_re
         raise TypeError(f"n_bits must be an int, got {type(n_bits).__name__}")
     if n_bits != 0 and not (64 <= n_bits <= MORGAN_MAX_BITS and n_bits & (n_bits - 1) == 0):
         raise ValueError(f"n_bits must be 0 (unfolded) or a power of two in [64, {MORGAN_MAX_BITS}], got {n_bits}")
-    return _record_call("morgan_similarity_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, scalars + [C.c_int32(n_bits)],
+    return _record_call("morgan_similarity_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, scalars + [n_bits],
                         [(torch.int32, ()), (torch.int32, ()), (torch.int32, ()), (torch.uint8, ())])
 
 
@@ -567,7 +564,7 @@ def _class_tables(rec, bond_cls, angle_cls, dihedral_cls):
             raise ValueError(f"{name} holds {t.shape[0]} classes, at most {GEOM_MAX_CLASSES} fit")
         if torch.is_tensor(rec) and t.device != rec.device:
             raise RuntimeError(f"{name} must be on the records' device {rec.device}, got {t.device}")
-        args += [_ptr(t) if t.shape[0] else None, C.c_int32(t.shape[0])]
+        args += [ptr(t) if t.shape[0] else None, t.shape[0]]
     return args
 
 
@@ -601,14 +598,14 @@ def geometry_fill_records(rec: torch.Tensor, n: torch.Tensor, bond_cls: torch.Te
         raise RuntimeError(f"offsets must be on the records' device {rec.device}, got {offsets.device}")
     out = tuple((torch.empty(t, dtype=torch.float32, device=rec.device), torch.empty(t, dtype=torch.uint8, device=rec.device)) for t in totals)
     _record_call("geometry_fill_records", [(rec, n)], None,
-                 tables + [C.c_int64(t) for t in totals] + [_ptr(offsets)] + [_ptr(t) if t.numel() else None for pair in out for t in pair], [])
+                 tables + totals + [ptr(offsets)] + [ptr(t) if t.numel() else None for pair in out for t in pair], [])
     return out
 
 
 def mmd_workspace_bytes(n_classes: int) -> int:
     """``ds_mmd_1d_workspace_bytes``: the device bytes ``mmd_1d_segments`` needs for ``n_classes`` classes (a pure host function)."""
     size = C.c_int64(0)
-    _check(load_library().ds_mmd_1d_workspace_bytes(C.c_int64(int(n_classes)), C.byref(size)), "ds_mmd_1d_workspace_bytes")
+    _check(load_library().ds_mmd_1d_workspace_bytes(int(n_classes), C.byref(size)), "ds_mmd_1d_workspace_bytes")
     return int(size.value)
 
 
@@ -657,9 +654,9 @@ def mmd_1d_segments(x: torch.Tensor, x_off: torch.Tensor, y: torch.Tensor, y_off
     out = torch.empty(n_cls, 5, dtype=torch.float64, device=dev)
     status = torch.empty(n_cls, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        st = lib.ds_mmd_1d_segments(_ptr(x) if x.numel() else None, _ptr(x_off), C.c_int64(x.shape[0]), _ptr(y) if y.numel() else None, _ptr(y_off),
-                                    C.c_int64(y.shape[0]), C.c_int64(n_cls), C.c_double(kernel_mul), C.c_int32(kernel_num), C.c_double(sigma),
-                                    _ptr(workspace), C.c_int64(workspace.shape[0]), _ptr(out), _ptr(status), _stream())
+        st = lib.ds_mmd_1d_segments(ptr(x) if x.numel() else None, ptr(x_off), x.shape[0], ptr(y) if y.numel() else None, ptr(y_off),
+                                    y.shape[0], n_cls, kernel_mul, kernel_num, sigma, ptr(workspace), workspace.shape[0], ptr(out),
+                                    ptr(status), _stream())
     _check(st, "ds_mmd_1d_segments")
     return out, status
 
@@ -727,35 +724,33 @@ class DmtEngine:
             out_xh = torch.empty(L.B, L.N, 9, dtype=torch.float32, device=dev)
         if out_edge is None:
             out_edge = torch.empty(L.B, L.N, L.N, 2, dtype=torch.float32, device=dev)
-        st = self.lib.ds_forward(C.byref(self.w), C.byref(L.c), C.byref(ws.c), _ptr(xh), _ptr(edge_x), _ptr(cond_x),
-                                 _ptr(cond_edge_x), _ptr(noise_level), _ptr(ctx_emb), _ptr(out_xh), _ptr(out_edge),
+        st = self.lib.ds_forward(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(xh), ptr(edge_x), ptr(cond_x),
+                                 ptr(cond_edge_x), ptr(noise_level), ptr(ctx_emb), ptr(out_xh), ptr(out_edge),
                                  _stream())
         _check(st, "ds_forward")
         return out_xh, out_edge
 
     # stage-level calls for the parity tests
     def stage_time(self, L, ws, noise_level, ctx_emb):
-        _check(self.lib.ds_stage_time(C.byref(self.w), C.byref(L.c), C.byref(ws.c), _ptr(noise_level), _ptr(ctx_emb),
+        _check(self.lib.ds_stage_time(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(noise_level), ptr(ctx_emb),
                                       _stream()), "ds_stage_time")
 
     def stage_init(self, L, ws, xh, edge_x, cond_x, cond_edge_x):
-        _check(self.lib.ds_stage_init(C.byref(self.w), C.byref(L.c), C.byref(ws.c), _ptr(xh), _ptr(edge_x),
-                                      _ptr(cond_x), _ptr(cond_edge_x), _stream()), "ds_stage_init")
+        _check(self.lib.ds_stage_init(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(xh), ptr(edge_x),
+                                      ptr(cond_x), ptr(cond_edge_x), _stream()), "ds_stage_init")
 
     def stage_block(self, L, ws, blk, last=False):
-        _check(self.lib.ds_stage_block(C.byref(self.w), C.byref(L.c), C.byref(ws.c), C.c_int(blk), C.c_int(int(last)),
+        _check(self.lib.ds_stage_block(C.byref(self.w), C.byref(L.c), C.byref(ws.c), blk, int(last),
                                        _stream()), "ds_stage_block")
 
     def stage_readout(self, L, ws, out_xh, out_edge):
-        _check(self.lib.ds_stage_readout(C.byref(self.w), C.byref(L.c), C.byref(ws.c), _ptr(out_xh), _ptr(out_edge),
+        _check(self.lib.ds_stage_readout(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(out_xh), ptr(out_edge),
                                          _stream()), "ds_stage_readout")
 
     def sampler_step(self, L, c_x, c_pred, sigma, temperature, x, edge_x, pred, edge_pred, raw_pos, raw_feat, raw_edge,
                      x_mean, edge_mean):
-        st = self.lib.ds_sampler_step(C.byref(L.c), C.c_float(c_x), C.c_float(c_pred), C.c_float(sigma),
-                                      C.c_float(temperature), _ptr(x), _ptr(edge_x), _ptr(pred), _ptr(edge_pred),
-                                      _ptr(raw_pos), _ptr(raw_feat), _ptr(raw_edge), _ptr(x_mean), _ptr(edge_mean),
-                                      _stream())
+        st = self.lib.ds_sampler_step(C.byref(L.c), c_x, c_pred, sigma, temperature, ptr(x), ptr(edge_x), ptr(pred), ptr(edge_pred),
+                                      ptr(raw_pos), ptr(raw_feat), ptr(raw_edge), ptr(x_mean), ptr(edge_mean), _stream())
         _check(st, "ds_sampler_step")
 
     def initial_noise_philox(self, L, seed: int, mol_id: torch.Tensor):
@@ -763,26 +758,24 @@ class DmtEngine:
         dev = self.device
         x = torch.empty(L.B, L.N, 9, dtype=torch.float32, device=dev)
         edge_x = torch.empty(L.B, L.N, L.N, 2, dtype=torch.float32, device=dev)
-        _check(self.lib.ds_initial_noise(C.byref(L.c), C.c_uint64(seed), _ptr(mol_id), _ptr(x), _ptr(edge_x), _stream()),
+        _check(self.lib.ds_initial_noise(C.byref(L.c), seed, ptr(mol_id), ptr(x), ptr(edge_x), _stream()),
                "ds_initial_noise")
         return x, edge_x
 
     def sampler_step_philox(self, L, c_x, c_pred, sigma, temperature, seed: int, step: int, mol_id, x, edge_x, pred, edge_pred,
                             x_mean, edge_mean):
-        st = self.lib.ds_sampler_step_philox(C.byref(L.c), C.c_float(c_x), C.c_float(c_pred), C.c_float(sigma),
-                                             C.c_float(temperature), C.c_uint64(seed), C.c_int32(step), _ptr(mol_id), _ptr(x),
-                                             _ptr(edge_x), _ptr(pred), _ptr(edge_pred), _ptr(x_mean), _ptr(edge_mean), _stream())
+        st = self.lib.ds_sampler_step_philox(C.byref(L.c), c_x, c_pred, sigma, temperature, seed, step, ptr(mol_id), ptr(x),
+                                             ptr(edge_x), ptr(pred), ptr(edge_pred), ptr(x_mean), ptr(edge_mean), _stream())
         _check(st, "ds_sampler_step_philox")
 
     def step_begin(self, table, n_steps: int, step_dev, B: int, noise_level):
-        _check(self.lib.ds_step_begin(_ptr(table), C.c_int32(n_steps), _ptr(step_dev), C.c_int32(B), _ptr(noise_level), _stream()),
+        _check(self.lib.ds_step_begin(ptr(table), n_steps, ptr(step_dev), B, ptr(noise_level), _stream()),
                "ds_step_begin")
 
     def sampler_step_philox_dev(self, L, table, step_dev, temperature, seed: int, mol_id, x, edge_x, pred, edge_pred, x_mean,
                                 edge_mean):
-        st = self.lib.ds_sampler_step_philox_dev(C.byref(L.c), _ptr(table), _ptr(step_dev), C.c_float(temperature),
-                                                 C.c_uint64(seed), _ptr(mol_id), _ptr(x), _ptr(edge_x), _ptr(pred),
-                                                 _ptr(edge_pred), _ptr(x_mean), _ptr(edge_mean), _stream())
+        st = self.lib.ds_sampler_step_philox_dev(C.byref(L.c), ptr(table), ptr(step_dev), temperature, seed, ptr(mol_id), ptr(x),
+                                                 ptr(edge_x), ptr(pred), ptr(edge_pred), ptr(x_mean), ptr(edge_mean), _stream())
         _check(st, "ds_sampler_step_philox_dev")
 
     def check_stability(self, L, pos, atom_type, want_orders: bool = True):
@@ -794,7 +787,7 @@ class DmtEngine:
         order = torch.empty(L.B, L.N, L.N, dtype=torch.int32, device=dev) if want_orders else None
         nr = torch.empty(L.B, dtype=torch.int32, device=dev)
         ok = torch.empty(L.B, dtype=torch.int32, device=dev)
-        _check(self.lib.ds_check_stability(C.byref(L.c), _ptr(pos), _ptr(at), _ptr(order), _ptr(nr), _ptr(ok), _stream()),
+        _check(self.lib.ds_check_stability(C.byref(L.c), ptr(pos), ptr(at), ptr(order), ptr(nr), ptr(ok), _stream()),
                "ds_check_stability")
         n_atoms = torch.as_tensor(L.n_atoms, device=dev)
         return ok.bool(), nr.long(), n_atoms, (order.long() if want_orders else None)
@@ -841,8 +834,8 @@ class DmtEngine:
         atom = torch.empty(L.B, L.N, dtype=torch.int32, device=dev)
         fc = torch.empty(L.B, L.N, dtype=torch.int32, device=dev)
         et = torch.empty(L.B, L.N, L.N, dtype=torch.float32, device=dev)
-        st = self.lib.ds_post_process(C.byref(L.c), _ptr(_f32c(xh, dev)), _ptr(_f32c(edge_x, dev)), _ptr(pos), _ptr(atom),
-                                      _ptr(fc), _ptr(et), _stream())
+        st = self.lib.ds_post_process(C.byref(L.c), ptr(_f32c(xh, dev)), ptr(_f32c(edge_x, dev)), ptr(pos), ptr(atom),
+                                      ptr(fc), ptr(et), _stream())
         _check(st, "ds_post_process")
         return pos, atom, fc, et
 

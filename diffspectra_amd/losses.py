@@ -24,6 +24,7 @@ import torch
 import torch.distributed as dist
 
 from . import engine as E
+from .abi import ptr
 from .ema import ExponentialMovingAverage
 from .scalers import _factors, get_self_cond_fn
 from .spec_train import SpecTrainGraph
@@ -120,8 +121,8 @@ class FusedAdamW:
     def _norm_sq(self):
         self._sync_grads()
         self._synced = True
-        E._check(self.lib.dst_sumsq(E._ptr(self.Gs), C.c_int64(self.shard), E._ptr(self.norm_sq), C.c_int32(0), E._ptr(self.scratch),
-                                    C.c_int64(self.scratch.numel()), E._stream()), "dst_sumsq")
+        E._check(self.lib.dst_sumsq(ptr(self.Gs), self.shard, ptr(self.norm_sq), 0, ptr(self.scratch),
+                                    self.scratch.numel(), E._stream()), "dst_sumsq")
         if self.sharded:
             ns = self.norm_sq if dist.get_backend() != "gloo" else self.norm_sq.cpu()
             dist.all_reduce(ns)
@@ -142,7 +143,7 @@ class FusedAdamW:
             self.clip_state[0] = first                                  # "large value that will be flushed" (losses.py:79)
             self.clip_state[50] = 1.0
         self._norm_sq()
-        E._check(self.lib.dst_clip_update(E._ptr(self.norm_sq), C.c_float(1.0 / self.world), C.c_float(float(max_grad)), E._ptr(self.clip_state),
+        E._check(self.lib.dst_clip_update(ptr(self.norm_sq), 1.0 / self.world, float(max_grad), ptr(self.clip_state),
                                           E._stream()), "dst_clip_update")
         self._clip_pending = True
         return self.clip_state
@@ -198,11 +199,11 @@ class FusedAdamW:
                 ema.num_updates += 1
             lo = self.rank * self.shard
             ema_ptr = self.ema_flat[lo:lo + self.shard]
-        E._check(self.lib.dst_adamw_ema(E._ptr(self.Ps), E._ptr(self.Gs), E._ptr(self.M), E._ptr(self.V), E._ptr(self.Vmax), E._ptr(ema_ptr),
-                                        C.c_int64(self.shard), C.c_float(float(g["lr"])), C.c_double(b1), C.c_double(b2), C.c_float(g["eps"]),
-                                        C.c_float(g["weight_decay"]), C.c_float(1.0 - b1 ** self.steps), C.c_float(1.0 - b2 ** self.steps),
-                                        C.c_float(float(clip_coef) / self.world), E._ptr(self.clip_state[51:52]) if self._clip_pending else None,
-                                        C.c_float(ema_omd), E._stream()), "dst_adamw_ema")
+        E._check(self.lib.dst_adamw_ema(ptr(self.Ps), ptr(self.Gs), ptr(self.M), ptr(self.V), ptr(self.Vmax), ptr(ema_ptr),
+                                        self.shard, float(g["lr"]), b1, b2, g["eps"],
+                                        g["weight_decay"], 1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps,
+                                        float(clip_coef) / self.world, ptr(self.clip_state[51:52]) if self._clip_pending else None,
+                                        ema_omd, E._stream()), "dst_adamw_ema")
         self._clip_pending = False
         if self.sharded:
             if dist.get_backend() == "gloo":                           # rehearsal backend: host tensors
@@ -555,8 +556,8 @@ def get_sde_graph_loss_fn(noise_scheduler, train, scaler, config, prop_norm=None
         pos_p, oh_p = TL.pack_nodes(f32(batch["positions"])), TL.pack_nodes(f32(batch["atom_one_hot"]))
         fc_p, edge_p = TL.pack_nodes(f32(batch["formal_charges"])).reshape(-1).contiguous(), TL.pack_pairs(f32(batch["edge_one_hot"]))
         x, ex = dmt.f(TL.Nn, 9), dmt.f(max(TL.Pp, 1), 2)
-        E._check(lib.dst_prepare_batch(C.byref(TL.c), E._ptr(pos_p), E._ptr(oh_p), E._ptr(fc_p), E._ptr(edge_p), C.c_float(pos_norm), C.c_float(type_norm),
-                                       C.c_float(fc_norm), C.c_float(edge_norm), E._ptr(x), E._ptr(ex), tr.ops._s()), "dst_prepare_batch")
+        E._check(lib.dst_prepare_batch(C.byref(TL.c), ptr(pos_p), ptr(oh_p), ptr(fc_p), ptr(edge_p), pos_norm, type_norm,
+                                       fc_norm, edge_norm, ptr(x), ptr(ex), tr.ops._s()), "dst_prepare_batch")
         context = batch["context"]
         context = [f32(c) for c in context] if isinstance(context, (list, tuple)) else f32(context)
         # the random draws, in the reference's order and shapes (losses.py:314-317, models/utils.py:67-106)
@@ -568,10 +569,10 @@ def get_sde_graph_loss_fn(noise_scheduler, train, scaler, config, prop_norm=None
         raw_e = raw_edge.permute(0, 2, 3, 1).reshape(B * N * N, 2).index_select(0, TL.pair_dense_t).contiguous()   # tril(-1) value of the pair
         z, ez = dmt.f(TL.Nn, 9), dmt.f(max(TL.Pp, 1), 2)
         alpha_t, sigma_t = alpha_t.to(torch.float32).contiguous(), sigma_t.to(torch.float32).contiguous()
-        E._check(lib.dst_noising(C.byref(TL.c), E._ptr(alpha_t), E._ptr(sigma_t), E._ptr(x), E._ptr(raw_n), E._ptr(z), E._ptr(ex), E._ptr(raw_e), E._ptr(ez),
+        E._check(lib.dst_noising(C.byref(TL.c), ptr(alpha_t), ptr(sigma_t), ptr(x), ptr(raw_n), ptr(z), ptr(ex), ptr(raw_e), ptr(ez),
                                  tr.ops._s()), "dst_noising")
         rot, aligned = dmt.f(B, 9), dmt.f(TL.Nn, 3)
-        E._check(lib.dst_kabsch(C.byref(TL.c), E._ptr(z), C.c_int64(9), E._ptr(x), C.c_int64(9), E._ptr(rot), E._ptr(aligned), tr.ops._s()), "dst_kabsch")
+        E._check(lib.dst_kabsch(C.byref(TL.c), ptr(z), 9, ptr(x), 9, ptr(rot), ptr(aligned), tr.ops._s()), "dst_kabsch")
         noise_level = torch.log(alpha_t ** 2 / sigma_t ** 2).contiguous()
         cond_n = cond_e = None
         # FF dropout (dmt.py:114-120) is active whenever the model is in training mode - in the no-grad self-conditioning forward too

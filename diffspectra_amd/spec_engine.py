@@ -8,11 +8,11 @@ the LayerNorm kernel.  Arithmetic restated from reference ``models/specformer.py
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict
 
 import torch
 
+from .abi import ptr
 from .config import SPECTRUM_LENGTHS, used_spectra
 
 
@@ -84,8 +84,7 @@ class SpecEngine:
         head = torch.empty(B, 256, dtype=torch.float32, device=self.device)
         hn = torch.empty(B, 256, dtype=torch.float32, device=self.device)
         E.gemm(lib, zall, L * D, self._w("head.w"), self._w("head.b"), head, 256, B, L * D, 256)
-        E._check(lib.ds_layernorm_affine(E._ptr(head), C.c_void_p(self._w("norm.g")), C.c_void_p(self._w("norm.b")),
-                                         E._ptr(hn), C.c_int(B), C.c_int(256), C.c_float(1e-5), E._stream()),
+        E._check(lib.ds_layernorm_affine(ptr(head), self._w("norm.g"), self._w("norm.b"), ptr(hn), B, 256, 1e-5, E._stream()),
                  "ds_layernorm_affine")
         E.gemm(lib, hn, 256, self._w("cond.w"), self._w("cond.b"), out, 1024, B, 256, 1024)
         return out
@@ -110,9 +109,8 @@ class SpecEngine:
         for l in range(self.LAYERS):
             k = f"l{l}."
             E.gemm(lib, z, D, self._w(k + "qkv.w"), self._w(k + "qkv.b"), qkv, 3 * D, B * L, D, 3 * D)
-            E._check(lib.ds_spec_attention(E._ptr(qkv), E._ptr(scores), E._ptr(o), C.c_int(B), C.c_int(L),
-                                           C.c_int(self.HEADS), C.c_int(self.DK), C.c_float(self.scales[l]),
-                                           C.c_int(1 if l > 0 else 0), E._stream()), "ds_spec_attention")
+            E._check(lib.ds_spec_attention(ptr(qkv), ptr(scores), ptr(o), B, L, self.HEADS, self.DK, self.scales[l], 1 if l > 0 else 0,
+                                           E._stream()), "ds_spec_attention")
             E.gemm(lib, o, D, self._w(k + "out.w"), self._w(k + "out.b"), z1, D, B * L, D, D, R=z, ldr=D,
                    col_scale=self._w(k + "norm_attn.scale"), col_shift=self._w(k + "norm_attn.shift"))
             E.gemm(lib, z1, D, self._w(k + "ff0.w"), self._w(k + "ff0.b"), ff, self.DFF, B * L, D, self.DFF, act=2)

@@ -9,12 +9,12 @@ encoder are 0 in the reference's constructor defaults.  No PyTorch arithmetic: G
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
 
 from . import engine as E
+from .abi import ptr
 from .config import SPECTRUM_LENGTHS, used_spectra
 from .train_engine import ADDREF, GELU, Ops, mv
 
@@ -52,9 +52,9 @@ class SpecTrainGraph:
         p, b = self.p, self.buf
         o = self.ops
         R, Cc = x.shape
-        E._check(self.lib.dst_bn_fwd(E._ptr(x), C.c_int32(R), C.c_int32(Cc), E._ptr(p[name + ".weight"]), E._ptr(p[name + ".bias"]), C.c_float(1e-5),
-                                     E._ptr(y), E._ptr(stats), E._ptr(b[name + ".running_mean"]), E._ptr(b[name + ".running_var"]), E._ptr(o.scratch),
-                                     C.c_int64(o.scratch.numel()), self.ops._s()), "dst_bn_fwd")
+        E._check(self.lib.dst_bn_fwd(ptr(x), R, Cc, ptr(p[name + ".weight"]), ptr(p[name + ".bias"]), 1e-5,
+                                     ptr(y), ptr(stats), ptr(b[name + ".running_mean"]), ptr(b[name + ".running_var"]), ptr(o.scratch),
+                                     o.scratch.numel(), self.ops._s()), "dst_bn_fwd")
         b[name + ".num_batches_tracked"] += 1
         self._bn_last.append((name, stats))
 
@@ -63,8 +63,8 @@ class SpecTrainGraph:
         else of that pass would differ): the reference's self-conditioning step evaluates the encoder twice on one input."""
         b = self.buf
         for name, stats in self._bn_last:
-            E._check(self.lib.dst_bn_running_again(E._ptr(stats), C.c_int32(stats.shape[1]), E._ptr(b[name + ".running_mean"]),
-                                                   E._ptr(b[name + ".running_var"]), self.ops._s()), "dst_bn_running_again")
+            E._check(self.lib.dst_bn_running_again(ptr(stats), stats.shape[1], ptr(b[name + ".running_mean"]),
+                                                   ptr(b[name + ".running_var"]), self.ops._s()), "dst_bn_running_again")
             b[name + ".num_batches_tracked"] += 1
 
     def _bn_bwd(self, dy, x, stats, name, dx, g):
@@ -72,8 +72,8 @@ class SpecTrainGraph:
         R, Cc = x.shape
         gb = self.gbuf
         g[name + ".weight"], g[name + ".bias"] = (gb[name + ".weight"], gb[name + ".bias"]) if gb is not None else (self.f(Cc), self.f(Cc))
-        E._check(self.lib.dst_bn_bwd(E._ptr(dy), E._ptr(x), E._ptr(stats), C.c_int32(R), C.c_int32(Cc), E._ptr(self.p[name + ".weight"]), E._ptr(dx),
-                                     E._ptr(g[name + ".weight"]), E._ptr(g[name + ".bias"]), E._ptr(o.scratch), C.c_int64(o.scratch.numel()), self.ops._s()),
+        E._check(self.lib.dst_bn_bwd(ptr(dy), ptr(x), ptr(stats), R, Cc, ptr(self.p[name + ".weight"]), ptr(dx),
+                                     ptr(g[name + ".weight"]), ptr(g[name + ".bias"]), ptr(o.scratch), o.scratch.numel(), self.ops._s()),
                  "dst_bn_bwd")
 
     # ------------------------------------------------------------------ forward
@@ -110,15 +110,15 @@ class SpecTrainGraph:
             ast, ao = self.f(B, N_HEADS, L, 2), self.f(B * L, D_MODEL)
             qkvs.append(qkv)
             if flash:                                                  # bf16 mode: scores recomputed from the q | k of layers 0 .. l, never stored
-                qp = [E._ptr(q_) for q_ in qkvs] + [None] * (3 - len(qkvs))
-                E._check(self.lib.dst_spec_attn_flash_fwd(qp[0], qp[1], qp[2], C.c_int32(l + 1), E._ptr(ast), E._ptr(ao), C.c_int32(B), C.c_int32(L),
-                                                          C.c_int32(N_HEADS), C.c_int32(D_K), C.c_float(scale), self.ops._s()), "dst_spec_attn_flash_fwd")
+                qp = [ptr(q_) for q_ in qkvs] + [None] * (3 - len(qkvs))
+                E._check(self.lib.dst_spec_attn_flash_fwd(qp[0], qp[1], qp[2], l + 1, ptr(ast), ptr(ao), B, L,
+                                                          N_HEADS, D_K, scale, self.ops._s()), "dst_spec_attn_flash_fwd")
                 scores = None
             else:
                 Lp = (L + 31) // 32 * 32                               # padded row stride of the [L, L] score matrices
                 scores = self.f(B, N_HEADS, L, Lp)
-                E._check(self.lib.dst_spec_attn_fwd(E._ptr(qkv), E._ptr(prev), E._ptr(scores), E._ptr(ast), E._ptr(ao), C.c_int32(B), C.c_int32(L),
-                                                    C.c_int32(N_HEADS), C.c_int32(D_K), C.c_float(scale), self.ops._s()), "dst_spec_attn_fwd")
+                E._check(self.lib.dst_spec_attn_fwd(ptr(qkv), ptr(prev), ptr(scores), ptr(ast), ptr(ao), B, L,
+                                                    N_HEADS, D_K, scale, self.ops._s()), "dst_spec_attn_fwd")
             r1 = self.f(B * L, D_MODEL)                               # Z + to_out(attention): the residual is added in the product's epilogue
             o.gemm(mv(ao), mv(p[base + "self_attn.to_out.0.weight"]), mv(r1), False, True, bias=p[base + "self_attn.to_out.0.bias"], dact=ADDREF, ref=mv(Z))
             z1, st1 = self.f(B * L, D_MODEL), self.f(3, D_MODEL)
@@ -138,8 +138,8 @@ class SpecTrainGraph:
         zh = self.f(B, 256)
         o.lin_fwd(mv(flat), mv(p[pre + "head.linear.weight"]), p[pre + "head.linear.bias"], mv(zh))
         zs, st_ln = self.f(B, 256), self.f(B, 2)
-        E._check(self.lib.dst_ln_affine_fwd(E._ptr(zh), C.c_int32(B), C.c_int32(256), E._ptr(p[pre + "out_norm.weight"]), E._ptr(p[pre + "out_norm.bias"]),
-                                            C.c_float(1e-5), E._ptr(zs), E._ptr(st_ln), self.ops._s()), "dst_ln_affine_fwd")
+        E._check(self.lib.dst_ln_affine_fwd(ptr(zh), B, 256, ptr(p[pre + "out_norm.weight"]), ptr(p[pre + "out_norm.bias"]),
+                                            1e-5, ptr(zs), ptr(st_ln), self.ops._s()), "dst_ln_affine_fwd")
         ctx = self.f(B, 1024)
         o.lin_fwd(mv(zs), mv(p["cond_lin.weight"]), p["cond_lin.bias"], mv(ctx))
         if save:
@@ -165,8 +165,8 @@ class SpecTrainGraph:
         dzs = self.f(B, 256)
         o.lin_bwd_x(mv(dctx), mv(p["cond_lin.weight"]), mv(dzs))
         dzh = self.f(B, 256)
-        E._check(self.lib.dst_ln_affine_bwd(E._ptr(dzs), E._ptr(t["zh"]), E._ptr(t["st_ln"]), C.c_int32(B), C.c_int32(256), E._ptr(p[pre + "out_norm.weight"]),
-                                            E._ptr(dzh), E._ptr(gw(pre + "out_norm.weight")), E._ptr(gw(pre + "out_norm.bias")), self.ops._s()),
+        E._check(self.lib.dst_ln_affine_bwd(ptr(dzs), ptr(t["zh"]), ptr(t["st_ln"]), B, 256, ptr(p[pre + "out_norm.weight"]),
+                                            ptr(dzh), ptr(gw(pre + "out_norm.weight")), ptr(gw(pre + "out_norm.bias")), self.ops._s()),
                  "dst_ln_affine_bwd")
         o.lin_bwd_w(mv(dzh), mv(t["flat"]), mv(gw(pre + "head.linear.weight")), gw(pre + "head.linear.bias"))
         dZ = self.f(B * L, D_MODEL)
@@ -196,12 +196,12 @@ class SpecTrainGraph:
             dao = self.f(B * L, D_MODEL)
             o.lin_bwd_x(mv(dr1), mv(p[base + "self_attn.to_out.0.weight"]), mv(dao))
             if flash:
-                qp = [E._ptr(q_) for q_ in qkv_all[:l + 1]] + [None] * (2 - l)
-                gp = [E._ptr(q_) for q_ in dqkv_all[:l + 1]] + [None] * (2 - l)
+                qp = [ptr(q_) for q_ in qkv_all[:l + 1]] + [None] * (2 - l)
+                gp = [ptr(q_) for q_ in dqkv_all[:l + 1]] + [None] * (2 - l)
                 def flash_bwd(part):
-                    E._check(self.lib.dst_spec_attn_flash_bwd(qp[0], qp[1], qp[2], C.c_int32(l + 1), E._ptr(lt["ast"]), E._ptr(lt["ao"]), E._ptr(dao), gp[0], gp[1],
-                                                              gp[2], C.c_int32(B), C.c_int32(L), C.c_int32(N_HEADS), C.c_int32(D_K), C.c_float(scale),
-                                                              C.c_int32(part), C.c_int32(0 if l == N_LAYERS - 1 else 1), self.ops._s()), "dst_spec_attn_flash_bwd")
+                    E._check(self.lib.dst_spec_attn_flash_bwd(qp[0], qp[1], qp[2], l + 1, ptr(lt["ast"]), ptr(lt["ao"]), ptr(dao), gp[0], gp[1],
+                                                              gp[2], B, L, N_HEADS, D_K, scale,
+                                                              part, 0 if l == N_LAYERS - 1 else 1, self.ops._s()), "dst_spec_attn_flash_bwd")
                 if two_streams:                                        # the key side beside the query side (disjoint columns of dqkv): each kernel
                     with o.node_section():                             # alone keeps two 4-wave workgroups on a CU
                         flash_bwd(2)
@@ -212,8 +212,8 @@ class SpecTrainGraph:
                 dqkv, dscores = dqkv_all[l], None
             else:
                 dqkv, dscores = self.f(B * L, 3 * D_MODEL), self.f(B, N_HEADS, L, (L + 31) // 32 * 32)
-                E._check(self.lib.dst_spec_attn_bwd(E._ptr(lt["qkv"]), E._ptr(lt["scores"]), E._ptr(lt["ast"]), E._ptr(dao), E._ptr(dscores_in), E._ptr(dqkv), E._ptr(dscores),
-                                                    C.c_int32(B), C.c_int32(L), C.c_int32(N_HEADS), C.c_int32(D_K), C.c_float(scale), self.ops._s()),
+                E._check(self.lib.dst_spec_attn_bwd(ptr(lt["qkv"]), ptr(lt["scores"]), ptr(lt["ast"]), ptr(dao), ptr(dscores_in), ptr(dqkv), ptr(dscores),
+                                                    B, L, N_HEADS, D_K, scale, self.ops._s()),
                          "dst_spec_attn_bwd")
             dzin = self.f(B * L, D_MODEL)                                                        # dZin = dr1 (residual) + dqkv Wqkv (dr1 stays intact, as dr2 above)
             dWc, dbc = self.f(3 * D_MODEL, D_MODEL), self.f(3 * D_MODEL)

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import abi, engine as E
+from .abi import ptr
 
 ADA, ADA_STRIDE, ADA_TOP = E.ADA_COLS, E.ADA_STRIDE, E.CONSTS["DS_ADA_TOP"]
 NODE_OFF, EDGE_OFF, EQUI_OFF, DIST_OFF = (E.CONSTS[k] for k in ("DS_ADA_NODE", "DS_ADA_EDGE", "DS_ADA_EQUI", "DS_ADA_DIST"))
@@ -72,7 +73,7 @@ def _piece_table(dev, dst: List[torch.Tensor], src: List[torch.Tensor], cache: d
     if ent is None or ent[0] != sig:
         arr = (DstPiece * len(dst))(*(row(i, d, s_) for i, (d, s_) in enumerate(zip(dst, src))))
         ent = cache[key] = (sig, torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), len(dst))
-    return C.c_void_p(ent[1].data_ptr()), C.c_int32(ent[2])
+    return ent[1].data_ptr(), ent[2]
 
 
 def copy_pieces(lib, dev, dst: List[torch.Tensor], src: List[torch.Tensor], cache: dict, key: str, stream=None):
@@ -106,14 +107,13 @@ _lib = None
 
 
 def load_train_library() -> C.CDLL:
-    """The training entry points live in the same shared library as the sampling path; fail loudly if any is missing."""
+    """The training entry points live in the same shared library as the sampling path (``engine.load_library`` binds both headers and fails
+    loudly if an entry point is missing); here the training argument structs are compared with the library's."""
     global _lib
     if _lib is None:
         lib = E.load_library()
-        for name in train_exports():
-            getattr(lib, name).restype = C.c_int
         sizes = (C.c_int64 * len(STRUCT_NAMES))()
-        E._check(lib.dst_struct_sizes(sizes, C.c_int32(len(sizes))), "dst_struct_sizes")
+        E._check(lib.dst_struct_sizes(sizes, len(sizes)), "dst_struct_sizes")
         bad = [(n, lib_n, STRUCTS[n].size) for n, lib_n in zip(STRUCT_NAMES, sizes) if STRUCTS[n].size != lib_n]
         if bad:
             raise RuntimeError(f"C-ABI struct layout mismatch (training): (struct, library, binding) {bad}")
@@ -153,11 +153,6 @@ def mv(t: torch.Tensor, c0: Optional[int] = None, c1: Optional[int] = None, r0: 
     return MV(t, r1 - r0, c1 - c0, t2c, r0 * t2c + c0)
 
 
-def ptr(t) -> int:
-    """Data pointer of a tensor, 0 for None (an output the fused chain kernels need not write)."""
-    return 0 if t is None else t.data_ptr()
-
-
 def _need_bf16(*weights):
     """The fused row chains stream their weights as bf16 (dst_pack_bf16_pieces / .to(torch.bfloat16): nearest even)."""
     assert all(w_.dtype == torch.bfloat16 for w_ in weights)
@@ -192,7 +187,7 @@ class Ops:
 
     def begin(self):
         self.main_stream = torch.cuda.current_stream(self.dev)
-        self.stream_ptr = C.c_void_p(self.main_stream.cuda_stream)
+        self.stream_ptr = self.main_stream.cuda_stream
 
     def end(self):
         self.stream_ptr = None
@@ -227,7 +222,9 @@ class Ops:
             assert ref.rows == M and ref.cols == N
         if out2 is not None:
             assert out2.rows == M and out2.cols == N
-        E._check(self.lib.dst_gemm(args, self._s()), "dst_gemm")
+        st = self.lib.dst_gemm(args, self._s())       # ~650 calls per step and no scalar argument to convert: the status is tested here,
+        if st:                                        # _check is the error path only
+            E._check(st, "dst_gemm")
 
     def colsum(self, X: MV, out: torch.Tensor, acc: bool = False, param_grad: bool = False):
         """``param_grad``: the sums are a parameter gradient (nothing downstream of the pass reads them) - with the weight-gradient stream on
@@ -236,8 +233,8 @@ class Ops:
         if param_grad and self.async_dw:
             with self._to_side(X.t, out, out=out):
                 return self.colsum(X, out, acc)
-        E._check(self.lib.dst_colsum(C.c_void_p(X.ptr), C.c_int64(X.ld), C.c_int32(X.rows), C.c_int32(X.cols), E._ptr(out), C.c_int32(int(acc)),
-                                     E._ptr(self.scratch), C.c_int64(self.scratch.numel()), self._s()), "dst_colsum")
+        E._check(self.lib.dst_colsum(X.ptr, X.ld, X.rows, X.cols, ptr(out), int(acc),
+                                     ptr(self.scratch), self.scratch.numel(), self._s()), "dst_colsum")
 
     def _to_side(self, *keep, out=None):
         """Pick the weight-gradient stream of this product (``out``: its output tensor - the same output always goes to the same stream) and let
@@ -311,32 +308,32 @@ class Ops:
         self._dw_keep = []
 
     def act_fwd(self, x, y, kind):
-        E._check(self.lib.dst_act_fwd(E._ptr(x), E._ptr(y), C.c_int64(x.numel()), C.c_int32(kind), self._s()), "dst_act_fwd")
+        E._check(self.lib.dst_act_fwd(ptr(x), ptr(y), x.numel(), kind, self._s()), "dst_act_fwd")
 
     def act_bwd(self, dy, ref, dx, kind):
-        E._check(self.lib.dst_act_bwd(E._ptr(dy), E._ptr(ref), E._ptr(dx), C.c_int64(dy.numel()), C.c_int32(kind), self._s()), "dst_act_bwd")
+        E._check(self.lib.dst_act_bwd(ptr(dy), ptr(ref), ptr(dx), dy.numel(), kind, self._s()), "dst_act_bwd")
 
     def dropout(self, x, p, seed, stream_id):
         """In place; the same (seed, stream_id) on the gradient is the backward."""
         if p > 0.0:
-            E._check(self.lib.dst_dropout(E._ptr(x), E._ptr(x), C.c_int64(x.numel()), C.c_float(p), C.c_uint64(seed), C.c_uint32(stream_id), self._s()),
+            E._check(self.lib.dst_dropout(ptr(x), ptr(x), x.numel(), p, seed, stream_id, self._s()),
                      "dst_dropout")
 
     def axpy(self, a, x, y):
-        E._check(self.lib.dst_axpy(C.c_float(a), E._ptr(x), E._ptr(y), C.c_int64(x.numel()), self._s()), "dst_axpy")
+        E._check(self.lib.dst_axpy(a, ptr(x), ptr(y), x.numel(), self._s()), "dst_axpy")
 
     def lnmod_fwd(self, x, Cc, seg, mul, B, ada, sh, sc, y, stats):
-        E._check(self.lib.dst_lnmod_fwd(E._ptr(x), C.c_int32(Cc), E._ptr(seg), C.c_int32(mul), C.c_int32(B), E._ptr(ada), C.c_int64(ADA), C.c_int32(sh),
-                                        C.c_int32(sc), E._ptr(y), E._ptr(stats), self._s()), "dst_lnmod_fwd")
+        E._check(self.lib.dst_lnmod_fwd(ptr(x), Cc, ptr(seg), mul, B, ptr(ada), ADA, sh,
+                                        sc, ptr(y), ptr(stats), self._s()), "dst_lnmod_fwd")
 
     def lnmod_bwd(self, dy, x, stats, Cc, seg, mul, B, ada, d_ada, sh, sc, dx, acc):
-        E._check(self.lib.dst_lnmod_bwd(E._ptr(dy), E._ptr(x), E._ptr(stats), C.c_int32(Cc), E._ptr(seg), C.c_int32(mul), C.c_int32(B), E._ptr(ada),
-                                        E._ptr(d_ada), C.c_int64(ADA), C.c_int32(sh), C.c_int32(sc), E._ptr(dx), C.c_int32(int(acc)), E._ptr(self.scratch),
-                                        C.c_int64(self.scratch.numel()), self._s()), "dst_lnmod_bwd")
+        E._check(self.lib.dst_lnmod_bwd(ptr(dy), ptr(x), ptr(stats), Cc, ptr(seg), mul, B, ptr(ada),
+                                        ptr(d_ada), ADA, sh, sc, ptr(dx), int(acc), ptr(self.scratch),
+                                        self.scratch.numel(), self._s()), "dst_lnmod_bwd")
 
     def gate_add_fwd(self, r, z, Cc, seg, mul, B, ada, g, out):
-        E._check(self.lib.dst_gate_add_fwd(E._ptr(r), E._ptr(z), C.c_int32(Cc), E._ptr(seg), C.c_int32(mul), C.c_int32(B), E._ptr(ada), C.c_int64(ADA),
-                                           C.c_int32(g), E._ptr(out), self._s()), "dst_gate_add_fwd")
+        E._check(self.lib.dst_gate_add_fwd(ptr(r), ptr(z), Cc, ptr(seg), mul, B, ptr(ada), ADA,
+                                           g, ptr(out), self._s()), "dst_gate_add_fwd")
 
     def pair_chain_fwd(self, TL, u, n2e_bias, e_in, feat, ld_feat, ada, g1, sh, sc, g2, W3, b3, W4, b4, Wed, ld_wed, bed, Wro, bro, drop, out):
         """The pair rows of a block behind the attention as one kernel (``dst_pair_chain_fwd``, bf16 products).  ``drop = (p, seed, stream3,
@@ -410,20 +407,20 @@ class Ops:
         E._check(self.lib.dst_pair_front_fwd(C.byref(TL.c), args, self._s()), "dst_pair_front_fwd")
 
     def geom_fwd(self, TL, pos, ada, dist_off, means, stds, X, ldx, col0, xs, d2s):
-        E._check(self.lib.dst_geom_fwd(C.byref(TL.c), E._ptr(pos), E._ptr(ada), C.c_int64(ADA), C.c_int32(dist_off), E._ptr(means), E._ptr(stds),
-                                       C.c_void_p(X.data_ptr() + 4 * col0), C.c_int64(ldx), E._ptr(xs), E._ptr(d2s), self._s()), "dst_geom_fwd")
+        E._check(self.lib.dst_geom_fwd(C.byref(TL.c), ptr(pos), ptr(ada), ADA, dist_off, ptr(means), ptr(stds),
+                                       X.data_ptr() + 4 * col0, ldx, ptr(xs), ptr(d2s), self._s()), "dst_geom_fwd")
 
     def geom_bwd(self, TL, pos, ada, d_ada, dist_off, means, stds, xs, d2s, g1, g2, dms, dd2, dpos):
-        E._check(self.lib.dst_geom_bwd(C.byref(TL.c), E._ptr(pos), E._ptr(ada), E._ptr(d_ada), C.c_int64(ADA), C.c_int32(dist_off), E._ptr(means),
-                                       E._ptr(stds), E._ptr(xs), E._ptr(d2s), E._ptr(g1), C.c_int64(g1.shape[1]), E._ptr(g2),
-                                       C.c_int64(0 if g2 is None else g2.shape[1]), E._ptr(dms), E._ptr(dd2), E._ptr(dpos), self._s()), "dst_geom_bwd")
+        E._check(self.lib.dst_geom_bwd(C.byref(TL.c), ptr(pos), ptr(ada), ptr(d_ada), ADA, dist_off, ptr(means),
+                                       ptr(stds), ptr(xs), ptr(d2s), ptr(g1), g1.shape[1], ptr(g2),
+                                       0 if g2 is None else g2.shape[1], ptr(dms), ptr(dd2), ptr(dpos), self._s()), "dst_geom_bwd")
 
     def gate_add_bwd(self, dout, z, Cc, seg, mul, B, ada, d_ada, g, dr, acc_r, dz, drop=None):
         """``drop = (p, seed, stream_id)``: ``z`` was a dropout's output; ``dz`` is then the gradient in FRONT of that dropout."""
         p_, seed, stream = drop if drop and drop[0] > 0 else (0.0, 0, 0)
-        E._check(self.lib.dst_gate_add_bwd(E._ptr(dout), E._ptr(z), C.c_int32(Cc), E._ptr(seg), C.c_int32(mul), C.c_int32(B), E._ptr(ada), E._ptr(d_ada),
-                                           C.c_int64(ADA), C.c_int32(g), E._ptr(dr), C.c_int32(int(acc_r)), E._ptr(dz), C.c_float(p_), C.c_uint64(seed),
-                                           C.c_uint32(stream), self._s()), "dst_gate_add_bwd")
+        E._check(self.lib.dst_gate_add_bwd(ptr(dout), ptr(z), Cc, ptr(seg), mul, B, ptr(ada), ptr(d_ada),
+                                           ADA, g, ptr(dr), int(acc_r), ptr(dz), p_, seed,
+                                           stream, self._s()), "dst_gate_add_bwd")
 
 
 class _OnStream:
@@ -432,7 +429,7 @@ class _OnStream:
     __slots__ = ("o", "stream", "ptr", "scratch", "saved")
 
     def __init__(self, ops, stream, scratch):
-        self.o, self.stream, self.ptr, self.scratch = ops, stream, C.c_void_p(stream.cuda_stream), scratch
+        self.o, self.stream, self.ptr, self.scratch = ops, stream, stream.cuda_stream, scratch
 
     def __enter__(self):
         o = self.o
@@ -671,7 +668,7 @@ class DmtTrainGraph:
         s = self.ops._s
         # ---- time embedding + adaLN table (dmt.py:249-257,353-357; every *time_mlp)
         tf = self.f(B, 17)
-        E._check(lib.dst_time_feat_fwd(E._ptr(noise_level), E._ptr(p["time_mlp.0.weights"]), C.c_int32(B), E._ptr(tf), s()), "dst_time_feat_fwd")
+        E._check(lib.dst_time_feat_fwd(ptr(noise_level), ptr(p["time_mlp.0.weights"]), B, ptr(tf), s()), "dst_time_feat_fwd")
         tm1, tg, temb, st = self.f(B, 1024), self.f(B, 1024), self.f(B, 1024), self.f(B, 1024)
         o.lin_fwd(mv(tf), mv(p["time_mlp.1.weight"]), p["time_mlp.1.bias"], mv(tm1), act=GELU, out2=mv(tg))
         o.lin_fwd(mv(tg), mv(p["time_mlp.3.weight"]), p["time_mlp.3.bias"], mv(temb))
@@ -697,8 +694,8 @@ class DmtTrainGraph:
             xs0, d2c = self.f(Pp), self.f(Pp)
             o.geom_fwd(TL, cpos, ada, ADA_TOP, p["dist_layer.means.weight"], p["dist_layer.stds.weight"], X0p, 68, 4, xs0, d2c)
             adj = torch.empty(Pp, dtype=torch.int32, device=self.dev)
-            E._check(lib.dst_adj_bits(E._ptr(cond_e), C.c_int64(cond_e.shape[1]), E._ptr(d2c), C.c_float(self.edge_th), C.c_float(self.cutoff), C.c_int32(Pp),
-                                      E._ptr(adj), s()), "dst_adj_bits")
+            E._check(lib.dst_adj_bits(ptr(cond_e), cond_e.shape[1], ptr(d2c), self.edge_th, self.cutoff, Pp,
+                                      ptr(adj), s()), "dst_adj_bits")
             t.update(cpos=cpos)
         else:
             adj = torch.full((Pp,), 3, dtype=torch.int32, device=self.dev)
@@ -764,8 +761,8 @@ class DmtTrainGraph:
         if ns:
             o.main_wait()                                        # q | k | v
         attn, alpha = self.f(Nn, 256), self.f(max(D, 1), 16)
-        E._check(lib.dst_attn_fwd(C.byref(TL.c), E._ptr(bt["qkv"]), E._ptr(te[:, 0:256]), E._ptr(te[:, 256:512]), C.c_int64(512), E._ptr(adj), E._ptr(attn),
-                                  E._ptr(alpha), s()), "dst_attn_fwd")
+        E._check(lib.dst_attn_fwd(C.byref(TL.c), ptr(bt["qkv"]), ptr(te[:, 0:256]), ptr(te[:, 256:512]), 512, ptr(adj), ptr(attn),
+                                  ptr(alpha), s()), "dst_attn_fwd")
         bt.update(attn=attn, alpha=alpha)
         # node stream (dmt.py:156-163): node2edge per node first (the pair rows wait for it), then the node rows behind the attention (the
         # directed rows wait for their `ac`, not for the read-out slice behind it)
@@ -782,8 +779,8 @@ class DmtTrainGraph:
             o.main_wait(ev_ac)
         dir_rows(TL, ada, k, bt, save)
         pos_out = self.f(Nn, 3)
-        E._check(lib.dst_coord_fwd(C.byref(TL.c), E._ptr(bt["pos_in"]), E._ptr(bt["c2"]), E._ptr(adj), E._ptr(p[k.bp + "equi_update.coord_norm.scale"]),
-                                   E._ptr(pos_out), s()), "dst_coord_fwd")
+        E._check(lib.dst_coord_fwd(C.byref(TL.c), ptr(bt["pos_in"]), ptr(bt["c2"]), ptr(adj), ptr(p[k.bp + "equi_update.coord_norm.scale"]),
+                                   ptr(pos_out), s()), "dst_coord_fwd")
         return pos_out
 
     def _node_front_fwd(self, TL, ada, k, bt):
@@ -865,7 +862,7 @@ class DmtTrainGraph:
     def _pair_rear_fwd_ops(self, TL, ada, k, bt, drop, save):
         o, p, bp, i, B, Pp = self.ops, self.p, k.bp, k.i, TL.B, TL.Pp
         he = self.f(Pp, 64)
-        E._check(self.lib.dst_pair_sum_fwd(C.byref(TL.c), E._ptr(bt["u"]), C.c_int32(64), E._ptr(p[bp + "node2edge_lin.bias"]), E._ptr(he), o._s()),
+        E._check(self.lib.dst_pair_sum_fwd(C.byref(TL.c), ptr(bt["u"]), 64, ptr(p[bp + "node2edge_lin.bias"]), ptr(he), o._s()),
                  "dst_pair_sum_fwd")
         xe1, ye1, st_e2 = self.f(Pp, 64), self.f(Pp, 64), self.f(Pp, 2)
         o.gate_add_fwd(bt["e_in"], he, 64, TL.pair_off, 1, B, ada, k.edge.gate1, xe1)
@@ -898,7 +895,7 @@ class DmtTrainGraph:
         o, p, bp = self.ops, self.p, k.bp
         D = 2 * TL.Pp
         zz, zn, st_z = self.f(max(D, 1), 256), self.f(max(D, 1), 256), self.f(max(D, 1), 2)
-        E._check(self.lib.dst_zbuild_fwd(C.byref(TL.c), E._ptr(bt["ac"]), E._ptr(bt["ed"]), E._ptr(zz), o._s()), "dst_zbuild_fwd")
+        E._check(self.lib.dst_zbuild_fwd(C.byref(TL.c), ptr(bt["ac"]), ptr(bt["ed"]), ptr(zz), o._s()), "dst_zbuild_fwd")
         o.lnmod_fwd(zz, 256, TL.pair_off, 2, TL.B, ada, *k.equi_ln, zn, st_z)
         c0, sc0, c2 = self.f(max(D, 1), 256), self.f(max(D, 1), 256), self.f(max(D, 1), 3)
         o.lin_fwd(mv(zn, r1=D), mv(p[bp + "equi_update.coord_mlp.0.weight"]), p[bp + "equi_update.coord_mlp.0.bias"], mv(c0, r1=D), act=SILU,
@@ -975,8 +972,8 @@ class DmtTrainGraph:
         o.lin_bwd_w(mv(dtg), mv(t["tf"]), mv(gw("time_mlp.1.weight")), gw("time_mlp.1.bias"))
         dtf = self.f(B, 17)
         o.lin_bwd_x(mv(dtg), mv(p["time_mlp.1.weight"]), mv(dtf))
-        E._check(lib.dst_time_feat_bwd(E._ptr(t["noise_level"]), E._ptr(p["time_mlp.0.weights"]), E._ptr(dtf), C.c_int32(B),
-                                       E._ptr(gw("time_mlp.0.weights")), s()), "dst_time_feat_bwd")
+        E._check(lib.dst_time_feat_bwd(ptr(t["noise_level"]), ptr(p["time_mlp.0.weights"]), ptr(dtf), B,
+                                       ptr(gw("time_mlp.0.weights")), s()), "dst_time_feat_bwd")
         o.join_dw()                                          # the concatenated gradients are read right here, on the main stream
         o.async_dw = False
         self.scatter_cat_grads(g, gw)
@@ -1010,14 +1007,14 @@ class DmtTrainGraph:
         # equivariant update
         dpos_in, dc2 = self.f(Nn, 3), self.f(max(D, 1), 3)
         dsp, dms_buf = self.f(B), self.f(B, 128)          # per block: their column sums (parameter gradients) run on the side stream
-        E._check(lib.dst_coord_bwd(C.byref(TL.c), E._ptr(bt["pos_in"]), E._ptr(bt["c2"]), E._ptr(t["adj"]), E._ptr(p[bp + "equi_update.coord_norm.scale"]),
-                                   E._ptr(dpos_out), E._ptr(dpos_in), E._ptr(dc2), E._ptr(dsp), s()), "dst_coord_bwd")
+        E._check(lib.dst_coord_bwd(C.byref(TL.c), ptr(bt["pos_in"]), ptr(bt["c2"]), ptr(t["adj"]), ptr(p[bp + "equi_update.coord_norm.scale"]),
+                                   ptr(dpos_out), ptr(dpos_in), ptr(dc2), ptr(dsp), s()), "dst_coord_bwd")
         o.colsum(mv(dsp.view(B, 1)), gw(bp + "equi_update.coord_norm.scale"), param_grad=True)
         dWin = gw(bp + "equi_update.input_lin.weight")
         o.lin_bwd_w(mv(dc2, r1=D), mv(bt["sc0"], r1=D), mv(gw(bp + "equi_update.coord_mlp.2.weight")))
         dz = dir_rows(TL, ada, d_ada, k, bt, gw, dc2)
         dac, ded = self.f(Nn, 512), self.f(Pp, 256)
-        E._check(lib.dst_zbuild_bwd(C.byref(TL.c), E._ptr(dz), E._ptr(dac), E._ptr(ded), s()), "dst_zbuild_bwd")
+        E._check(lib.dst_zbuild_bwd(C.byref(TL.c), ptr(dz), ptr(dac), ptr(ded), s()), "dst_zbuild_bwd")
         # node stream (the section waits for dac)
         with sec():
             o.lin_bwd_w(mv(dac), mv(bt["h_out"]), mv(dcat["Wac"][i]))           # both node parts at once; scattered into dWin[:, 0:512] at the end
@@ -1027,7 +1024,7 @@ class DmtTrainGraph:
         dfeat2, de_in, dhe = pair_rear(TL, ada, d_ada, k, bt, gw, drop, de, dEH.data_ptr() + 4 * (64 + 16 * i), ded)
         # node2edge
         du = self.f(Nn, 64)
-        E._check(lib.dst_pair_sum_bwd(C.byref(TL.c), E._ptr(dhe), C.c_int32(64), E._ptr(du), C.c_int32(0), s()), "dst_pair_sum_bwd")
+        E._check(lib.dst_pair_sum_bwd(C.byref(TL.c), ptr(dhe), 64, ptr(du), 0, s()), "dst_pair_sum_bwd")
         o.colsum(mv(dhe), gw(bp + "node2edge_lin.bias"), param_grad=True)
         with sec():                                                              # (waits for du)
             o.lin_bwd_w(mv(du), mv(bt["attn"]), mv(gw(bp + "node2edge_lin.weight")))
@@ -1037,9 +1034,9 @@ class DmtTrainGraph:
         # attention
         dqkv, dte = self.f(Nn, 768), self.f(Pp, 512)
         te = bt["te"]
-        E._check(lib.dst_attn_bwd(C.byref(TL.c), E._ptr(bt["qkv"]), E._ptr(te[:, 0:256]), E._ptr(te[:, 256:512]), C.c_int64(512), E._ptr(bt["alpha"]),
-                                  E._ptr(dattn), E._ptr(dqkv), E._ptr(dte[:, 0:256]), E._ptr(dte[:, 256:512]), C.c_int32(1), E._ptr(o.scratch),
-                                  C.c_int64(o.scratch.numel()), s()), "dst_attn_bwd")
+        E._check(lib.dst_attn_bwd(C.byref(TL.c), ptr(bt["qkv"]), ptr(te[:, 0:256]), ptr(te[:, 256:512]), 512, ptr(bt["alpha"]),
+                                  ptr(dattn), ptr(dqkv), ptr(dte[:, 0:256]), ptr(dte[:, 256:512]), 1, ptr(o.scratch),
+                                  o.scratch.numel(), s()), "dst_attn_bwd")
         with sec():                                                              # (waits for dqkv) q | k | v and the adaLN modulate of the block input
             dhn = self.f(Nn, 256)
             o.lin_bwd_w(mv(dqkv), mv(bt["hn"]), mv(dcat["Wqkv"][i]), dcat["bqkv"][i])
@@ -1159,7 +1156,7 @@ class DmtTrainGraph:
     def loss(self, TL: TrainLayout, pos, atom_pred, edge_pred, tpos, tfeat, tedge, wm, weights=(1.0, 0.25, 0.1)):
         """losses.py:359-394 on packed predictions: (per-molecule loss [B], dpos, datom, dedge)."""
         loss_m, dpos, dfeat, dedge = self.f(TL.B), self.f(TL.Nn, 3), self.f(TL.Nn, 6), self.f(max(TL.Pp, 1), 2)
-        E._check(self.lib.dst_loss(C.byref(TL.c), E._ptr(pos), E._ptr(atom_pred), E._ptr(edge_pred), E._ptr(tpos), E._ptr(tfeat), E._ptr(tedge),
-                                   E._ptr(wm), C.c_float(weights[0]), C.c_float(weights[1]), C.c_float(weights[2]), E._ptr(loss_m), E._ptr(dpos),
-                                   E._ptr(dfeat), E._ptr(dedge), self.ops._s()), "dst_loss")
+        E._check(self.lib.dst_loss(C.byref(TL.c), ptr(pos), ptr(atom_pred), ptr(edge_pred), ptr(tpos), ptr(tfeat), ptr(tedge),
+                                   ptr(wm), weights[0], weights[1], weights[2], ptr(loss_m), ptr(dpos),
+                                   ptr(dfeat), ptr(dedge), self.ops._s()), "dst_loss")
         return loss_m, dpos, dfeat, dedge

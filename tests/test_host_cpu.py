@@ -31,6 +31,119 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(tl, name), name
 
 
+def _headers():
+    from diffspectra_amd import abi
+    return abi, (abi.SAMPLING, abi.TRAINING)
+
+
+def test_prototypes_match_a_hand_written_table():
+    """``abi.Header.prototypes`` against prototypes copied by hand from the two headers: a void return, a plain ``int``, a struct pointer, a
+    pointer to pointers, mixed 32 / 64-bit integers with ``float`` and ``double*``, ``uint64_t`` / ``uint32_t``, a ``double`` by value among floats."""
+    abi, (smp, trn) = _headers()
+    P, i32, i64, u32, u64, f, d = "*", "int32_t", "int64_t", "uint32_t", "uint64_t", "float", "double"
+    want = {
+        "ds_struct_sizes": ("void", [("out", P)]),
+        "ds_set_two_stream": ("int", [("on", "int")]),
+        "ds_gemm": ("int", [("args", P), ("stream", P)]),
+        "ds_fingerprint": ("int", [("ptrs", P), ("prefix", P), ("n", i32), ("out", P), ("stream", P)]),
+        "ds_match_records": ("int", [("prb_rec", P), ("prb_n", P), ("P", i64), ("ref_rec", P), ("ref_n", P), ("M", i64), ("ref_index", P),
+                                     ("max_distance", f), ("min_atoms", i32), ("rmsd", P), ("n_matched", P), ("type_acc", P), ("bond_acc", P),
+                                     ("exact", P), ("map", P), ("stream", P)]),
+        "ds_initial_noise": ("int", [("L", P), ("seed", u64), ("mol_id", P), ("x", P), ("edge_x", P), ("stream", P)]),
+        "dst_adamw_ema": ("int", [("p", P), ("g", P), ("m", P), ("v", P), ("vmax", P), ("ema", P), ("n", i64), ("lr", f), ("beta1", d), ("beta2", d),
+                                  ("eps", f), ("weight_decay", f), ("bc1", f), ("bc2", f), ("clip_coef", f), ("clip_coef_dev", P),
+                                  ("ema_one_minus_decay", f), ("stream", P)]),
+        "dst_dropout": ("int", [("x", P), ("y", P), ("n", i64), ("p", f), ("seed", u64), ("stream_id", u32), ("stream", P)]),
+    }
+    for name, (ret, params) in want.items():
+        proto = (trn if name.startswith("dst_") else smp).prototypes[name]
+        assert (proto.name, proto.ret, proto.params) == (name, ret, params), name
+    table = {P: ctypes.c_void_p, "int": ctypes.c_int, i32: ctypes.c_int32, i64: ctypes.c_int64, u32: ctypes.c_uint32, u64: ctypes.c_uint64,
+             f: ctypes.c_float, d: ctypes.c_double}
+    assert trn.prototypes["dst_dropout"].argtypes == [table[t] for _, t in want["dst_dropout"][1]]
+    assert trn.prototypes["dst_adamw_ema"].argtypes[7:10] == [ctypes.c_float, ctypes.c_double, ctypes.c_double]
+
+
+def test_every_export_is_bound_with_its_signature():
+    """Over both whole headers: the exports ARE the parsed prototypes, the totals are those of the headers, and every function of the loaded
+    library carries the parsed ``restype`` and ``argtypes``.  The headers hold 80 prototypes with 679 parameters - counted independently of the
+    parser below, as commas + 1 - of which 478 are pointers (479 stars: ``const float* const* ptrs`` has two)."""
+    import __graft_entry__ as g
+    from collections import Counter
+    g.build()
+    lib = E.load_library()
+    abi, headers = _headers()
+    kinds, n_params, n_by_commas = Counter(), 0, 0
+    for hdr, prefix, n_fn in zip(headers, ("ds_", "dst_"), (31, 49)):
+        assert hdr.exports(prefix) == list(hdr.prototypes) and len(hdr.prototypes) == n_fn
+        n_by_commas += sum(text.count(",") + 1 for text in re.findall(r"\b(?:int|void)\s+%s\w+\s*\(([^()]*)\)\s*;" % prefix, hdr.text))
+        for name, proto in hdr.prototypes.items():
+            assert proto.params and all(t in abi._ARG_CTYPES for _, t in proto.params), name
+            kinds.update(t for _, t in proto.params)
+            n_params += len(proto.params)
+            fn = getattr(lib, name)
+            assert fn.restype is (None if proto.ret == "void" else ctypes.c_int), name
+            assert len(fn.argtypes) == len(proto.params) and list(fn.argtypes) == proto.argtypes, name
+    assert E.EXPORTS == headers[0].exports("ds_")
+    assert n_params == n_by_commas == 679
+    assert dict(kinds) == {"*": 478, "int32_t": 90, "int64_t": 48, "float": 39, "int": 13, "uint64_t": 5, "double": 4, "uint32_t": 2}
+    assert [n for h in headers for n, p in h.prototypes.items() if p.ret == "void"] == ["ds_struct_sizes"]
+
+
+@pytest.mark.parametrize("decl, param", [
+    ("int ds_x(const float* a, size_t n, void* stream);", "size_t n"),               # a scalar type outside the table
+    ("int ds_x(const float* a,\n         ds_layout L, void* stream);", "ds_layout L"),   # a struct by value
+    ("int ds_x(int32_t n[4]);", "int32_t n[4]"),                                      # an array declarator
+    ("int ds_x(unsigned int n);", "unsigned int n"),
+])
+def test_prototype_parser_refuses_what_it_does_not_know(decl, param):
+    """A parameter that is neither a pointer nor a scalar of the table raises when the header is parsed, naming function and parameter:
+    there is no default type."""
+    abi, _ = _headers()
+    ok = abi.Header("synthetic.h", "/* c */ int ds_y(const float* const* p, const int64_t n, double\n s); // c\nvoid ds_z(void);\n")
+    assert ok.prototypes["ds_y"].params == [("p", "*"), ("n", "int64_t"), ("s", "double")] and ok.prototypes["ds_z"] == ("ds_z", "void", [])
+    with pytest.raises(ValueError) as err:
+        abi.Header("synthetic.h", "typedef struct ds_layout { int32_t B; } ds_layout;\n" + decl)
+    assert "ds_x" in str(err.value) and param in str(err.value)
+
+
+def test_ctypes_refuses_calls_that_disagree_with_the_header():
+    """With ``argtypes`` set a wrong call never enters the library (every pointer here is NULL and P = 0: a call that did get through would
+    return a status instead of raising).  A mistyped argument is ``ctypes.ArgumentError``; too few arguments are ctypes' plain ``TypeError``."""
+    import __graft_entry__ as g
+    g.build()
+    lib = E.load_library()
+    assert lib.ds_graph_hash_records(None, None, 0, None, None) == 0
+    with pytest.raises(TypeError, match="at least 5 arguments"):                      # a missing argument
+        lib.ds_graph_hash_records(None, None, 0, None)
+    with pytest.raises(ctypes.ArgumentError, match="argument 3"):                     # a Python float where int64_t P is declared
+        lib.ds_graph_hash_records(None, None, 0.0, None, None)
+    with pytest.raises(ctypes.ArgumentError, match="argument 8"):                     # a c_int64 where int32_t max_nodes is declared
+        lib.ds_graph_identity_records(None, None, 0, None, None, 0, None, ctypes.c_int64(0), None, None, None, None)
+    with pytest.raises(ctypes.ArgumentError, match="argument 3"):                     # and a c_int32 where int64_t P is declared
+        lib.ds_graph_hash_records(None, None, ctypes.c_int32(0), None, None)
+    # what call sites do pass: ints, None, byref, ctypes arrays, the bytes of a packed struct - c_void_p takes them all
+    size = ctypes.c_int64(-1)
+    assert lib.ds_mmd_1d_workspace_bytes(3, ctypes.byref(size)) == 0 and size.value > 0
+    assert ctypes.c_void_p.from_param(b"\0" * 8) is not None and ctypes.c_void_p.from_param((ctypes.c_int64 * 2)()) is not None
+
+
+def test_call_sites_leave_the_argument_types_to_the_binder():
+    """In the package, outside ``abi.py``: no scalar or pointer cast as a call argument (a by-reference out-parameter is the exception), and
+    neither ``restype`` nor ``argtypes`` is set anywhere but in ``abi.Header.bind``."""
+    root = os.path.dirname(os.path.abspath(E.__file__))
+    cast = re.compile(r"\bC\.c_(?:int|int32|int64|uint32|uint64|float|double|void_p)\(")
+    for name in sorted(os.listdir(root)):
+        if not name.endswith(".py") or name == "abi.py":
+            continue
+        for no, line in enumerate(open(os.path.join(root, name)), 1):
+            assert ".restype" not in line and ".argtypes" not in line, (name, no)
+            if cast.search(line):
+                assert re.match(r"\s*\w+ = C\.c_int64\(0\)$", line.rstrip()), (name, no, line)      # `size`, passed with byref
+    src = open(os.path.join(root, "abi.py")).read()
+    assert src.count(".restype =") == src.count(".argtypes =") == 1
+
+
 def test_training_structs_parsed_from_the_header():
     """The binding packs the training C-ABI's argument structs in the layouts parsed from include/diffspectra_train.h: pinned to the
     layouts the kernels were validated with (the library checks the sizes at load time)."""

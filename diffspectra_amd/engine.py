@@ -54,6 +54,7 @@ def load_library() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     abi.SAMPLING.bind(lib)               # restype and argtypes of every export, as the headers declare them; AttributeError if the
     abi.TRAINING.bind(lib)               # headers declare something the .so lacks
+    abi.SETS.bind(lib)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
     mine = [C.sizeof(t) for t in (DsWeights, DsLayout, DsWorkspace, DsGemmArgs)]
@@ -661,6 +662,93 @@ def mmd_1d_segments(x: torch.Tensor, x_off: torch.Tensor, y: torch.Tensor, y_off
     return out, status
 
 
+# ----------------------------------------------------------------------------------------- bit rows: nearest neighbour and mean similarity of sets
+
+SETS_CONSTS = abi.SETS.consts             # include/diffspectra_sets.h
+SETS_TILE_A, SETS_TILE_B, SETS_CHUNKS = (SETS_CONSTS["DSS_" + k] for k in ("TILE_A", "TILE_B", "CHUNKS"))
+
+
+def _fold_width(n_bits):
+    if isinstance(n_bits, bool) or not isinstance(n_bits, int):
+        raise TypeError(f"n_bits must be an int, got {type(n_bits).__name__}")
+    if not (64 <= n_bits <= MORGAN_MAX_BITS and n_bits & (n_bits - 1) == 0):
+        raise ValueError(f"n_bits must be a power of two in [64, {MORGAN_MAX_BITS}], got {n_bits}")
+    return n_bits
+
+
+def _one_device(name, tensors):
+    dev = tensors[0].device
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise RuntimeError(f"{name} needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    return dev
+
+
+def fold_bits(ids: torch.Tensor, count: torch.Tensor, n_bits: int = 1024):
+    """``dss_fold_bits``: the feature lists of ``morgan_records`` (``ids [P, 116] i64`` bit patterns, ``count [P] i32``) folded to packed bit rows:
+    ``(words [P, n_bits / 64] i64, popcount [P] i32)`` on the current stream without synchronising.  Bit ``f mod n_bits`` is set for every
+    feature f; bit b lives in word ``b // 64`` at position ``b % 64`` (int64 bit patterns: read them as unsigned with ``& (2**64 - 1)``).
+    ``n_bits`` is a power of two in [64, 4096].  A count outside [0, 116] is clamped.  Checked, never converted; no CPU path."""
+    n_bits = _fold_width(n_bits)
+    _want(ids, "ids", torch.int64, (None, MORGAN_MAX_FEATURES))
+    _want(count, "count", torch.int32, (ids.shape[0],))
+    dev = _one_device("fold_bits", [ids, count])
+    lib = load_library()
+    P = ids.shape[0]
+    words = torch.empty(P, n_bits // 64, dtype=torch.int64, device=dev)
+    popcount = torch.empty(P, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = lib.dss_fold_bits(ptr(ids), ptr(count), P, n_bits, ptr(words), ptr(popcount), _stream())
+    _check(st, "dss_fold_bits")
+    return words, popcount
+
+
+def tanimoto_nn_workspace_bytes(Na: int, Nb: int) -> int:
+    """``dss_tanimoto_nn_workspace_bytes``: the device bytes ``tanimoto_nn`` needs for ``Na`` rows against ``Nb`` (a pure host function)."""
+    size = C.c_int64(0)
+    _check(load_library().dss_tanimoto_nn_workspace_bytes(int(Na), int(Nb), C.byref(size)), "dss_tanimoto_nn_workspace_bytes")
+    return int(size.value)
+
+
+def tanimoto_nn(a_words: torch.Tensor, a_pop: torch.Tensor, b_words: torch.Tensor, b_pop: torch.Tensor, n_bits: int, skip_same_index: bool = False,
+                workspace: Optional[torch.Tensor] = None):
+    """``dss_tanimoto_nn``: every bit row of A against every bit row of B (``fold_bits`` makes them: ``a_words [Na, n_bits / 64] i64``, ``a_pop
+    [Na] i32``, ``b_words [Nb, n_bits / 64] i64``, ``b_pop [Nb] i32``); with ``skip_same_index`` row i of A leaves out row i of B (A against
+    itself without the self-pairs).  Tanimoto ``T = c / u``, ``c = popcount(a & b)``, ``u = |a| + |b| - c``, and ``T = 1`` for two empty rows.
+
+    Returns the device tensors ``(best_common [Na] i32, best_union [Na] i32, best_index [Na] i64, sum [Na] f64, compared [Na] i64)`` on the
+    current stream without synchronising: c, u and the row of the most similar row of B (decided in integers; among equals the lowest row;
+    -1 / -1 / -1 when nothing was compared), the fp64 sum of T over the compared rows and their number.  Bit-identical from run to run.
+    ``workspace``: a ``uint8`` device tensor of at least ``tanimoto_nn_workspace_bytes(Na, Nb)`` bytes, allocated here when ``None``.  Checked,
+    never converted; no CPU path."""
+    n_bits = _fold_width(n_bits)
+    if not isinstance(skip_same_index, bool):
+        raise TypeError(f"skip_same_index must be a bool, got {type(skip_same_index).__name__}")
+    _want(a_words, "a_words", torch.int64, (None, n_bits // 64))
+    _want(a_pop, "a_pop", torch.int32, (a_words.shape[0],))
+    _want(b_words, "b_words", torch.int64, (None, n_bits // 64))
+    _want(b_pop, "b_pop", torch.int32, (b_words.shape[0],))
+    Na, Nb = a_words.shape[0], b_words.shape[0]
+    tensors = [a_words, a_pop, b_words, b_pop]
+    need = tanimoto_nn_workspace_bytes(Na, Nb)
+    if workspace is not None:
+        _want(workspace, "workspace", torch.uint8, (None,))
+        if workspace.shape[0] < need:
+            raise ValueError(f"workspace holds {workspace.shape[0]} bytes, {need} are needed for {Na} rows against {Nb}")
+        tensors.append(workspace)
+    dev = _one_device("tanimoto_nn", tensors)
+    lib = load_library()
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    i32 = lambda: torch.empty(Na, dtype=torch.int32, device=dev)
+    out = (i32(), i32(), torch.empty(Na, dtype=torch.int64, device=dev), torch.empty(Na, dtype=torch.float64, device=dev),
+           torch.empty(Na, dtype=torch.int64, device=dev))
+    with torch.cuda.device(dev):
+        st = lib.dss_tanimoto_nn(ptr(a_words), ptr(a_pop), Na, ptr(b_words) if Nb else None, ptr(b_pop) if Nb else None, Nb, n_bits,
+                                 int(skip_same_index), ptr(workspace), workspace.shape[0], *(ptr(t) for t in out), _stream())
+    _check(st, "dss_tanimoto_nn")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -827,6 +915,18 @@ class DmtEngine:
     def mmd_1d_segments(self, x, x_off, y, y_off, kernel_mul: float = 2.0, kernel_num: int = 5, fix_sigma=None, workspace=None):
         """``engine.mmd_1d_segments`` on this engine's library (the MMD needs no weights)."""
         return mmd_1d_segments(x, x_off, y, y_off, kernel_mul, kernel_num, fix_sigma, workspace)
+
+    def fold_bits(self, ids, count, n_bits: int = 1024):
+        """``engine.fold_bits`` on this engine's library."""
+        return fold_bits(ids, count, n_bits)
+
+    def tanimoto_nn_workspace_bytes(self, Na: int, Nb: int) -> int:
+        """``engine.tanimoto_nn_workspace_bytes`` on this engine's library."""
+        return tanimoto_nn_workspace_bytes(Na, Nb)
+
+    def tanimoto_nn(self, a_words, a_pop, b_words, b_pop, n_bits: int, skip_same_index: bool = False, workspace=None):
+        """``engine.tanimoto_nn`` on this engine's library (the set similarities need no weights)."""
+        return tanimoto_nn(a_words, a_pop, b_words, b_pop, n_bits, skip_same_index, workspace)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

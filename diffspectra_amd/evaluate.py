@@ -105,7 +105,7 @@ def _structure_summary(run, table, top_k: int) -> Dict:
 
 
 def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = "eval",
-                         metric_fns: Optional[Dict[str, Callable]] = None, structure_metrics: bool = False):
+                         metric_fns: Optional[Dict[str, Callable]] = None, structure_metrics: bool = False, known_records=None):
     """Sampling evaluation over the configured checkpoints; returns ``{ckpt: {'processed_mols', 'gt_pos', 'gt_rdmols',
     'metrics'}}``.  ``metric_fns[name](processed_mols, gt_pos, gt_rdmols)`` are optional host-side callbacks.
 
@@ -139,6 +139,14 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     ``bond_length_mean`` / ``bond_angle_mean`` / ``dihedral_angle_mean`` (``structure_metrics.get_sub_geometry_metric``, which states the
     deviations: every angle counts once, RDKit parity unpinned, a seeded sample cap).  Without the flag the dict has no such key.
 
+    With ``config.eval.set_similarity`` true ``metrics['structure']['set_similarity']`` holds the set-level numbers of the reference's
+    "Metric-2D" line that need no RDKit model (``run_lib.py:346-390``): ``snn`` and ``int_div`` of the generated records against ALL records of
+    the test table, ``nearest`` / ``nearest_index`` (device tensors: every kept generated molecule's similarity to, and the table row of, its
+    nearest test molecule), ``n_generated`` / ``n_test`` and, when ``known_records = (records [*, 1248] u8, n_atoms [*])`` of the training
+    molecules is given, ``novelty`` (``structure_metrics.get_set_similarity_metric``, which states the deviations: the MOSES definitions are
+    restated and unpinned, one representative per constitution-level class stands for ``set(smiles)``, no RDKit sanitisation filter; FCD, Frag
+    and Scaf are not computed).  Without the flag the dict has no such key.
+
     ``test_ds=None`` reads the reference's processed files under ``config.data.root`` (``run_lib.py:313`` ->
     ``build_dataset.py:31-42``: the 'test' entry of ``split_dict_diffspectra_qm9.pt``) into the device-resident table of
     ``qm9s_reader.ProcessedQM9S.packed_table`` - no PyG, no per-molecule Python."""
@@ -162,6 +170,7 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                                             inverse_scaler, test_ds, top_k=top_k)
     results = {}
     geometry_fn = None                            # the test side of the geometry MMD is extracted once, at the first checkpoint
+    set_fn = None                                 # and so are the bit rows of the test molecules
     for ckpt in checkpoint_ids(config):
         ckpt_path = os.path.join(workdir, "checkpoints", "checkpoint_{}.pth".format(ckpt))
         if not os.path.exists(ckpt_path):
@@ -184,5 +193,12 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                 if geometry_fn is None:
                     geometry_fn = get_sub_geometry_metric((test_ds.gt_records.to(run.records_by_slot.device), test_ds.num_atom), engine=run.eng)
                 metrics["structure"]["sub_geometry"] = geometry_fn((run.records_by_slot, torch.tensor(run.n_atoms)))
+            if getattr(config.eval, "set_similarity", False):
+                from .structure_metrics import get_set_similarity_metric
+                if set_fn is None:
+                    dev = run.records_by_slot.device
+                    known = None if known_records is None else (known_records[0].to(dev), known_records[1])
+                    set_fn = get_set_similarity_metric((test_ds.gt_records.to(dev), test_ds.num_atom), known=known, engine=run.eng)
+                metrics["structure"]["set_similarity"] = set_fn((run.records_by_slot, torch.tensor(run.n_atoms)))
         results[ckpt] = dict(processed_mols=processed_mols, gt_pos=gt_pos, gt_rdmols=gt_rdmols, metrics=metrics, step=state["step"])
     return results

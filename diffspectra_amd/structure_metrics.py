@@ -33,6 +33,15 @@ dihedral-angle MMD between generated and test molecules per substructure symbol 
 (the reference counts it 0, 1 or 2 times depending on the atom numbering), parity with RDKit's angle functions is unpinned, and the
 20 000-sample cap is a seeded ``torch.randperm``.
 
+How a generated SET stands against another set is ``get_set_similarity_metric``: the SNN, IntDiv and novelty of the reference's "Metric-2D"
+line (``run_lib.py:346-390``, ``evaluation/mose_metric.py``, ``evaluation/rdkit_metric.py:45-65,113-122``).  ``morgan_bit_rows`` packs the
+fingerprints into bit rows (``dss_fold_bits``), ``nearest_neighbour_similarity`` scans every generated row against every test row
+(``dss_tanimoto_nn``, ``csrc/ds_sets.hip``; the nearest neighbour is decided in integers, the sums have one fixed order), ``snn`` and
+``internal_diversity`` reduce it, ``novelty`` is ``graph_classes`` on the known and the generated molecules together.  The MOSES definitions
+(``SNNMetric``; ``internal_diversity`` with p = 1, self-pairs included; 1024-bit radius-2 Morgan fingerprints) are restated from the package as
+remembered - MOSES is neither vendored by the reference nor runnable here, so parity with it is unpinned - and the fingerprints carry the
+deviations of ``morgan_similarity_batch``.  FCD, Frag and Scaf of that line are not reproduced.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -502,3 +511,152 @@ def get_sub_geometry_metric(test, dataset_info: Optional[Dict] = None, max_sampl
             result[mean_name] = sum(seen) / len(seen) if seen else float("nan")
         return result
     return sub_geometry_metric
+
+
+# ------------------------------------------------------------------------------------------------------------------ set against set
+
+class SetSimilarity(NamedTuple):
+    """Per-row device tensors of ``dss_tanimoto_nn``: every row of a set against all rows of another."""
+    best_common: torch.Tensor     # [Na] i32: |a & b| of the most similar row b; -1 when no row was compared
+    best_union: torch.Tensor      # [Na] i32: |a | b| of that pair (0 with 0 common: two empty rows, similarity 1); -1 when no row was compared
+    best_index: torch.Tensor      # [Na] i64: its row, the lowest among equally similar ones; -1 when no row was compared
+    sum: torch.Tensor             # [Na] f64: the sum of the Tanimoto similarity over the compared rows
+    compared: torch.Tensor        # [Na] i64: how many rows were compared
+
+    @property
+    def nearest(self) -> torch.Tensor:
+        """Tanimoto similarity to the nearest neighbour as f64: 1.0 for two empty rows, NaN when no row was compared."""
+        c, u = self.best_common.double(), self.best_union.double()
+        out = torch.where(self.best_union == 0, torch.ones_like(c), c / u)
+        return torch.where(self.best_index >= 0, out, torch.full_like(out, float("nan")))
+
+    @property
+    def mean(self) -> torch.Tensor:
+        """Mean Tanimoto similarity to the compared rows as f64, NaN when no row was compared."""
+        return self.sum / self.compared.double()                                   # 0.0 / 0 = NaN
+
+
+class Novelty(NamedTuple):
+    """What ``novelty`` returns."""
+    novel: torch.Tensor                   # [P] bool: no known molecule is the same labelled graph
+    novel_fraction_of_unique: float       # distinct novel graphs / distinct generated graphs (``rdkit_metric.py:45-52,63-65``); NaN without any
+    novel_over_all: float                 # distinct novel graphs / generated rows (``eval_rdmol``, ``rdkit_metric.py:120-122``); NaN without any
+
+
+def morgan_bit_rows(records: torch.Tensor, n_atoms, drop_h: bool = True, radius: int = 2, n_bits: int = 1024, engine=None):
+    """The Morgan fingerprint of every record as a packed bit row: ``(words [P, n_bits / 64] i64 bit patterns, popcount [P] i32)`` on the
+    records' device (``ds_morgan_records``, then ``dss_fold_bits``) - the operands of ``nearest_neighbour_similarity``.  Bit ``f mod n_bits`` is
+    set for every feature f, as ``morgan_fingerprints(..., n_bits=...)`` sets it; bit b is bit ``b % 64`` of word ``b // 64``.  The default of
+    1024 bits is MOSES's Morgan setting (restated from the package as remembered); the per-pair metric keeps the reference's 2048.  The
+    fingerprint is not RDKit's bit for bit (``morgan_similarity_batch`` lists the deviations).  No Python per molecule."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    ids, count = eng.morgan_records(records, n, drop_h, radius)
+    return eng.fold_bits(ids, count, n_bits)
+
+
+def nearest_neighbour_similarity(gen, ref, skip_same_index: bool = False, engine=None) -> SetSimilarity:
+    """Every bit row of ``gen`` against every bit row of ``ref`` (both ``(words, popcount)`` of ``morgan_bit_rows``, of one width): the
+    nearest neighbour of each generated row and the sum of its Tanimoto similarities (``dss_tanimoto_nn``).  ``skip_same_index`` leaves out row
+    i of ``ref`` for row i of ``gen`` (a set against itself without the self-pairs).  Device tensors, no synchronisation."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    n_bits = 64 * gen[0].shape[-1] if gen[0].dim() == 2 else 0                         # a wrong shape is the binding's to refuse
+    return SetSimilarity(*eng.tanimoto_nn(gen[0], gen[1], ref[0], ref[1], n_bits, skip_same_index))
+
+
+def _host_sum(t: torch.Tensor) -> float:
+    """Sum of a vector on the host, in index order (the evaluate driver's rule: one order of summation everywhere)."""
+    acc = 0.0
+    for v in t.detach().to("cpu", torch.float64).tolist():
+        acc += v
+    return acc
+
+
+def snn(gen, ref, skip_same_index: bool = False, engine=None) -> float:
+    """MOSES's SNN (``SNNMetric``, restated from the package as remembered; parity unpinned): the mean over the generated rows of the
+    Tanimoto similarity to the nearest row of ``ref``, over the rows that have one; NaN without any.  Arguments as
+    ``nearest_neighbour_similarity``.  A Python float (synchronises)."""
+    near = nearest_neighbour_similarity(gen, ref, skip_same_index, engine).nearest.cpu()
+    have = ~torch.isnan(near)
+    n = int(have.sum())
+    return _host_sum(near[have]) / n if n else float("nan")
+
+
+def internal_diversity(gen, engine=None) -> float:
+    """MOSES's IntDiv (``internal_diversity`` with p = 1, restated from the package as remembered; parity unpinned): one minus the mean
+    Tanimoto similarity over all ordered pairs of the set, self-pairs included as MOSES includes them - ``1 - sum_i sum_i / sum_i compared_i``,
+    the row sums added on the host in index order.  ``gen``: ``(words, popcount)`` of ``morgan_bit_rows``.  NaN for an empty set.  A Python
+    float (synchronises)."""
+    out = nearest_neighbour_similarity(gen, gen, False, engine)
+    pairs = int(out.compared.sum())
+    return 1.0 - _host_sum(out.sum) / pairs if pairs else float("nan")
+
+
+def novelty(generated, known, engine=None) -> Novelty:
+    """Which generated molecules are no known molecule: ``generated`` and ``known`` are ``(records [*, 1248] u8 on the GPU, n_atoms [*])``
+    pairs; ``graph_classes`` runs on the concatenation known + generated, and a generated row is novel iff the lowest row of its class lies
+    in the generated part.  Returns ``Novelty(novel [P] bool on the device, novel_fraction_of_unique, novel_over_all)``: distinct novel graphs
+    over distinct generated graphs (``compute_novelty`` on the unique list, ``evaluation/rdkit_metric.py:45-52,63-65``) and over all generated
+    rows (``eval_rdmol``, ``rdkit_metric.py:120-122``); NaN without a generated row.  Identity is constitution-level (atom type, formal charge,
+    bond order under a bijection, whole molecules): unlike the reference's canonical SMILES it has no stereo and no tautomer / charge
+    normalisation, and the reference's RDKit sanitisation filter is not reproduced."""
+    (g_rec, g_n), (k_rec, k_n) = generated, known
+    dev = g_rec.device
+    i32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.int32).reshape(-1)
+    K, P = k_rec.shape[0], g_rec.shape[0]
+    cls = graph_classes(torch.cat([k_rec.to(dev), g_rec]).contiguous(), torch.cat([i32(k_n), i32(g_n)]), engine)[K:]
+    novel = cls >= K
+    if P == 0:
+        return Novelty(novel, float("nan"), float("nan"))
+    n_novel = int(cls[novel].unique().numel())
+    return Novelty(novel, n_novel / int(cls.unique().numel()), n_novel / P)
+
+
+def _class_representatives(records, n, engine):
+    """Rows of the lowest member of every ``graph_classes`` class, ascending."""
+    cls = graph_classes(records, n, engine)
+    return torch.nonzero(cls == torch.arange(cls.shape[0], device=cls.device)).reshape(-1)
+
+
+def get_set_similarity_metric(test, known=None, n_bits: int = 1024, unique: bool = True, engine=None):
+    """The set-level numbers of the reference's "Metric-2D" line that need no RDKit model (``get_moses_metrics``, ``evaluation/mose_metric.py``;
+    ``run_lib.py:346-390``) on record tensors: ``test`` is ``(records [*, 1248] u8 on the GPU, n_atoms [*])`` of the test molecules, whose bit
+    rows are made once, here; ``known``, optional, is such a pair of the training molecules.  Returns ``fn(generated, keep=None)``,
+    ``generated`` another such pair, which gives a dict: ``snn`` and ``int_div`` (Python floats: ``snn`` of the generated against the test
+    set, ``internal_diversity`` of the generated set), ``nearest`` (f64 device tensor: every compared generated row's similarity to its
+    nearest test molecule) and ``nearest_index`` (i64: that molecule's row in the CALLER's test table), ``n_generated`` / ``n_test`` (rows that
+    entered) and, with ``known``, ``novelty`` (the ``Novelty`` of the rows that entered).
+
+    ``unique=True`` keeps one representative - the lowest row - of every ``graph_classes`` class on both sides, where the reference takes
+    ``list(set(smiles))``.  ``keep`` is an optional bool mask over the generated rows (the device-side stability mask, say): the reference's own
+    filter is RDKit sanitisation, which is not reproduced.  FCD, Frag and Scaf are not computed.  The MOSES definitions are restated from the
+    package as remembered and parity with MOSES is unpinned; identity is constitution-level (``graph_identity_batch``)."""
+    from . import engine as E
+    dev = test[0].device
+    i32 = lambda t, d: torch.as_tensor(t).to(device=d, dtype=torch.int32).reshape(-1).contiguous()
+    t_rec, t_n = test[0], i32(test[1], dev)
+    t_rows = _class_representatives(t_rec, t_n, engine) if unique else torch.arange(t_rec.shape[0], device=dev)
+    ref = morgan_bit_rows(t_rec[t_rows].contiguous(), t_n[t_rows], n_bits=n_bits, engine=engine)
+
+    def set_similarity_metric(generated, keep=None):
+        g_rec, g_n = generated[0], i32(generated[1], generated[0].device)
+        if keep is not None:
+            rows = torch.nonzero(torch.as_tensor(keep).to(g_rec.device).bool().reshape(-1)).reshape(-1)
+            g_rec, g_n = g_rec[rows].contiguous(), g_n[rows].contiguous()
+        if unique:
+            rows = _class_representatives(g_rec, g_n, engine)
+            g_rec, g_n = g_rec[rows].contiguous(), g_n[rows].contiguous()
+        gen = morgan_bit_rows(g_rec, g_n, n_bits=n_bits, engine=engine)
+        near = nearest_neighbour_similarity(gen, ref, engine=engine)
+        nearest = near.nearest
+        have = near.best_index >= 0
+        n_have = int(have.sum())
+        out = dict(snn=_host_sum(nearest[have]) / n_have if n_have else float("nan"), int_div=internal_diversity(gen, engine),
+                   nearest=nearest, nearest_index=torch.where(have, t_rows[near.best_index.clamp(min=0)], near.best_index) if n_have else near.best_index,
+                   n_generated=int(g_rec.shape[0]), n_test=int(t_rows.shape[0]))
+        if known is not None:
+            out["novelty"] = novelty((g_rec, g_n), known, engine)
+        return out
+    return set_similarity_metric

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/diffspectra_hip.h"
+#include "ds_bonds.h"
 #include "ds_host.h"
 
 namespace {
@@ -206,12 +207,8 @@ __global__ void k_post_process(ds_layout L, const float* __restrict__ xh, const 
 }
 
 // Stability check, one workgroup per molecule (evaluation/stability.py:40-73; tables of evaluation/bond_analyze.py:5-45 for
-// H, C, N, O, F; 0 = no such bond).  Thread a walks the other atoms of its molecule.
-__constant__ int c_bond1[5][5] = {{74, 109, 101, 96, 92}, {109, 154, 147, 143, 135}, {101, 147, 145, 140, 136},
-                                  {96, 143, 140, 148, 142}, {92, 135, 136, 142, 142}};
-__constant__ int c_bond2[5][5] = {{0, 0, 0, 0, 0}, {0, 134, 129, 120, 0}, {0, 129, 125, 121, 0}, {0, 120, 121, 121, 0}, {0, 0, 0, 0, 0}};
-__constant__ int c_bond3[5][5] = {{0, 0, 0, 0, 0}, {0, 120, 116, 113, 0}, {0, 116, 110, 0, 0}, {0, 113, 0, 0, 0}, {0, 0, 0, 0, 0}};
-__constant__ int c_valence[5] = {1, 4, 3, 2, 1};
+// H, C, N, O, F in ds_bonds.h, which the valence analytics on result records share).  Thread a walks the other atoms of its molecule.
+using ds_bonds::c_valence;
 __global__ __launch_bounds__(64) void k_check_stability(ds_layout L, const float* __restrict__ pos, const int32_t* __restrict__ atom_type,
                                                         int32_t* __restrict__ bond_order, int32_t* __restrict__ nr_stable,
                                                         int32_t* __restrict__ mol_stable) {
@@ -234,16 +231,8 @@ __global__ __launch_bounds__(64) void k_check_stability(ds_layout L, const float
     for (int b = 0; b < n; ++b) {
       if (b == a) continue;
       const float dx = px[a] - px[b], dy = py[a] - py[b], dz = pz[a] - pz[b];
-      const float d = __fmul_rn(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))), 100.0f);
-      const int tb = ty[b];
-      int order = 0;
-      if (d < (float)(c_bond1[ta][tb] + 10)) {
-        order = 1;
-        if (c_bond2[ta][tb] != 0 && d < (float)(c_bond2[ta][tb] + 5)) {
-          order = 2;
-          if (c_bond3[ta][tb] != 0 && d < (float)(c_bond3[ta][tb] + 3)) order = 3;
-        }
-      }
+      const float d = ds_bonds::scaled_distance(dx, dy, dz);
+      const int order = ds_bonds::order_of(ta, ty[b], d);
       bonds += order;
       if (bond_order) bond_order[(size_t)dn[a] * N + (dn[b] - m * N)] = order;
     }

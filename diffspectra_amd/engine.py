@@ -55,6 +55,7 @@ def load_library() -> C.CDLL:
     abi.SAMPLING.bind(lib)               # restype and argtypes of every export, as the headers declare them; AttributeError if the
     abi.TRAINING.bind(lib)               # headers declare something the .so lacks
     abi.SETS.bind(lib)
+    abi.VALENCE.bind(lib)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
     mine = [C.sizeof(t) for t in (DsWeights, DsLayout, DsWorkspace, DsGemmArgs)]
@@ -392,11 +393,13 @@ def _want(t, name, dtype, shape):
         raise ValueError(f"{name} must be contiguous")
 
 
-def _record_call(name, tables, ref_index, scalars, outputs):
+def _record_call(name, tables, ref_index, scalars, outputs, prefix="ds_", also=()):
     """The binding of an entry point on result records.  ``tables``: ``[(rec, n)]`` (``ds_graph_hash_records``, ``ds_morgan_records``; ``ref_index`` unused) or
     ``[(prb_rec, prb_n), (ref_rec, ref_n)]`` with ``ref_index`` (the record pairs of the header).  Checks the tensors (never converts them),
     the pairing rule and the one-device rule, allocates ``outputs`` - ``[(dtype, trailing shape)]``, one row per pair - and issues ``ds_<name>``
-    with the C ``scalars`` between the tables and the outputs, on the current stream of the tensors' device.  Returns the output tensors."""
+    with the C ``scalars`` between the tables and the outputs, on the current stream of the tensors' device.  Returns the output tensors.
+    ``prefix`` names the header's family when it is not ``ds_``; ``also`` are further input tensors, already checked by the caller and passed
+    among the ``scalars`` as addresses, that the one-device rule covers."""
     pairs = len(tables) == 2
     tensors, args = [], []
     for (rec, n), (rec_name, n_name) in zip(tables, (("prb_rec", "prb_n"), ("ref_rec", "ref_n")) if pairs else (("rec", "n"),)):
@@ -412,14 +415,15 @@ def _record_call(name, tables, ref_index, scalars, outputs):
         elif tensors[2].shape[0] < P:
             raise ValueError(f"without ref_index pair p reads ground-truth row p: {tensors[2].shape[0]} rows for {P} pairs")
         args.append(ptr(ref_index))
+    tensors += list(also)
     dev = tensors[0].device
     if dev.type != "cuda" or any(t.device != dev for t in tensors):
         raise RuntimeError(f"{name} needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
     lib = load_library()
     out = tuple(torch.empty(P, *shape, dtype=dtype, device=dev) for dtype, shape in outputs)
     with torch.cuda.device(dev):
-        st = getattr(lib, "ds_" + name)(*args, *scalars, *(ptr(t) for t in out), _stream())
-    _check(st, "ds_" + name)
+        st = getattr(lib, prefix + name)(*args, *scalars, *(ptr(t) for t in out), _stream())
+    _check(st, prefix + name)
     return out
 
 
@@ -749,6 +753,49 @@ def tanimoto_nn(a_words: torch.Tensor, a_pop: torch.Tensor, b_words: torch.Tenso
     return out
 
 
+# ----------------------------------------------------------------------------------------- valence analytics: stability, validity, fragments
+
+VALENCE_CONSTS = abi.VALENCE.consts       # include/diffspectra_valence.h
+BONDS_RECORD, BONDS_DISTANCE = VALENCE_CONSTS["DSV_BONDS_RECORD"], VALENCE_CONSTS["DSV_BONDS_DISTANCE"]
+VALENCE_OK, VALENCE_UNUSABLE = VALENCE_CONSTS["DSV_OK"], VALENCE_CONSTS["DSV_UNUSABLE"]
+
+
+def _bonds_from(bonds_from):
+    if isinstance(bonds_from, bool) or not isinstance(bonds_from, int):
+        raise TypeError(f"bonds_from must be an int, got {type(bonds_from).__name__}")
+    if bonds_from not in (BONDS_RECORD, BONDS_DISTANCE):
+        raise ValueError(f"bonds_from must be BONDS_RECORD ({BONDS_RECORD}) or BONDS_DISTANCE ({BONDS_DISTANCE}), got {bonds_from}")
+    return bonds_from
+
+
+def valence_records(rec: torch.Tensor, n: torch.Tensor, bonds_from: int = 0):
+    """``dsv_valence_records``: valences, stability, validity and fragments of every record (definitions in ``include/diffspectra_valence.h``).
+    ``bonds_from``: ``BONDS_RECORD`` (0: the record's bond bytes, the 2-D tables with the raw charge bytes) or ``BONDS_DISTANCE`` (1: orders from
+    the fp32 positions with the arithmetic of ``ds_check_stability``, every charge 0).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(valence [P, 29] u8, stable_mask [P] i32, valid_mask [P] i32, summary [P, 4] i32,
+    largest_mask [P] i32, status [P] u8)`` on the current stream without synchronising: the masks hold a bit per atom, ``summary`` is (n, stable
+    atoms, fragments, atoms of the largest fragment), status ``VALENCE_UNUSABLE`` (3: n = 0, a type above 4, a bond byte above 3) zeroes the row.
+    The validity restates RDKit's valence check and is unpinned against RDKit.  Checked, never converted; no CPU path."""
+    i32 = (torch.int32, ())
+    return _record_call("valence_records", [(rec, n)], None, [_bonds_from(bonds_from)],
+                        [(torch.uint8, (MAX_ATOMS,)), i32, i32, (torch.int32, (4,)), i32, (torch.uint8, ())], prefix="dsv_")
+
+
+def fragment_records(rec: torch.Tensor, n: torch.Tensor, keep: torch.Tensor, bonds_from: int = 0, charge_rule: bool = True):
+    """``dsv_fragment_records``: the atoms of ``keep [P] i32`` (bit i = keep atom i; bits at and above n are ignored) of every record as a
+    well-formed record of their own, atoms in ascending original order: ``(out_rec [P, 1248] u8, out_n [P] i32)`` on the current stream without
+    synchronising.  ``charge_rule`` writes the charge the reference applies to its RDKit atom (N+1, N-1, C+1, O-1, C-1; else 0) instead of the
+    raw byte; with ``BONDS_DISTANCE`` the bonds written are the derived orders and every charge is 0.  An unusable record gives ``out_n = 0`` and
+    zeros.  With ``valence_records``' ``largest_mask`` this is the largest fragment.  Checked, never converted; no CPU path."""
+    if not isinstance(charge_rule, bool):
+        raise TypeError(f"charge_rule must be a bool, got {type(charge_rule).__name__}")
+    _want(rec, "rec", torch.uint8, (None, RECORD_BYTES))
+    _want(keep, "keep", torch.int32, (rec.shape[0],))
+    return _record_call("fragment_records", [(rec, n)], None, [_bonds_from(bonds_from), ptr(keep), int(charge_rule)],
+                        [(torch.uint8, (RECORD_BYTES,)), (torch.int32, ())], prefix="dsv_", also=[keep])
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -927,6 +974,14 @@ class DmtEngine:
     def tanimoto_nn(self, a_words, a_pop, b_words, b_pop, n_bits: int, skip_same_index: bool = False, workspace=None):
         """``engine.tanimoto_nn`` on this engine's library (the set similarities need no weights)."""
         return tanimoto_nn(a_words, a_pop, b_words, b_pop, n_bits, skip_same_index, workspace)
+
+    def valence_records(self, rec, n, bonds_from: int = 0):
+        """``engine.valence_records`` on this engine's library (the valence analytics need no weights)."""
+        return valence_records(rec, n, bonds_from)
+
+    def fragment_records(self, rec, n, keep, bonds_from: int = 0, charge_rule: bool = True):
+        """``engine.fragment_records`` on this engine's library."""
+        return fragment_records(rec, n, keep, bonds_from, charge_rule)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

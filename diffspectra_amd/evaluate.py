@@ -147,6 +147,15 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     restated and unpinned, one representative per constitution-level class stands for ``set(smiles)``, no RDKit sanitisation filter; FCD, Frag
     and Scaf are not computed).  Without the flag the dict has no such key.
 
+    With ``config.eval.edm_metrics`` true ``metrics['structure']['metric_2d']`` and ``['metric_3d']`` are the reference's first two evaluation
+    lines (``run_lib.py:371-387``): ``mol_stable``, ``atom_stable``, ``Validity``, ``Complete``, ``Unique`` and ``Novelty`` (against
+    ``known_records``; -1 without) of the generated records, from the predicted bonds and charges and from the distance-derived bonds, plus
+    the per-record device tensors ``valence``, ``valid`` and ``largest`` (``structure_metrics.get_edm_metric_2d`` / ``get_edm_metric_3d``, which
+    state the deviations: RDKit's valence check restated and unpinned, constitution-level identity, Kekule orders only, ``n = 0`` counted as
+    unusable).  Without the flag the dict has no such keys.  ``set_similarity`` stays as it is with both flags set - the reference filters its
+    set metrics by RDKit sanitisation, and a caller who wants that passes the mask on:
+    ``get_set_similarity_metric(test)(generated, keep=metrics['structure']['metric_2d']['valid'])``.
+
     ``test_ds=None`` reads the reference's processed files under ``config.data.root`` (``run_lib.py:313`` ->
     ``build_dataset.py:31-42``: the 'test' entry of ``split_dict_diffspectra_qm9.pt``) into the device-resident table of
     ``qm9s_reader.ProcessedQM9S.packed_table`` - no PyG, no per-molecule Python."""
@@ -171,6 +180,7 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     results = {}
     geometry_fn = None                            # the test side of the geometry MMD is extracted once, at the first checkpoint
     set_fn = None                                 # and so are the bit rows of the test molecules
+    edm_fns = None
     for ckpt in checkpoint_ids(config):
         ckpt_path = os.path.join(workdir, "checkpoints", "checkpoint_{}.pth".format(ckpt))
         if not os.path.exists(ckpt_path):
@@ -200,5 +210,13 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                     known = None if known_records is None else (known_records[0].to(dev), known_records[1])
                     set_fn = get_set_similarity_metric((test_ds.gt_records.to(dev), test_ds.num_atom), known=known, engine=run.eng)
                 metrics["structure"]["set_similarity"] = set_fn((run.records_by_slot, torch.tensor(run.n_atoms)))
+            if getattr(config.eval, "edm_metrics", False):
+                from .structure_metrics import get_edm_metric_2d, get_edm_metric_3d
+                if edm_fns is None:
+                    dev = run.records_by_slot.device
+                    known = None if known_records is None else (known_records[0].to(dev), known_records[1])
+                    edm_fns = dict(metric_2d=get_edm_metric_2d(known=known, engine=run.eng), metric_3d=get_edm_metric_3d(known=known, engine=run.eng))
+                for key, fn in edm_fns.items():
+                    metrics["structure"][key] = fn(run.records_by_slot, torch.tensor(run.n_atoms))
         results[ckpt] = dict(processed_mols=processed_mols, gt_pos=gt_pos, gt_rdmols=gt_rdmols, metrics=metrics, step=state["step"])
     return results

@@ -42,6 +42,18 @@ fingerprints into bit rows (``dss_fold_bits``), ``nearest_neighbour_similarity``
 remembered - MOSES is neither vendored by the reference nor runnable here, so parity with it is unpinned - and the fingerprints carry the
 deviations of ``morgan_similarity_batch``.  FCD, Frag and Scaf of that line are not reproduced.
 
+Whether the generated molecules are chemically sound is ``get_edm_metric_2d`` / ``get_edm_metric_3d``: the reference's first two evaluation lines,
+"Metric-3D || atom stability, mol stability, validity, complete" and "Metric-2D || ..., unique & valid, unique & valid & novelty"
+(``run_lib.py:371-387``; ``evaluation/stability.py:76-230``, ``evaluation/rdkit_metric.py:86-129``).  ``valence_batch`` gives the per-record
+valences, stability, validity and fragments (``dsv_valence_records``, ``csrc/ds_valence.hip``; definitions in ``include/diffspectra_valence.h``) from
+the predicted bond orders and charges (2-D) or from bond orders derived from the distances with ``ds_check_stability``'s arithmetic (3-D);
+``largest_fragment_records`` turns every molecule's largest fragment into a record of its own (``dsv_fragment_records``), which is what lets
+``graph_classes``, ``novelty``, ``morgan_bit_rows`` and the set metrics run on largest fragments and on distance-derived graphs.  Deviations: the
+validity restates RDKit's valence check (no aromatic bonds exist in a record, so nothing else of ``Chem.SanitizeMol`` can fail) and is
+unpinned against RDKit; ``Unique`` / ``Novelty`` count constitution-level classes of the explicit graph where the reference counts canonical
+SMILES; the records hold Kekule orders only; a record with ``n = 0`` (or with a byte outside the alphabet) is UNUSABLE: it counts in every
+denominator and in no numerator, where the reference would count an empty molecule as stable and valid.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -660,3 +672,114 @@ def get_set_similarity_metric(test, known=None, n_bits: int = 1024, unique: bool
             out["novelty"] = novelty((g_rec, g_n), known, engine)
         return out
     return set_similarity_metric
+
+
+# ------------------------------------------------------------------------------------------------------------------ stability, validity, fragments
+
+class Valence(NamedTuple):
+    """Per-record device tensors of ``dsv_valence_records``."""
+    valence: torch.Tensor         # [P, 29] u8: the valence of every atom < n, 0 elsewhere
+    stable_mask: torch.Tensor     # [P] i32: bit i = atom i is stable
+    valid_mask: torch.Tensor      # [P] i32: bit i = atom i passes the (restated) RDKit valence check
+    summary: torch.Tensor         # [P, 4] i32: n, stable atoms, fragments, atoms of the largest fragment
+    largest_mask: torch.Tensor    # [P] i32: bit i = atom i belongs to the largest fragment (ties: the one with the lowest atom)
+    status: torch.Tensor          # [P] u8: 0 ok, 3 unusable (n = 0, a type above 4, a bond byte above 3): every other output of the row is 0
+
+    @property
+    def usable(self) -> torch.Tensor:
+        return self.status == 0
+
+    @property
+    def mol_stable(self) -> torch.Tensor:
+        """Every atom of the molecule is stable (``stability.py:160``); False for an unusable record."""
+        return self.usable & (self.summary[:, 1] == self.summary[:, 0])
+
+    @property
+    def valid(self) -> torch.Tensor:
+        """Every atom passes the valence check - the ``Chem.SanitizeMol`` of ``mol2smiles``, restated; False for an unusable record."""
+        return self.usable & (self.valid_mask == torch.bitwise_left_shift(torch.ones_like(self.valid_mask), self.summary[:, 0]) - 1)
+
+    @property
+    def complete(self) -> torch.Tensor:
+        """Valid and in one piece (``rdkit_metric.py:99-100``)."""
+        return self.valid & (self.summary[:, 2] == 1)
+
+
+def _bonds_from(bonds: str) -> int:
+    from . import engine as E
+    if bonds not in ("record", "distance"):
+        raise ValueError(f"bonds must be 'record' or 'distance', got {bonds!r}")
+    return E.BONDS_RECORD if bonds == "record" else E.BONDS_DISTANCE
+
+
+def valence_batch(records: torch.Tensor, n_atoms, bonds: str = "record", engine=None) -> Valence:
+    """Valences, stability, validity and fragments of every record of ``records [P, 1248] u8`` (GPU) in one launch of ``dsv_valence_records``.
+    ``bonds="record"``: the predicted bond orders and the raw charge bytes with ``allowed_fc_bonds`` - the reference's ``check_2D_stability``;
+    ``bonds="distance"``: orders from the fp32 positions by ``get_bond_order`` with the arithmetic of ``ds_check_stability``, charges 0,
+    ``allowed_bonds`` - its ``check_stability``.  The validity restates RDKit's valence check with the charges the reference applies (N+1, N-1,
+    C+1, O-1, C-1) and is unpinned against RDKit.  Device tensors, no synchronisation."""
+    from . import engine as E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    return Valence(*(engine if engine is not None else E).valence_records(records, n, _bonds_from(bonds)))
+
+
+def largest_fragment_records(records: torch.Tensor, n_atoms, bonds: str = "record", engine=None):
+    """``(records [P, 1248] u8, n_atoms [P] i32)`` of the largest fragment of every molecule (connected components over all atoms, bonds of
+    order > 0; among equally large fragments the one with the lowest atom), atoms in their original order, with the charges the reference
+    applies to its RDKit atoms and, for ``bonds="distance"``, the derived bond orders and no charges - the ``largest_mol`` of ``eval_rdmol``.
+    An unusable record gives 0 atoms.  Two launches (``dsv_valence_records``, ``dsv_fragment_records``), no synchronisation."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    mode = _bonds_from(bonds)
+    return eng.fragment_records(records, n, eng.valence_records(records, n, mode)[4], mode, True)
+
+
+def _edm_metric(bonds: str, known, engine):
+    def edm_metric(records, n_atoms):
+        from . import engine as E
+        eng = engine if engine is not None else E
+        dev = records.device
+        n = torch.as_tensor(n_atoms).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        mode = _bonds_from(bonds)
+        v = Valence(*eng.valence_records(records, n, mode))
+        frag_rec, frag_n = eng.fragment_records(records, n, v.largest_mask, mode, True)
+        valid = v.valid
+        P, atoms = int(n.shape[0]), int(n.clamp(0, shard.RECORD_ATOMS).sum())
+        rows = torch.nonzero(valid).reshape(-1)
+        g_rec, g_n = frag_rec[rows].contiguous(), frag_n[rows].contiguous()
+        K = 0
+        if known is not None:
+            K = known[0].shape[0]
+            k_n = torch.as_tensor(known[1]).to(device=dev, dtype=torch.int32).reshape(-1)
+            g_rec, g_n = torch.cat([known[0].to(dev), g_rec]).contiguous(), torch.cat([k_n, g_n]).contiguous()
+        cls = graph_classes(g_rec, g_n, engine)[K:]
+        over = lambda count, total: count / total if total else float("nan")
+        return dict(mol_stable=over(int(v.mol_stable.sum()), P), atom_stable=over(int(v.summary[:, 1].sum()), atoms),
+                    Validity=over(int(valid.sum()), P), Complete=over(int(v.complete.sum()), P), Unique=over(int(cls.unique().numel()), P),
+                    Novelty=-1 if known is None else over(int(cls[cls >= K].unique().numel()), P),
+                    valence=v, valid=valid, largest=(frag_rec, frag_n))
+    return edm_metric
+
+
+def get_edm_metric_2d(known=None, engine=None):
+    """``get_2D_edm_metric`` of ``evaluation/stability.py:199-230`` with ``eval_rdmol`` (``rdkit_metric.py:86-129``) on record tensors - the
+    reference's "Metric-2D" line.  ``known``, optional, is ``(records [*, 1248] u8, n_atoms [*])`` of the training molecules.  Returns
+    ``fn(records, n_atoms)`` (records on the GPU), which gives the reference's two dicts merged, as Python numbers: ``mol_stable`` (stable
+    molecules / P), ``atom_stable`` (stable atoms / all atoms), ``Validity`` (valid / P), ``Complete`` (valid and one fragment / P), ``Unique``
+    (distinct ``graph_classes`` classes of the largest fragments of the VALID molecules / P - over all generated molecules, as the reference
+    divides), ``Novelty`` (those classes that are no known molecule / P; -1 without ``known``); NaN where a denominator is 0.  Next to them the
+    device tensors: ``valence`` (the ``Valence`` of ``valence_batch``), ``valid`` (``[P] bool``, the mask that ``get_set_similarity_metric``'s
+    ``keep=`` takes) and ``largest`` (``(records, n_atoms)`` of every molecule's largest fragment).
+
+    Deviations from the reference: the validity restates RDKit's valence check and is unpinned against RDKit; identity is constitution-level
+    on the explicit graph (what a SMILES of an all-explicit, stereo-free RDKit molecule distinguishes), with Kekule orders only; an unusable
+    record (``n = 0``, a byte outside the alphabet) counts in every denominator and in no numerator."""
+    return _edm_metric("record", known, engine)
+
+
+def get_edm_metric_3d(known=None, engine=None):
+    """``get_edm_metric`` of ``evaluation/stability.py:164-196`` on record tensors - the reference's "Metric-3D" line: as
+    ``get_edm_metric_2d``, with the bond orders derived from the distances (``get_bond_order``, the arithmetic of ``ds_check_stability``),
+    no charges and ``allowed_bonds``; the largest fragments carry the derived orders.  The same deviations apply."""
+    return _edm_metric("distance", known, engine)

@@ -599,84 +599,87 @@ int env_int(const char* name, int dflt) {
   return v ? atoi(v) : dflt;
 }
 
-}  // namespace
+// ------------------------------------------------------------------------------------------------------------------ launch plan
+// Which kernel one call of dst_gemm launches and how: computed here and nowhere else - dst_gemm launches from it, dst_gemm_route reports it.
+// Pointers are inspected (NULL, 16-byte alignment), never dereferenced.  A plain value on the caller's stack (~650 products per step).
+struct gemm_plan {
+  int kernel;                       // DST_ROUTE_*; DST_ROUTE_NONE: valid arguments, nothing to launch
+  int BM, BN, threads;              // ws: 32 x 32 nct
+  int splits, kchunk;               // splits > 1: k_tr_gemm_reduce follows
+  int a_rfast, b_rfast;             // vector kernels: the operand's memory order runs along its rows; element-wise kernels: a_cs != 1, b_cs == 1
+  int epi;                          // dst_gemm_args._pad of the launch
+  int tm, tn;
+  unsigned int wgs;                 // workgroups of the product kernel (padding workgroups included)
+  int bf16;                         // products on the bf16 MFMA (0: fp32 MFMA / fp32 FMAs)
+  int Kp, nct, nchunks, ngroups;    // ws only
+  size_t lds;                       // ws only: dynamic LDS bytes
+};
 
-extern "C" {
-
-int dst_struct_sizes(int64_t* out, int32_t cap) {
-  const int64_t sizes[] = {sizeof(dst_gemm_args),       sizeof(dst_layout),          sizeof(dst_piece),         sizeof(dst_pair_chain_args),
-                           sizeof(dst_pair_front_args), sizeof(dst_dir_chain_args),  sizeof(dst_node_chain_args), sizeof(dst_dir_bwd_args),
-                           sizeof(dst_pair_bwd_args),   sizeof(dst_node_bwd_args)};
-  const int32_t n = (int32_t)(sizeof(sizes) / sizeof(sizes[0]));
-  if (!out || cap < n) return DS_ERR_ARG;
-  for (int32_t i = 0; i < n; ++i) out[i] = sizes[i];
-  return DS_OK;
-}
-
-int dst_gemm(const dst_gemm_args* a, void* stream) {
+int plan_gemm(const dst_gemm_args* a, gemm_plan& p) {
+  p = gemm_plan{};
+  p.kernel = DST_ROUTE_NONE;
   if (!a || !a->C || a->M < 0 || a->N < 0 || a->K < 0 || (a->K > 0 && (!a->A || !a->B))) return DS_ERR_ARG;
   if ((a->dact && !a->ref) || a->act < 0 || a->act > 3 || a->dact < 0 || a->dact > 4 || !(a->drop_p >= 0.0f && a->drop_p < 1.0f)) return DS_ERR_ARG;
   if (a->act && a->accumulate) return DS_ERR_ARG;                       // an activated output is written, never accumulated
   if (a->M == 0 || (a->N == 0 && !a->rowsum)) return DS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  dst_gemm_args g = *a;
+  const dst_gemm_args& g = *a;
+  const bool fused = g.act || g.dact || g.drop_p > 0.0f;
   {   // vector epilogue (epi_fused4): every pointer of the fused epilogue 16-byte aligned, every stride and N a multiple of 4, no fused row sum
     static const bool vec_epi_on = env_int("DST_GEMM_VEC_EPI", 1) != 0;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool fused = g.act || g.dact || g.drop_p > 0.0f;
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     static const bool vec_plain_on = env_int("DST_GEMM_VEC_PLAIN", 1) != 0;
     const bool ok = !g.rowsum && (g.N & 3) == 0 && (g.ldc & 3) == 0 && al16(g.C) && (!g.bias || al16(g.bias)) &&
                     (!g.ref || (al16(g.ref) && (g.ldref & 3) == 0)) && (!g.C2 || (al16(g.C2) && (g.ldc2 & 3) == 0)) &&
                     (!(g.drop_p > 0.0f) || (g.drop_ld & 3) == 0) && vec_epi_on;
     // bit 0: the vector form of the staged epilogue; bit 1: a plain epilogue (bias / accumulate only) takes the staged vector form too
     // (four 16-byte stores per tile and lane instead of sixteen 4-byte ones)
-    g._pad = ok ? (1 | ((!fused && vec_plain_on) ? 2 : 0)) : 0;
+    p.epi = ok ? (1 | ((!fused && vec_plain_on) ? 2 : 0)) : 0;
   }
   const int Nx = g.N + (g.rowsum ? 1 : 0);            // the fused row sum is one more (virtual, all-ones) column of B
   const bool bf = g.bf16 != 0;
   // the vector kernel needs every operand either k-contiguous or row-contiguous, 16-byte aligned with a leading stride of whole vec4s
   // ... and a leading stride that covers the fast extent rounded up to a vec4 (fetch_tile's clamped 16-byte loads stay inside the row that
   // way; a broadcast operand - leading stride 0 - or overlapping rows take the element-wise kernel)
-  auto vec_ok = [](const float* p, int64_t fast, int64_t slow, int64_t extent) {
-    return fast == 1 && (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (slow & 3) == 0 && slow >= ((extent + 3) & ~(int64_t)3);
+  auto vec_ok = [](const float* q, int64_t fast, int64_t slow, int64_t extent) {
+    return fast == 1 && (reinterpret_cast<uintptr_t>(q) & 15) == 0 && (slow & 3) == 0 && slow >= ((extent + 3) & ~(int64_t)3);
   };
   const bool a_k = vec_ok(g.A, g.a_cs, g.a_rs, g.K), a_r = !a_k && vec_ok(g.A, g.a_rs, g.a_cs, g.M);
   const bool b_k = vec_ok(g.B, g.b_rs, g.b_cs, g.K), b_r = !b_k && vec_ok(g.B, g.b_cs, g.b_rs, g.N);
   static const int force_old = env_int("DST_GEMM_OLD", 0), bn_pref = env_int("DST_GEMM_BN", 0), bm_pref = env_int("DST_GEMM_BM", 0),
                    split_target = env_int("DST_GEMM_SPLIT_WGS", 1024), wg_target = env_int("DST_GEMM_WGS", 768);
   const bool vec = bf && !force_old && (a_k || a_r) && (b_k || b_r) && g.K >= 8 && g.N > 0;
+  p.a_rfast = vec ? (int)a_r : (int)(g.a_cs != 1);
+  p.b_rfast = vec ? (int)b_r : (int)(g.b_cs == 1);
+  p.splits = 1;
+  p.kchunk = g.K;
   static const int ws_off = env_int("DST_GEMM_WS", 1) == 0, ws_min_m = env_int("DST_GEMM_WS_MIN_M", 65536);
   // measured inside the training step (same box, DST_GEMM_WS=0 / 1): the resident-weight form wins where the weight is large and the
   // rows are many (81 014 x 256 x 256 input gradient: 66 us against 113) and loses on the short-K products (K = 64 / 128: its 256
   // workgroups re-stage the weight for too little work per row), so it takes K >= 256 on the directed rows only
   if (vec && !ws_off && a_k && g.K >= 256 && g.K <= 512 && (g.K & 127) == 0 && g.M >= ws_min_m && !g.rowsum && g.N >= 16) {
-    const int Kp = (g.K + 15) / 16 * 16;
-    int nct = g.N > 64 ? 4 : 2;
-    if ((size_t)32 * nct * (Kp + 8) * 2 + STAGE_BYTES * 2 > 160 * 1024) nct = 2;      // K = 512: 64 columns of the weight at a time
-    const int NC = 32 * nct;
-    const int nchunks = (g.N + NC - 1) / NC;
-    const size_t lds = (size_t)NC * (Kp + 8) * 2 + STAGE_BYTES * 2;          // eight waves' staging tiles
-    int ngroups = (g.M + 255) / 256;
-    const int max_groups = (256 + nchunks - 1) / nchunks;                     // one workgroup per CU (the resident weight takes most of its LDS)
-    if (ngroups > max_groups) ngroups = max_groups;
-    const dim3 grid(8 * ((ngroups + 7) / 8) * nchunks), blk(512);
-    static std::atomic<uint64_t> lds_set[2];
-    if (nct == 4) {
-      if (!dst::allow_dynamic_lds(lds_set[0], &k_tr_gemm_ws<4>, 160 * 1024)) return DS_ERR_LAUNCH;
-      hipLaunchKernelGGL((k_tr_gemm_ws<4>), grid, blk, lds, s, g, (int)b_r, Kp, nchunks, ngroups);
-    } else {
-      if (!dst::allow_dynamic_lds(lds_set[1], &k_tr_gemm_ws<2>, 160 * 1024)) return DS_ERR_LAUNCH;
-      hipLaunchKernelGGL((k_tr_gemm_ws<2>), grid, blk, lds, s, g, (int)b_r, Kp, nchunks, ngroups);
-    }
-    return DST_CHECK_LAUNCH();
+    p.kernel = DST_ROUTE_WS;
+    p.Kp = (g.K + 15) / 16 * 16;
+    p.nct = g.N > 64 ? 4 : 2;
+    if ((size_t)32 * p.nct * (p.Kp + 8) * 2 + STAGE_BYTES * 2 > 160 * 1024) p.nct = 2;      // K = 512: 64 columns of the weight at a time
+    const int NC = 32 * p.nct;
+    p.nchunks = (g.N + NC - 1) / NC;
+    p.lds = (size_t)NC * (p.Kp + 8) * 2 + STAGE_BYTES * 2;                   // eight waves' staging tiles
+    p.ngroups = (g.M + 255) / 256;
+    const int max_groups = (256 + p.nchunks - 1) / p.nchunks;                 // one workgroup per CU (the resident weight takes most of its LDS)
+    if (p.ngroups > max_groups) p.ngroups = max_groups;
+    p.wgs = 8u * ((p.ngroups + 7) / 8) * p.nchunks;
+    p.BM = 32; p.BN = NC; p.threads = 512; p.bf16 = 1;
+    p.tm = (g.M + 31) / 32; p.tn = p.nchunks;
+    return DS_OK;
   }
   static const int skinny_off = env_int("DST_GEMM_SKINNY", 1) == 0;
   if (bf && !skinny_off && g.K <= 8 && g.M >= 1024 && !g.rowsum && g.N > 0) {       // (bf16 mode only: the fp32 mode keeps one summation order everywhere)
-    if ((g._pad & 1) && g.b_cs == 1 && (g.b_rs & 3) == 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0)
-      hipLaunchKernelGGL(k_tr_gemm_skinny4, dim3((unsigned)(((int64_t)g.M * (g.N >> 2) + 255) / 256)), dim3(256), 0, s, g);
-    else
-      hipLaunchKernelGGL(k_tr_gemm_skinny, dim3((unsigned)(((int64_t)g.M * g.N + 255) / 256)), dim3(256), 0, s, g);
-    return DST_CHECK_LAUNCH();
+    const bool four = (p.epi & 1) && g.b_cs == 1 && (g.b_rs & 3) == 0 && (reinterpret_cast<uintptr_t>(g.B) & 15) == 0;
+    p.kernel = four ? DST_ROUTE_SKINNY4 : DST_ROUTE_SKINNY;
+    p.BM = 1; p.BN = four ? 4 : 1; p.threads = 256;
+    p.tm = g.M; p.tn = four ? g.N >> 2 : g.N;
+    p.wgs = (unsigned)(((int64_t)g.M * p.tn + 255) / 256);
+    return DS_OK;
   }
   static const int wide_off = env_int("DST_GEMM_WIDE", 1) == 0;
   // (K = 4 633 node-row gradients: 52 us in this form against 40 us as 1 024 workgroups of 128 x 64 - too few k-steps per CU)
@@ -717,27 +720,85 @@ int dst_gemm(const dst_gemm_args* a, void* stream) {
   if (kchunk < kq) kchunk = kq;
   splits = g.K > 0 ? (g.K + kchunk - 1) / kchunk : 1;
   const int inner = splits > 1 ? (int)tiles : tn, outer = splits > 1 ? splits : tm;
-  const dim3 grid(8 * ((outer + 7) / 8) * inner), blk(wide ? 512 : 256);
-  if (wide) {
-    if (BN == 256) hipLaunchKernelGGL((k_tr_gemm_bf16<256, 256, 512>), grid, blk, 0, s, g, splits, kchunk, (int)a_r, (int)b_r, tm, tn);
-    else if (BN == 128) hipLaunchKernelGGL((k_tr_gemm_bf16<256, 128, 512>), grid, blk, 0, s, g, splits, kchunk, (int)a_r, (int)b_r, tm, tn);
-    else hipLaunchKernelGGL((k_tr_gemm_bf16<256, 64, 512>), grid, blk, 0, s, g, splits, kchunk, (int)a_r, (int)b_r, tm, tn);
-  } else if (vec) {
-#define DST_LAUNCH_BF16(M_, N_) hipLaunchKernelGGL((k_tr_gemm_bf16<M_, N_>), grid, blk, 0, s, g, splits, kchunk, (int)a_r, (int)b_r, tm, tn)
-    if (BM == 128 && BN == 128) DST_LAUNCH_BF16(128, 128);
-    else if (BM == 128) DST_LAUNCH_BF16(128, 64);
-    else if (BN == 128) DST_LAUNCH_BF16(64, 128);
+  p.kernel = vec ? DST_ROUTE_BF16 : DST_ROUTE_BIG;
+  p.BM = BM; p.BN = BN; p.threads = wide ? 512 : 256;
+  p.splits = splits; p.kchunk = kchunk;
+  p.tm = tm; p.tn = tn;
+  p.wgs = 8u * ((outer + 7) / 8) * inner;
+  p.bf16 = bf ? 1 : 0;
+  return DS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dst_struct_sizes(int64_t* out, int32_t cap) {
+  const int64_t sizes[] = {sizeof(dst_gemm_args),       sizeof(dst_layout),          sizeof(dst_piece),         sizeof(dst_pair_chain_args),
+                           sizeof(dst_pair_front_args), sizeof(dst_dir_chain_args),  sizeof(dst_node_chain_args), sizeof(dst_dir_bwd_args),
+                           sizeof(dst_pair_bwd_args),   sizeof(dst_node_bwd_args)};
+  const int32_t n = (int32_t)(sizeof(sizes) / sizeof(sizes[0]));
+  if (!out || cap < n) return DS_ERR_ARG;
+  for (int32_t i = 0; i < n; ++i) out[i] = sizes[i];
+  return DS_OK;
+}
+
+int dst_gemm(const dst_gemm_args* a, void* stream) {
+  gemm_plan p;
+  const int st = plan_gemm(a, p);
+  if (st != DS_OK || p.kernel == DST_ROUTE_NONE) return st;
+  hipStream_t s = (hipStream_t)stream;
+  dst_gemm_args g = *a;
+  g._pad = p.epi;
+  const int Nx = g.N + (g.rowsum ? 1 : 0);
+  const dim3 grid(p.wgs), blk(p.threads);
+  const int splits = p.splits, kchunk = p.kchunk, tm = p.tm, tn = p.tn;
+  if (p.kernel == DST_ROUTE_WS) {
+    static std::atomic<uint64_t> lds_set[2];
+    if (p.nct == 4) {
+      if (!dst::allow_dynamic_lds(lds_set[0], &k_tr_gemm_ws<4>, 160 * 1024)) return DS_ERR_LAUNCH;
+      hipLaunchKernelGGL((k_tr_gemm_ws<4>), grid, blk, p.lds, s, g, p.b_rfast, p.Kp, p.nchunks, p.ngroups);
+    } else {
+      if (!dst::allow_dynamic_lds(lds_set[1], &k_tr_gemm_ws<2>, 160 * 1024)) return DS_ERR_LAUNCH;
+      hipLaunchKernelGGL((k_tr_gemm_ws<2>), grid, blk, p.lds, s, g, p.b_rfast, p.Kp, p.nchunks, p.ngroups);
+    }
+    return DST_CHECK_LAUNCH();
+  }
+  if (p.kernel == DST_ROUTE_SKINNY4 || p.kernel == DST_ROUTE_SKINNY) {
+    if (p.kernel == DST_ROUTE_SKINNY4) hipLaunchKernelGGL(k_tr_gemm_skinny4, grid, blk, 0, s, g);
+    else hipLaunchKernelGGL(k_tr_gemm_skinny, grid, blk, 0, s, g);
+    return DST_CHECK_LAUNCH();
+  }
+  if (p.kernel == DST_ROUTE_BF16 && p.threads == 512) {                 // the wide form: 256-row tiles
+    if (p.BN == 256) hipLaunchKernelGGL((k_tr_gemm_bf16<256, 256, 512>), grid, blk, 0, s, g, splits, kchunk, p.a_rfast, p.b_rfast, tm, tn);
+    else if (p.BN == 128) hipLaunchKernelGGL((k_tr_gemm_bf16<256, 128, 512>), grid, blk, 0, s, g, splits, kchunk, p.a_rfast, p.b_rfast, tm, tn);
+    else hipLaunchKernelGGL((k_tr_gemm_bf16<256, 64, 512>), grid, blk, 0, s, g, splits, kchunk, p.a_rfast, p.b_rfast, tm, tn);
+  } else if (p.kernel == DST_ROUTE_BF16) {
+#define DST_LAUNCH_BF16(M_, N_) hipLaunchKernelGGL((k_tr_gemm_bf16<M_, N_>), grid, blk, 0, s, g, splits, kchunk, p.a_rfast, p.b_rfast, tm, tn)
+    if (p.BM == 128 && p.BN == 128) DST_LAUNCH_BF16(128, 128);
+    else if (p.BM == 128) DST_LAUNCH_BF16(128, 64);
+    else if (p.BN == 128) DST_LAUNCH_BF16(64, 128);
     else DST_LAUNCH_BF16(64, 64);
 #undef DST_LAUNCH_BF16
-  } else if (BM == 128) {
-    if (bf) hipLaunchKernelGGL((k_tr_gemm_big<128, 64, true>), grid, blk, 0, s, g, splits, kchunk, tm, tn);
+  } else if (p.BM == 128) {
+    if (p.bf16) hipLaunchKernelGGL((k_tr_gemm_big<128, 64, true>), grid, blk, 0, s, g, splits, kchunk, tm, tn);
     else hipLaunchKernelGGL((k_tr_gemm_big<128, 64, false>), grid, blk, 0, s, g, splits, kchunk, tm, tn);
   } else {
-    if (bf) hipLaunchKernelGGL((k_tr_gemm_big<64, 64, true>), grid, blk, 0, s, g, splits, kchunk, tm, tn);
+    if (p.bf16) hipLaunchKernelGGL((k_tr_gemm_big<64, 64, true>), grid, blk, 0, s, g, splits, kchunk, tm, tn);
     else hipLaunchKernelGGL((k_tr_gemm_big<64, 64, false>), grid, blk, 0, s, g, splits, kchunk, tm, tn);
   }
   if (splits > 1) hipLaunchKernelGGL(k_tr_gemm_reduce, dim3((unsigned)(((int64_t)g.M * Nx + 255) / 256)), dim3(256), 0, s, g, splits);
   return DST_CHECK_LAUNCH();
+}
+
+int dst_gemm_route(const dst_gemm_args* a, int32_t* out, int32_t cap) {
+  if (!out || cap < DST_ROUTE_FIELDS) return DS_ERR_ARG;
+  gemm_plan p;
+  const int st = plan_gemm(a, p);
+  if (st != DS_OK) return st;
+  const int32_t v[DST_ROUTE_FIELDS] = {p.kernel, p.BM, p.BN, p.threads, p.splits, p.kchunk, p.a_rfast, p.b_rfast, p.epi, (int32_t)p.wgs, p.bf16};
+  for (int i = 0; i < DST_ROUTE_FIELDS; ++i) out[i] = v[i];
+  return DS_OK;
 }
 
 }  // extern "C"

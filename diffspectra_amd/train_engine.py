@@ -17,7 +17,7 @@ import contextlib
 import ctypes as C
 import os
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -60,6 +60,23 @@ _DIRB_PACK = STRUCTS["dst_dir_bwd_args"].pack
 _PAIRB_PACK = STRUCTS["dst_pair_bwd_args"].pack
 _NODEB_PACK = STRUCTS["dst_node_bwd_args"].pack
 
+
+class GemmRoute(NamedTuple):
+    """What ``dst_gemm_route`` reports, in the order of its ``out`` array (``kernel``: a ``DST_ROUTE_*`` constant of the header)."""
+    kernel: int
+    BM: int
+    BN: int
+    threads: int
+    slices: int
+    k_per_slice: int
+    a_rfast: int
+    b_rfast: int
+    epilogue: int
+    workgroups: int
+    bf16: int
+
+
+assert len(GemmRoute._fields) == abi.TRAINING.consts["DST_ROUTE_FIELDS"]
 
 DstPiece = abi.TRAINING.ctypes_struct("dst_piece")
 DstLayout = abi.TRAINING.ctypes_struct("dst_layout")
@@ -200,10 +217,9 @@ class Ops:
         return (bool(int(os.environ.get("DIFFSPECTRA_NODE_STREAM", "1"))) and self.main_stream is not None,
                 bool(int(os.environ.get("DIFFSPECTRA_ASYNC_DW", "1"))))
 
-    def gemm(self, A: MV, Bm: MV, Cm: MV, ta: bool, tb: bool, bias: Optional[torch.Tensor] = None, acc: bool = False,
-             rowsum: Optional[torch.Tensor] = None, act: int = 0, dact: int = 0, ref: Optional[MV] = None, out2: Optional[MV] = None,
-             drop=None):
-        """``drop = (p, seed, stream_id, row_length)``: the Philox dropout mask of element (m, n) is taken at index m * row_length + n."""
+    def _gemm_args(self, A: MV, Bm: MV, Cm: MV, ta: bool, tb: bool, bias=None, acc=False, rowsum=None, act=0, dact=0, ref=None, out2=None,
+                   drop=None) -> bytes:
+        """The packed ``dst_gemm_args`` of one product (``gemm`` and ``gemm_route`` pass the same struct)."""
         M, K = (A.cols, A.rows) if ta else (A.rows, A.cols)
         a_rs, a_cs = (1, A.ld) if ta else (A.ld, 1)
         K2, N = (Bm.cols, Bm.rows) if tb else (Bm.rows, Bm.cols)
@@ -222,9 +238,24 @@ class Ops:
             assert ref.rows == M and ref.cols == N
         if out2 is not None:
             assert out2.rows == M and out2.cols == N
-        st = self.lib.dst_gemm(args, self._s())       # ~650 calls per step and no scalar argument to convert: the status is tested here,
-        if st:                                        # _check is the error path only
-            E._check(st, "dst_gemm")
+        return args
+
+    def gemm(self, A: MV, Bm: MV, Cm: MV, ta: bool, tb: bool, bias: Optional[torch.Tensor] = None, acc: bool = False,
+             rowsum: Optional[torch.Tensor] = None, act: int = 0, dact: int = 0, ref: Optional[MV] = None, out2: Optional[MV] = None,
+             drop=None):
+        """``drop = (p, seed, stream_id, row_length)``: the Philox dropout mask of element (m, n) is taken at index m * row_length + n."""
+        st = self.lib.dst_gemm(self._gemm_args(A, Bm, Cm, ta, tb, bias, acc, rowsum, act, dact, ref, out2, drop), self._s())
+        if st:                                        # ~650 calls per step and no scalar argument to convert: the status is tested here,
+            E._check(st, "dst_gemm")                  # _check is the error path only
+
+    def gemm_route(self, A: MV, Bm: MV, Cm: MV, ta: bool, tb: bool, bias: Optional[torch.Tensor] = None, acc: bool = False,
+                   rowsum: Optional[torch.Tensor] = None, act: int = 0, dact: int = 0, ref: Optional[MV] = None, out2: Optional[MV] = None,
+                   drop=None) -> "GemmRoute":
+        """The launch ``gemm`` would make for the same arguments (``dst_gemm_route``: kernel, tile, slices, operand orders, epilogue bits),
+        without making it.  Nothing is read through the pointers and no device is touched."""
+        out = (C.c_int32 * len(GemmRoute._fields))()
+        E._check(self.lib.dst_gemm_route(self._gemm_args(A, Bm, Cm, ta, tb, bias, acc, rowsum, act, dact, ref, out2, drop), out, len(out)), "dst_gemm_route")
+        return GemmRoute(*out)
 
     def colsum(self, X: MV, out: torch.Tensor, acc: bool = False, param_grad: bool = False):
         """``param_grad``: the sums are a parameter gradient (nothing downstream of the pass reads them) - with the weight-gradient stream on

@@ -64,6 +64,21 @@ typedef struct dst_gemm_args {
 } dst_gemm_args;
 int dst_gemm(const dst_gemm_args* a, void* stream);
 
+/* The kernels dst_gemm chooses between: the weight-stationary kernel (tall products with a resident weight), the two K <= 8 kernels (one /
+ * four columns per thread), the bf16 tile kernel (256-thread tiles and the 512-thread 256-row form of the long-K weight gradients) and the
+ * element-wise fp32-in-LDS kernel (fp32 mode; bf16 mode with operands the vector loads cannot take).  DST_ROUTE_NONE: nothing to launch. */
+enum dst_gemm_kernel { DST_ROUTE_NONE = 0, DST_ROUTE_WS, DST_ROUTE_SKINNY, DST_ROUTE_SKINNY4, DST_ROUTE_BF16, DST_ROUTE_BIG };
+#define DST_ROUTE_FIELDS 11
+/* The launch dst_gemm would make for these arguments, without making it: dst_gemm launches from the same plan, and the arguments pass the same
+ * checks (DS_ERR_ARG where dst_gemm returns it, and when cap < DST_ROUTE_FIELDS).  Pointers are inspected (NULL, 16-byte alignment), never
+ * dereferenced; no device is needed.
+ * out[0] kernel (DST_ROUTE_*), out[1] BM (ws: 32; K <= 8 kernels: 1), out[2] BN (ws: 32 * nct; K <= 8 kernels: columns per thread),
+ * out[3] threads per workgroup, out[4] k-slices (> 1: k_tr_gemm_reduce follows), out[5] k per slice,
+ * out[6] A row-fast, out[7] B row-fast (vector kernels: the operand is transposed on its way in; element-wise kernels: a_cs != 1, b_cs == 1),
+ * out[8] epilogue bits (_pad: 1 vector epilogue, 2 plain epilogue through the staged vector form), out[9] workgroups launched (padding
+ * workgroups included), out[10] bf16 arithmetic (0: fp32 MFMA / fp32 FMA). */
+int dst_gemm_route(const dst_gemm_args* a, int32_t* out, int32_t cap);
+
 /* sizeof of every argument struct of this header, in this order: dst_gemm_args, dst_layout, dst_piece, dst_pair_chain_args,
  * dst_pair_front_args, dst_dir_chain_args, dst_node_chain_args, dst_dir_bwd_args, dst_pair_bwd_args, dst_node_bwd_args (ten values;
  * DS_ERR_ARG when cap < 10).  The binding builds its layouts from this header and checks each against the library's. */

@@ -247,3 +247,22 @@ def test_mask_convention_is_the_oracles(block):
     assert torch.equal(f["keep3"], CM.keep_scaled(seed, 4 * block + 2, tb["Pp"], 128, P)[0])
     assert torch.equal(f["keep4"], CM.keep_scaled(seed, 4 * block + 3, tb["Pp"], 64, P)[0])
     assert bool((f["s3"][~f["keep3"]] == 0).all()) and bool((f["f4"][~f["keep4"]] == 0).all())
+
+
+# ------------------------------------------------------------------------------------------------ the activations of the GEMM epilogue
+def test_activations_and_their_derivatives_are_torchs():
+    """``silu`` / ``gelu`` / their derivatives and ``dtanh_of_output`` against torch in float64 (values) and torch.autograd (derivatives), and
+    ``LIPSCHITZ`` against the largest |f'| on a grid that holds the maxima (SiLU' peaks at 2.3994, GELU' at sqrt 2)."""
+    x = torch.linspace(-12.0, 12.0, 48001, dtype=torch.float64)
+    for f, df, ref, name in ((CM.silu, CM.dsilu, F.silu, "silu"), (CM.gelu, CM.dgelu, F.gelu, "gelu")):
+        xr = x.clone().requires_grad_(True)
+        y = ref(xr)
+        y.sum().backward()
+        assert relerr(f(x), y) <= 1e-15 and relerr(df(x), xr.grad) <= 1e-14, name
+        peak = float(df(x).abs().max())
+        assert peak <= CM.LIPSCHITZ[name] <= 1.01 * peak, (name, peak)
+    xr = x.clone().requires_grad_(True)
+    y = torch.tanh(xr)
+    y.sum().backward()
+    assert relerr(CM.dtanh_of_output(y.detach()), xr.grad) <= 1e-15 and float(xr.grad.max()) <= CM.LIPSCHITZ["tanh"] == 1.0
+    assert relerr(CM.dgelu(torch.tensor([2.0 ** 0.5], dtype=torch.float64)), torch.tensor([1.1289], dtype=torch.float64)) < 1e-4

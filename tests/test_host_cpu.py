@@ -66,15 +66,15 @@ def test_prototypes_match_a_hand_written_table():
 
 def test_every_export_is_bound_with_its_signature():
     """Over both whole headers: the exports ARE the parsed prototypes, the totals are those of the headers, and every function of the loaded
-    library carries the parsed ``restype`` and ``argtypes``.  The headers hold 80 prototypes with 679 parameters - counted independently of the
-    parser below, as commas + 1 - of which 478 are pointers (479 stars: ``const float* const* ptrs`` has two)."""
+    library carries the parsed ``restype`` and ``argtypes``.  The headers hold 81 prototypes with 682 parameters - counted independently of the
+    parser below, as commas + 1 - of which 480 are pointers (481 stars: ``const float* const* ptrs`` has two)."""
     import __graft_entry__ as g
     from collections import Counter
     g.build()
     lib = E.load_library()
     abi, headers = _headers()
     kinds, n_params, n_by_commas = Counter(), 0, 0
-    for hdr, prefix, n_fn in zip(headers, ("ds_", "dst_"), (31, 49)):
+    for hdr, prefix, n_fn in zip(headers, ("ds_", "dst_"), (31, 50)):
         assert hdr.exports(prefix) == list(hdr.prototypes) and len(hdr.prototypes) == n_fn
         n_by_commas += sum(text.count(",") + 1 for text in re.findall(r"\b(?:int|void)\s+%s\w+\s*\(([^()]*)\)\s*;" % prefix, hdr.text))
         for name, proto in hdr.prototypes.items():
@@ -85,8 +85,8 @@ def test_every_export_is_bound_with_its_signature():
             assert fn.restype is (None if proto.ret == "void" else ctypes.c_int), name
             assert len(fn.argtypes) == len(proto.params) and list(fn.argtypes) == proto.argtypes, name
     assert E.EXPORTS == headers[0].exports("ds_")
-    assert n_params == n_by_commas == 679
-    assert dict(kinds) == {"*": 478, "int32_t": 90, "int64_t": 48, "float": 39, "int": 13, "uint64_t": 5, "double": 4, "uint32_t": 2}
+    assert n_params == n_by_commas == 682
+    assert dict(kinds) == {"*": 480, "int32_t": 91, "int64_t": 48, "float": 39, "int": 13, "uint64_t": 5, "double": 4, "uint32_t": 2}
     assert [n for h in headers for n, p in h.prototypes.items() if p.ret == "void"] == ["ds_struct_sizes"]
 
 

@@ -66,8 +66,8 @@ def test_header_declares_and_library_exports_the_valence_functions(lib):
 
 
 def test_the_three_existing_headers_keep_their_prototypes():
-    assert (len(abi.SAMPLING.exports("ds_")), len(abi.TRAINING.exports("dst_")), len(abi.SETS.exports("dss_"))) == (31, 49, 3)
-    assert (len(abi.SAMPLING.prototypes), len(abi.TRAINING.prototypes), len(abi.SETS.prototypes)) == (31, 49, 3)
+    assert (len(abi.SAMPLING.exports("ds_")), len(abi.TRAINING.exports("dst_")), len(abi.SETS.exports("dss_"))) == (31, 50, 3)
+    assert (len(abi.SAMPLING.prototypes), len(abi.TRAINING.prototypes), len(abi.SETS.prototypes)) == (31, 50, 3)
     for other in (abi.SAMPLING, abi.TRAINING, abi.SETS):
         assert not other.exports("dsv_")
 

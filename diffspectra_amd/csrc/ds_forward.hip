@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/diffspectra_hip.h"
+#include "../../include/diffspectra_tiles.h"
 #include "ds_device.h"
 #include "ds_host.h"
 
@@ -21,6 +22,11 @@
 constexpr int DS_NODE_PF = 8;
 constexpr int DS_NODE_PF2 = 4;   // per ring when two chunks share the X fragments
 constexpr int DS_QKV_PF = 4;
+constexpr int DS_QKV_PF_WIDE = 4;   // k_node_qkv_wide
+// launch_node_update / launch_node_qkv: 64-row tiles from this many per CU on.  Measured (profiles/r06_node_tiles_ab.txt): at 5.5 tiles
+// per CU q|k|v gains 8 % and the update breaks even (one workgroup per CU pays every partial round in full), at 11 they gain 13 % and 5 %;
+// at 1.4 and 2.7 (two-stream sizes) the forward is 1 % slower / unchanged, so small launches keep the forms they had
+constexpr int DS_NODE_TILE64_MIN_PER_CU = 4;
 constexpr int DS_TWO_STREAM_MAX_PAIRS = 400000;   // ds_forward: side stream for batches below this many pair rows (~2 500 molecules)
 
 // Diagnostic build only (-DDS_STAMPS): per-phase shader-clock sums of wave 0 of every workgroup, accumulated into
@@ -328,28 +334,32 @@ __global__ __launch_bounds__(256) void k_edge_geom(Ctx c, int blk) {
 // Block stage B (nodes): LN -> modulate -> q|k|v projection (256 -> 768).  dmt.py:148; layers.py:147-149.
 // 64-row tiles, two row tiles per weight fragment (with one, the q|k|v weight stream alone asks the L2 for ~75 GB/s per
 // CU at full MFMA rate, the measured per-CU L2 ceiling); blockIdx.y picks one 384-column half of the projection so
-// that the launch keeps >= 4 workgroups per CU at bench sizes - the LayerNorm of the tile is simply done by both halves.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void k_node_qkv(Ctx c, int blk) {
+// that a small launch keeps >= 4 workgroups per CU - the LayerNorm of the tile is simply done by both halves.  Launches that fill
+// the chip take k_node_qkv_wide (below), which does it once.
+// The work of both forms: NW = 4 is the 384-column half picked by blockIdx.y, NW = 8 the whole 768 columns (one LayerNorm and
+// one tile per 64 rows).  A row's q|k|v does not depend on the form: same split tile, same fragment and k order per element.
+template <int NW, int PF>
+__device__ __forceinline__ void node_qkv_tile(const Ctx& c, int blk) {
   ds_fp16_saturate();
-  constexpr int NT = NW * 64;
   constexpr int T = 64;
+  constexpr int RW = T / NW;          // rows a wave normalises
+  constexpr int NCH = 3 * NW;         // 32-column chunks of this workgroup
   constexpr int LDH = 2 * 256 + 8;
   __shared__ __attribute__((aligned(16))) _Float16 Xh[T][LDH];    // LayerNorm output in the split-fp16 layout (ds_device.h)
   __shared__ int rmol[T];
   const int tid = threadIdx.x, row0 = blockIdx.x * T, col0 = blockIdx.y * 384;
   if (tid < T) rmol[tid] = (row0 + tid < c.L.Nn) ? c.L.node_mol[row0 + tid] : 0;
   __syncthreads();
-  {   // 64 rows: wave w normalises rows 16w .. 16w+15, four rows per pass (one per 16-lane DPP row), two passes in flight
+  {   // 64 rows: wave w normalises rows RW w .. RW w + RW - 1, four rows per pass (one per 16-lane DPP row), two passes in flight
     const float* adn = c.ws.ada + blk * DS_ADA_BLOCK_STRIDE + DS_ADA_NODE;
     const int lane = tid & 63, wv = tid >> 6, g = lane >> 4, j = lane & 15;
-    static_assert(NT == 256, "four waves x 16 rows");
+    static_assert(NW == 4 || NW == 8, "four waves x 16 rows or eight waves x 8 rows");
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
+    for (int half = 0; half < RW / 8; ++half) {
       float4 v[2][4], sh[2][4], sc[2][4];
 #pragma unroll
       for (int ps = 0; ps < 2; ++ps) {
-        const int row = 16 * wv + 8 * half + 4 * ps + g;
+        const int row = RW * wv + 8 * half + 4 * ps + g;
         const float4* hp = reinterpret_cast<const float4*>(c.ws.h + (size_t)min(row0 + row, c.L.Nn - 1) * 256) + j;
         const float4* ap = reinterpret_cast<const float4*>(adn + (size_t)rmol[row] * ADAC) + j;
 #pragma unroll
@@ -361,7 +371,7 @@ __global__ __launch_bounds__(NW * 64) void k_node_qkv(Ctx c, int blk) {
       }
 #pragma unroll
       for (int ps = 0; ps < 2; ++ps) {
-        const int row = 16 * wv + 8 * half + 4 * ps + g;
+        const int row = RW * wv + 8 * half + 4 * ps + g;
         ln_mod_quad256(v[ps], sh[ps], sc[ps]);   // dmt.py:148
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -373,7 +383,7 @@ __global__ __launch_bounds__(NW * 64) void k_node_qkv(Ctx c, int blk) {
   const float* bias = BW(c, blk, DS_BW_QKV_B) + col0;
   float* qkv = c.ws.qkv + (size_t)row0 * 768 + col0;
   const int valid = c.L.Nn - row0, wave = tid >> 6;
-  for (int ch = wave; ch < 12; ch += NW) {   // 32-column chunks of this half of q|k|v; both row tiles per weight fragment
+  for (int ch = wave; ch < NCH; ch += NW) {   // 32-column chunks of this workgroup's columns; both row tiles per weight fragment
     asm volatile("" ::: "memory");
     const float b = bias[ch * 32 + (tid & 31)];
     f32x16 acc[2], lo[2];
@@ -382,11 +392,16 @@ __global__ __launch_bounds__(NW * 64) void k_node_qkv(Ctx c, int blk) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[m][i] = b;
     acc_zero<2>(lo);
-    wave_mma_h_ring<2, false, 16, DS_QKV_PF>(&Xh[0][0], 256, BW(c, blk, DS_BW_QKV_H), 768, 256, col0 + ch * 32, 0, acc, lo);
+    wave_mma_h_ring<2, false, 16, PF>(&Xh[0][0], 256, BW(c, blk, DS_BW_QKV_H), 768, 256, col0 + ch * 32, 0, acc, lo);
     split_finish<2>(acc, lo);
     acc_store<2, 768>(acc, qkv + ch * 32, valid, [](int, float v) { return v; });
   }
 }
+__global__ __launch_bounds__(256) void k_node_qkv(Ctx c, int blk) { node_qkv_tile<4, DS_QKV_PF>(c, blk); }
+// One 512-thread workgroup per 64 rows: the prologue (h and adaLN rows, LayerNorm, the 66.5 kB tile) once instead of once per column
+// half; two workgroups per CU are 4 waves per SIMD (128 VGPRs) where the y-split form holds 2.  For launches that fill the chip
+// (launch_node_qkv): a small launch keeps more workgroups per CU with the y-split form.
+__global__ __launch_bounds__(512, 2) void k_node_qkv_wide(Ctx c, int blk) { node_qkv_tile<8, DS_QKV_PF_WIDE>(c, blk); }
 
 // Block stage C (one 1024-thread workgroup per molecule): the whole edge-modulated attention of TransMixLayer
 // (layers.py:131-186 + PyG propagate / softmax) with tanh(lin_edge0 e) and tanh(lin_edge1 e) recomputed on chip.
@@ -997,6 +1012,216 @@ __global__ __launch_bounds__(256, 2) void k_node_update(Ctx c, int blk) {
       wave_mma_h_ring<1, false, 16, DS_NODE_PF>(&H2[0][0], 256, BW(c, blk, DS_BW_AC_H), 512, 256, (it - 2) * 32, 0, acc, lo);
       split_finish<1>(acc, lo);
       store_of(it, acc);
+    }
+  }
+}
+
+// Block stage D, 64 rows per 512-thread workgroup, one workgroup per CU (150 276 B of LDS): k_node_update streams 1.66 MB of weights
+// per tile from L2 and sits on the L2-to-CU limit, so here every weight fragment serves two 32-row tiles (MT = 2: six MFMAs per
+// fragment, as the chunk pairs of the 32-row form have) and the stream per row halves.  Wave w owns column chunk w of each FF1 half
+// and of FF2, then chunks w and w + 8 of the 18-chunk tail; node2edge and the last two tail chunks are four (row tile, chunk) items
+// of MT = 1.  Every output element sees the k order and the hi / lo MFMA sequence of the 32-row form: the results are the same bits.
+// Measured against the 32-row form: -5 % at 11 tiles per CU, even at 5.5 (launch rule and figures: DS_NODE_TILE64_MIN_PER_CU).
+// node_gate_mlp: a tile holds up to 64 molecules (3.5 at QM9 sizes), so the gate rows of its first DS_GATE_SLOTS molecules are staged
+// in LDS with the tile's other loads, a whole FF ahead of their use; a tile with more (molecules under four atoms) stages the rest
+// into the dead hidden tile behind the FF.  Launch rule: launch_node_update.
+constexpr int DS_GATE_SLOTS = 16;
+template <bool N2E>
+__global__ __launch_bounds__(512) void k_node_update64(Ctx c, int blk) {
+  ds_fp16_saturate();
+  constexpr int T = 64, LDH = 2 * 256 + 8, GS = DS_GATE_SLOTS;
+  __shared__ __attribute__((aligned(16))) _Float16 B1[T][LDH];   // attention tile, then FF hidden halves, then gate rows GS ..
+  __shared__ __attribute__((aligned(16))) _Float16 H2[T][LDH];   // normalised residual stream, then h_out in place
+  __shared__ __attribute__((aligned(16))) float G[GS][256];      // node_gate_mlp rows of the tile's first GS molecules
+  __shared__ int rmol[T], rslot[T], smol[T], nslot;              // molecule / gate slot of a row, molecule of a slot, slots in use
+  const int tid = threadIdx.x, wave = tid >> 6, row0 = blockIdx.x * T;
+  const int Nn = c.L.Nn;
+  const float* ada = c.ws.ada;
+  const float* gsec = ada + blk * DS_ADA_BLOCK_STRIDE + DS_ADA_NODE + 1280;
+  // the attention and h rows do not wait for the row -> molecule table: requested ahead of its barrier (rows as in the staging below)
+  float4 va[2][4], vh[2][4];
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps) {
+    const size_t gr = (size_t)min(row0 + 8 * wave + 4 * ps + ((tid & 63) >> 4), Nn - 1);   // clamp instead of branching: loads stay batched
+    const float4* ap = reinterpret_cast<const float4*>(c.ws.attn + gr * 256) + (tid & 15);
+    const float4* hp = reinterpret_cast<const float4*>(c.ws.h + gr * 256) + (tid & 15);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      va[ps][u] = ap[16 * u];
+      vh[ps][u] = hp[16 * u];
+    }
+  }
+  if (tid < T) {   // wave 0, lane = row: rows are sorted by molecule, a slot starts where the molecule changes; padded rows carry
+                   // molecule 0 and the last valid row's slot (their results are never stored)
+    const bool in = row0 + tid < Nn;
+    const int m = in ? c.L.node_mol[row0 + tid] : 0;
+    const bool first = in && (tid == 0 || c.L.node_mol[row0 + tid - 1] != m);
+    const unsigned long long starts = __ballot(first);
+    const int slot = __popcll(starts & ((2ull << tid) - 1ull)) - 1;
+    rmol[tid] = m;
+    rslot[tid] = slot;
+    if (first) smol[slot] = m;
+    if (tid == 0) nslot = __popcll(starts);
+  }
+  __syncthreads();
+  const int ns = nslot;
+  {   // 64 rows: wave w takes rows 8w .. 8w+7 as two passes of four rows, as the 32-row form does
+    const int lane = tid & 63, g = lane >> 4, j = lane & 15;
+    float4 vg[2][4], sh[2][4], sc[2][4], gv[2];
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+      const int row = 8 * wave + 4 * ps + g;
+      const float4* ad = reinterpret_cast<const float4*>(ada + (size_t)rmol[row] * ADAC + blk * DS_ADA_BLOCK_STRIDE + DS_ADA_NODE) + j;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        vg[ps][u] = ad[128 + 16 * u];   // node_gate_msa   (+512 floats)
+        sh[ps][u] = ad[192 + 16 * u];   // node_shift_mlp  (+768)
+        sc[ps][u] = ad[256 + 16 * u];   // node_scale_mlp  (+1024)
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)   // gate rows of slots wave, wave + 8 (an unused slot repeats the last one: no branch in the batch)
+      gv[u] = reinterpret_cast<const float4*>(gsec + (size_t)smol[min(wave + 8 * u, ns - 1)] * ADAC)[lane];
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+      const int row = 8 * wave + 4 * ps + g;
+      float4 r[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (row0 + row >= Nn) va[ps][u] = vh[ps][u] = make_float4(0, 0, 0, 0);
+        if (N2E) split_store4(&B1[row][0], 256, 64 * u + 4 * j, va[ps][u]);
+        // h_in + gate_msa * attn (dmt.py:159)
+        r[u].x = vh[ps][u].x + vg[ps][u].x * va[ps][u].x; r[u].y = vh[ps][u].y + vg[ps][u].y * va[ps][u].y;
+        r[u].z = vh[ps][u].z + vg[ps][u].z * va[ps][u].z; r[u].w = vh[ps][u].w + vg[ps][u].w * va[ps][u].w;
+      }
+      ln_mod_quad256(r, sh[ps], sc[ps]);   // norm2_node + modulate (dmt.py:160)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) split_store4(&H2[row][0], 256, 64 * u + 4 * j, r[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) reinterpret_cast<float4*>(&G[wave + 8 * u][0])[lane] = gv[u];
+  }
+  // One workgroup per CU: its eight waves meet at every barrier, so no other wave covers the L2 round trip of a phase's first weight
+  // blocks.  Weights depend on nothing the workgroup computes: each phase's ring is requested as soon as the ring of the phase in front
+  // of it has been consumed - ahead of that phase's epilogue and of the barrier (loads return in issue order: no wait on the stores).
+  const float* W1 = BW(c, blk, DS_BW_FF1_H);
+  const float* W2 = BW(c, blk, DS_BW_FF2_H);
+  auto tail_ws = [&](int it) {   // chunks 0-1: readout slice, 2-17: node parts of input_lin
+    return it < 2 ? wstream_h(BW(c, blk, DS_BW_NODE_RO_H), 64, 256, it * 32) : wstream_h(BW(c, blk, DS_BW_AC_H), 512, 256, (it - 2) * 32);
+  };
+  WRingH<DS_NODE_PF> ring, ring_n2e;
+  const bool n2e = N2E && wave < 4 && row0 + (wave >> 1) * 32 < Nn;   // row tile wave >> 1, 32-column chunk wave & 1 (as k_node_n2e)
+  const WStreamH wsn = wstream_h(BW(c, blk, DS_BW_N2E_H), 64, 256, (wave & 1) * 32);
+  if (n2e) wring_h<DS_NODE_PF>(ring_n2e, wsn, 0);
+  wring_h<DS_NODE_PF>(ring, wstream_h(W1, 512, 256, wave * 32), 0);
+  __syncthreads();
+  if (N2E) {
+    {   // node2edge_lin applied per node (256 -> 64)
+      const int mt = wave >> 1, cc = wave & 1;
+      if (n2e) {
+        f32x16 acc[1], lo[1];
+        acc_zero<1>(acc);
+        acc_zero<1>(lo);
+        wave_mma_h_deep<1, false, 16, DS_NODE_PF>(&B1[mt * 32][0], 256, wsn, ring_n2e, 0, acc, lo);
+        split_finish<1>(acc, lo);
+        acc_store<1, 64>(acc, c.ws.u + (size_t)(row0 + mt * 32) * 64 + cc * 32, Nn - row0 - mt * 32, [](int, float v) { return v; });
+      }
+    }
+    __syncthreads();   // H2 normalised; every wave is done reading B1 (node2edge)
+  }
+  {
+    const float* b1 = BW(c, blk, DS_BW_FF1_B);
+    const WStreamH ws2 = wstream_h(W2, 256, 512, wave * 32);
+    f32x16 acc2[2], lo2[2];
+    acc_zero<2>(acc2);
+    acc_zero<2>(lo2);
+    const int col = wave * 32 + (tid & 31);
+    const float bb = BW(c, blk, DS_BW_FF2_B)[col];   // requested a whole FF ahead of its use
+    for (int half = 0; half < 2; ++half) {
+      {
+        asm volatile("" ::: "memory");
+        const int hhf = (tid & 63) >> 5;
+        f32x16 acc[2], lo[2];
+        const float bf = b1[half * 256 + col];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) acc[m][i] = bf;
+        acc_zero<2>(lo);
+        wave_mma_h_deep<2, false, 16, DS_NODE_PF>(&H2[0][0], 256, wstream_h(W1, 512, 256, (half * 8 + wave) * 32), ring, 0, acc, lo);
+        wring_h<DS_NODE_PF>(ring, ws2, half * 16);   // FF2 of this half
+        split_finish<2>(acc, lo);
+        // SiLU(FF1 + bias) -> hidden tile, two rows at a time (packed-fp32 epilogue)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int i = 0; i < 16; i += 2) {
+            f32x2 v;
+            v.x = acc[m][i]; v.y = acc[m][i + 1];
+            v = ds_silu2(v);
+            const int r0 = m * 32 + acc_row(i, hhf);
+            split_store1(&B1[r0][0], 256, col, v.x);
+            split_store1(&B1[r0 + 1][0], 256, col, v.y);
+          }
+      }
+      __syncthreads();
+      asm volatile("" ::: "memory");
+      wave_mma_h_deep<2, false, 16, DS_NODE_PF>(&B1[0][0], 256, ws2, ring, half * 16, acc2, lo2, half * 16);
+      wring_h<DS_NODE_PF>(ring, half == 0 ? wstream_h(W1, 512, 256, (8 + wave) * 32) : tail_ws(wave), 0);   // FF1 of half 1 / tail chunk `wave`
+      __syncthreads();
+    }
+    split_finish<2>(acc2, lo2);
+    float* Gx = reinterpret_cast<float*>(&B1[0][0]);   // the hidden tile is dead: gate rows of slots GS .. (48 kB of its 66.5 kB at most)
+    if (ns > GS) {                                     // workgroup-uniform
+      for (int idx = tid; idx < (ns - GS) * 64; idx += 512)
+        reinterpret_cast<float4*>(Gx)[idx] = reinterpret_cast<const float4*>(gsec + (size_t)smol[GS + (idx >> 6)] * ADAC)[idx & 63];
+      __syncthreads();
+    }
+    const int hhl = (tid & 63) >> 5;
+    const int rows_here = Nn - row0;
+    const RowStore st = row_store<256>(c.ws.h + (size_t)row0 * 256 + wave * 32);
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = m * 32 + acc_row(i, hhl), s = rslot[row];
+        const float g = s < GS ? G[s][col] : Gx[(s - GS) * 256 + col];
+        const float out = split_load1(&H2[row][0], 256, col) + g * (acc2[m][i] + bb);   // in place
+        split_store1(&H2[row][0], 256, col, out);
+        if (row < rows_here) row_put(st, (m * 32 + (i & 3) + 8 * (i >> 2)) * 256 * 4, out);
+      }
+  }
+  __syncthreads();
+  {   // per-block readout slice (256 -> 64, chunks 0-1) and the node parts of equi_update.input_lin (256 -> 512, chunks 2-17)
+    const float* br = BW(c, blk, DS_BW_NODE_RO_B);
+    const int mt = (wave >> 1) & 1, itl = 16 + (wave & 1);   // chunks 16, 17: one row tile each, on the waves that got no bias chunk
+    const bool last = wave >= 4 && row0 + mt * 32 < Nn;
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {   // chunks wave, wave + 8 against both row tiles
+      asm volatile("" ::: "memory");
+      const int it = wave + 8 * pr;
+      const float bi = it < 2 ? br[it * 32 + (tid & 31)] : 0.0f;
+      f32x16 acc[2], lo[2];
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[m][i] = bi;
+      acc_zero<2>(lo);
+      wave_mma_h_deep<2, false, 16, DS_NODE_PF>(&H2[0][0], 256, tail_ws(it), ring, 0, acc, lo);
+      if (pr == 0) wring_h<DS_NODE_PF>(ring, tail_ws(wave + 8), 0);
+      else if (last) wring_h<DS_NODE_PF>(ring, tail_ws(itl), 0);
+      split_finish<2>(acc, lo);
+      if (it < 2) acc_store<2, 768>(acc, c.ws.atom_hids + (size_t)row0 * 768 + 256 + 64 * blk + it * 32, Nn - row0, [](int, float v) { return v; });
+      else acc_store<2, 512>(acc, c.ws.ac + (size_t)row0 * 512 + (it - 2) * 32, Nn - row0, [](int, float v) { return v; });
+    }
+    if (last) {
+      asm volatile("" ::: "memory");
+      f32x16 acc[1], lo[1];
+      acc_zero<1>(acc);
+      acc_zero<1>(lo);
+      wave_mma_h_deep<1, false, 16, DS_NODE_PF>(&H2[mt * 32][0], 256, tail_ws(itl), ring, 0, acc, lo);
+      split_finish<1>(acc, lo);
+      acc_store<1, 512>(acc, c.ws.ac + (size_t)(row0 + mt * 32) * 512 + (itl - 2) * 32, Nn - row0 - mt * 32, [](int, float v) { return v; });
     }
   }
 }
@@ -1857,9 +2082,20 @@ void launch_edge_geom(const Ctx& c, int blk, hipStream_t s) {
   ProfScope ps(PROF_EDGE_GEOM, s);
   hipLaunchKernelGGL(k_edge_geom, dim3((c.L.Pp + 63) / 64), dim3(256), 0, s, c, blk);
 }
+// Node-row tile form (ds_set_node_tile): 64 rows per 512-thread workgroup (k_node_update64, k_node_qkv_wide) once the launch has
+// DS_NODE_TILE64_MIN_PER_CU such tiles per CU, else the 32-row / column-split forms, which give a small launch more workgroups to
+// spread.  Same bits either way.
+int g_node_tile = -1;   // -1: from the environment (DIFFSPECTRA_NODE_TILE), else by size; 32 / 64: force
+bool node_tile64(const Ctx& c) {
+  static const int env_tile = [] { const char* e = getenv("DIFFSPECTRA_NODE_TILE"); return e ? atoi(e) : -1; }();
+  const int pick = g_node_tile > 0 ? g_node_tile : env_tile;
+  if (pick == 32 || pick == 64) return pick == 64;
+  return (c.L.Nn + 63) / 64 >= DS_NODE_TILE64_MIN_PER_CU * device_cus();
+}
 void launch_node_qkv(const Ctx& c, int blk, hipStream_t s) {
   ProfScope ps(PROF_NODE_QKV, s);
-  hipLaunchKernelGGL(k_node_qkv<4>, dim3((c.L.Nn + 63) / 64, 2), dim3(256), 0, s, c, blk);
+  if (node_tile64(c)) hipLaunchKernelGGL(k_node_qkv_wide, dim3((c.L.Nn + 63) / 64), dim3(512), 0, s, c, blk);
+  else hipLaunchKernelGGL(k_node_qkv, dim3((c.L.Nn + 63) / 64, 2), dim3(256), 0, s, c, blk);
 }
 void launch_attn(const Ctx& c, int blk, hipStream_t s) {
   ProfScope ps(PROF_ATTN, s);
@@ -1869,7 +2105,8 @@ void launch_node_n2e(const Ctx& c, int blk, hipStream_t s) { hipLaunchKernelGGL(
 template <bool N2E>   // true: node2edge_lin inside the kernel; false: k_node_n2e has run
 void launch_node_update(const Ctx& c, int blk, hipStream_t s) {
   ProfScope ps(PROF_NODE_UPDATE, s);
-  hipLaunchKernelGGL(k_node_update<N2E>, dim3((c.L.Nn + 31) / 32), dim3(256), 0, s, c, blk);
+  if (node_tile64(c)) hipLaunchKernelGGL(k_node_update64<N2E>, dim3((c.L.Nn + 63) / 64), dim3(512), 0, s, c, blk);
+  else hipLaunchKernelGGL(k_node_update<N2E>, dim3((c.L.Nn + 31) / 32), dim3(256), 0, s, c, blk);
 }
 void launch_edge_update(const Ctx& c, int blk, hipStream_t s) {
   if (c.L.Pp <= 0) return;
@@ -1966,7 +2203,8 @@ int ds_stage_readout(const ds_weights* w, const ds_layout* L, ds_workspace* ws, 
 //   main : edge_geom(b) -> [q|k|v(b)] attn(b) -> n2e(b) -> edge_update(b) -> [side(b)] equi_pairs(b) -> pos_update(b)
 //   side :                                        [n2e(b)] node_update(b) -> q|k|v(b + 1)
 // k_equi_pairs waits for the side stream (it needs `ac`, and as a persistent one-workgroup-per-CU kernel it must not find CUs taken).
-// One workgroup of either side fits beside one of the other in a CU's LDS (66.5 + 71 kB).  Results do not depend on the mode: the
+// One workgroup of either side fits beside one of the other in a CU's LDS (66.5 + 71 kB; the sizes at which two streams are the
+// default are below the 64-row rule of launch_node_update).  Results do not depend on the mode: the
 // same kernels' arithmetic, ws.u from k_node_n2e bit-identical to the fused form (tests: stage API = one stream, forward = two).
 struct SideStream {
   hipStream_t s = nullptr;
@@ -2020,6 +2258,12 @@ static int forward_blocks_two_streams(const ds_weights* w, const ds_layout* L, d
 int ds_set_two_stream(int on) {   // -1: follow DIFFSPECTRA_TWO_STREAM (default on); 0 / 1: force.  Returns the previous setting.
   const int prev = g_two_stream;
   g_two_stream = on;
+  return prev;
+}
+
+int ds_set_node_tile(int rows) {   // -1: follow DIFFSPECTRA_NODE_TILE, else by size; 32 / 64: force.  Returns the previous setting.
+  const int prev = g_node_tile;
+  g_node_tile = (rows == 32 || rows == 64) ? rows : -1;
   return prev;
 }
 

@@ -56,6 +56,7 @@ def load_library() -> C.CDLL:
     abi.TRAINING.bind(lib)               # headers declare something the .so lacks
     abi.SETS.bind(lib)
     abi.VALENCE.bind(lib)
+    abi.TILES.bind(lib)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
     mine = [C.sizeof(t) for t in (DsWeights, DsLayout, DsWorkspace, DsGemmArgs)]

@@ -7,7 +7,7 @@
  * Python mirror turns them into RuntimeError).  All buffers are caller-owned device memory
  * (PyTorch-ROCm allocations in the shipped host code); weights are a caller-owned packed buffer
  * described by ds_weights.  The library's own state is process-global and never changes a result:
- * the stream-mode switch (ds_set_two_stream), one side stream with its events per device
+ * the stream-mode switch (ds_set_two_stream), the node-row tile switch (ds_set_node_tile, diffspectra_tiles.h), one side stream with its events per device
  * (ds_forward), the compute-unit count per device, and the timing hook (ds_profile_config).
  *
  * Reference interfaces replaced (file:line in /root/reference):

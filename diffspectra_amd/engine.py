@@ -56,6 +56,7 @@ def load_library() -> C.CDLL:
     abi.TRAINING.bind(lib)               # headers declare something the .so lacks
     abi.SETS.bind(lib)
     abi.VALENCE.bind(lib)
+    abi.GROUPS.bind(lib)
     abi.TILES.bind(lib)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
@@ -797,6 +798,39 @@ def fragment_records(rec: torch.Tensor, n: torch.Tensor, keep: torch.Tensor, bon
                         [(torch.uint8, (RECORD_BYTES,)), (torch.int32, ())], prefix="dsv_", also=[keep])
 
 
+# ----------------------------------------------------------------------------------------- functional groups and aromaticity
+
+GROUPS_CONSTS = abi.GROUPS.consts         # include/diffspectra_groups.h
+GROUPS_OK, GROUPS_UNUSABLE, GROUPS_INVALID = (GROUPS_CONSTS["DSG_" + k] for k in ("OK", "UNUSABLE", "INVALID"))
+NUM_GROUPS = GROUPS_CONSTS["DSG_NUM_GROUPS"]
+
+
+def group_records(rec: torch.Tensor, n: torch.Tensor):
+    """``dsg_group_records``: the functional groups and the aromatic atoms of every record (definitions in ``include/diffspectra_groups.h``: the
+    17 groups of the reference's ``compute_metrics.py:38-56`` as predicates on the record graph, on top of the project's own, order-free
+    aromaticity rule, whose parity with RDKit is unpinned).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(groups [P] i32, aromatic_mask [P] i32, status [P] u8)`` on the current stream
+    without synchronising: bit g of ``groups`` = group g is present, bit i of ``aromatic_mask`` = atom i is aromatic, status ``GROUPS_UNUSABLE``
+    (2: n = 0, a type above 4, a bond byte above 3) zeroes the row.  Checked, never converted; no CPU path."""
+    i32 = (torch.int32, ())
+    return _record_call("group_records", [(rec, n)], None, [], [i32, i32, (torch.uint8, ())], prefix="dsg_")
+
+
+def group_similarity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                             ref_index: Optional[torch.Tensor] = None):
+    """``dsg_group_similarity_records``: the functional groups of both molecules of each of P (generated, ground-truth) pairs and the two
+    counts behind their Jaccard similarity - the reference's "Functional Group Similarity" (``compute_metrics.py:117-144``).
+
+    The tensors are those of ``match_records``.  Returns the device tensors ``(common [P] i32, either [P] i32, groups [P, 2] i32, status [P] u8)``,
+    enqueued on the current stream without synchronising: the sizes of the intersection and of the union of the two group sets, the group
+    words (generated, ground truth), status ``GROUPS_OK`` (0), ``GROUPS_UNUSABLE`` (2: a record of the pair is unusable) or ``GROUPS_INVALID`` (3:
+    ``ref_index`` outside the table); a pair that is not ok has ``common = either = -1`` and ``groups = 0``.  Checked, never converted."""
+    i32 = (torch.int32, ())
+    return _record_call("group_similarity_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [], [i32, i32, (torch.int32, (2,)), (torch.uint8, ())],
+                        prefix="dsg_")
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -983,6 +1017,14 @@ class DmtEngine:
     def fragment_records(self, rec, n, keep, bonds_from: int = 0, charge_rule: bool = True):
         """``engine.fragment_records`` on this engine's library."""
         return fragment_records(rec, n, keep, bonds_from, charge_rule)
+
+    def group_records(self, rec, n):
+        """``engine.group_records`` on this engine's library (the functional groups need no weights)."""
+        return group_records(rec, n)
+
+    def group_similarity_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None):
+        """``engine.group_similarity_records`` on this engine's library."""
+        return group_similarity_records(prb_rec, prb_n, ref_rec, ref_n, ref_index)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

@@ -104,6 +104,24 @@ def _structure_summary(run, table, top_k: int) -> Dict:
     return out
 
 
+def _functional_group_summary(run, table, top_k: int) -> Dict:
+    """The reference's "Functional Group Similarity" line of one finished run (the pairs of ``_structure_summary``), and how often each group
+    occurs among the generated molecules."""
+    from .structure_metrics import FUNCTIONAL_GROUP_NAMES, _host_sum, functional_group_similarity_batch, topk_groups
+    dev = run.records_by_slot.device
+    ref, prb = (table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms))
+    alike = functional_group_similarity_batch(ref, prb, ref_index=run.slot_ds, engine=run.eng)
+    ok = alike.valid
+    n_ok, P = int(ok.sum()), ok.numel()
+    mine = alike.groups[:, 0]
+    rate = lambda g: float((torch.bitwise_and(mine, 1 << g) != 0).sum()) / P if P else 0.0
+    entry = dict(similarity=alike.similarity, status=alike.status, mean=_host_sum(alike.similarity[ok]) / n_ok if n_ok else None,
+                 undefined=P - n_ok, presence_rate={name: rate(g) for g, name in enumerate(FUNCTIONAL_GROUP_NAMES)})
+    if top_k > 1:
+        entry["top_k"] = topk_groups(alike.similarity, alike.status, top_k)
+    return entry
+
+
 def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = "eval",
                          metric_fns: Optional[Dict[str, Callable]] = None, structure_metrics: bool = False, known_records=None):
     """Sampling evaluation over the configured checkpoints; returns ``{ckpt: {'processed_mols', 'gt_pos', 'gt_rdmols',
@@ -156,6 +174,14 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     set metrics by RDKit sanitisation, and a caller who wants that passes the mask on:
     ``get_set_similarity_metric(test)(generated, keep=metrics['structure']['metric_2d']['valid'])``.
 
+    With ``config.eval.functional_groups`` true ``metrics['structure']['functional_groups']`` is the reference's "Functional Group Similarity"
+    (``compute_metrics.py:117-144``, ``dsg_group_similarity_records``): ``similarity`` (f64 device tensor, one per slot: the Jaccard index of the
+    groups present in the generated molecule and in its ground truth, 1.0 when neither has one, NaN for a pair that is not ok), ``status`` (0
+    ok, 2 a record of the pair is unusable, 3 invalid), ``mean`` over the ok pairs (summed on the host; ``None`` without any), ``undefined`` (the
+    pairs that are not ok), ``presence_rate`` (group name -> fraction of the generated molecules that have it) and, with K > 1, ``top_k =
+    topk_groups(...)`` (``structure_metrics.functional_group_similarity_batch``, which states the deviations: the project's own aromaticity
+    rule, unpinned against RDKit; every usable pair is scored, with no RDKit filter).  Without the flag the dict has no such key.
+
     ``test_ds=None`` reads the reference's processed files under ``config.data.root`` (``run_lib.py:313`` ->
     ``build_dataset.py:31-42``: the 'test' entry of ``split_dict_diffspectra_qm9.pt``) into the device-resident table of
     ``qm9s_reader.ProcessedQM9S.packed_table`` - no PyG, no per-molecule Python."""
@@ -198,6 +224,8 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
         metrics = {name: fn(processed_mols, gt_pos, gt_rdmols) for name, fn in (metric_fns or {}).items()}
         if structure_metrics:
             metrics["structure"] = _structure_summary(run, test_ds, top_k)
+            if getattr(config.eval, "functional_groups", False):
+                metrics["structure"]["functional_groups"] = _functional_group_summary(run, test_ds, top_k)
             if getattr(config.eval, "sub_geometry", False):
                 from .structure_metrics import get_sub_geometry_metric
                 if geometry_fn is None:

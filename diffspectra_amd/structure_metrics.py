@@ -54,6 +54,16 @@ unpinned against RDKit; ``Unique`` / ``Novelty`` count constitution-level classe
 SMILES; the records hold Kekule orders only; a record with ``n = 0`` (or with a byte outside the alphabet) is UNUSABLE: it counts in every
 denominator and in no numerator, where the reference would count an empty molecule as stable and valid.
 
+Whether a generated molecule carries the ground truth's chemistry is ``functional_group_similarity_batch`` / ``topk_groups``: the reference's
+"Functional Group Similarity" (``compute_metrics.py:117-144``: the Jaccard index of the sets of functional groups present, 17 patterns,
+``compute_metrics.py:38-56``).  ``functional_groups`` gives the per-molecule group word and the aromatic atoms (``dsg_group_records``,
+``csrc/ds_groups.hip``; every definition in ``include/diffspectra_groups.h``).  Unlike every metric above it does not take the Kekule orders at
+face value: it perceives aromatic atoms by the project's own, order-free rule (C, N, O; simple cycles of 5 and 6 atoms; six electrons), so
+both Kekule drawings of a ring give the same groups.  Deviations: that rule restates RDKit's default model as remembered and is unpinned
+against RDKit (fused perimeters, other ring sizes, O+ and S are not perceived); the predicates restate the reference's patterns on the record
+graph with implicit hydrogens filled to the valence table of ``valence_batch``; sulfide and thiol are never present (no sulfur among the five
+types); and every usable pair is scored, where the reference sees only molecules that survived RDKit - ``valence_batch(...).valid`` filters.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -783,3 +793,76 @@ def get_edm_metric_3d(known=None, engine=None):
     ``get_edm_metric_2d``, with the bond orders derived from the distances (``get_bond_order``, the arithmetic of ``ds_check_stability``),
     no charges and ``allowed_bonds``; the largest fragments carry the derived orders.  The same deviations apply."""
     return _edm_metric("distance", known, engine)
+
+
+# ------------------------------------------------------------------------------------------------------------------ functional groups
+
+FUNCTIONAL_GROUP_NAMES = ("alkane", "alkene", "alkyne", "arene", "alcohol", "ether", "aldehyde", "ketone", "carboxylic acid", "ester", "haloalkane",
+                          "acyl halide", "amine", "amide", "nitrile", "sulfide", "thiol")         # bit order of include/diffspectra_groups.h
+
+
+class FunctionalGroups(NamedTuple):
+    """Per-record device tensors of ``dsg_group_records``."""
+    groups: torch.Tensor          # [P] i32: bit g = group ``FUNCTIONAL_GROUP_NAMES[g]`` is present
+    aromatic_mask: torch.Tensor   # [P] i32: bit i = atom i is aromatic (the project's rule; unpinned against RDKit)
+    status: torch.Tensor          # [P] u8: 0 ok, 2 unusable (n = 0, a type above 4, a bond byte above 3): the row is 0
+
+    @property
+    def usable(self) -> torch.Tensor:
+        return self.status == 0
+
+    def present(self, name: str) -> torch.Tensor:
+        """``[P] bool``: the molecule has the group ``name`` (False for an unusable record)."""
+        if name not in FUNCTIONAL_GROUP_NAMES:
+            raise ValueError(f"{name!r} is none of {list(FUNCTIONAL_GROUP_NAMES)}")
+        return torch.bitwise_and(self.groups, 1 << FUNCTIONAL_GROUP_NAMES.index(name)) != 0
+
+    def names(self, p: int) -> tuple:
+        """The names of the groups of row ``p``, in bit order (a host helper: synchronises)."""
+        word = int(self.groups[p])
+        return tuple(name for g, name in enumerate(FUNCTIONAL_GROUP_NAMES) if (word >> g) & 1)
+
+
+class GroupSimilarity(NamedTuple):
+    """Per-pair tensors of ``functional_group_similarity_batch``."""
+    similarity: torch.Tensor      # [P] f64: common / either, 1.0 when neither molecule has a group, NaN for a pair that is not ok
+    common: torch.Tensor          # [P] i32: groups both molecules have; -1 for a pair that is not ok
+    either: torch.Tensor          # [P] i32: groups at least one of them has; -1 for a pair that is not ok
+    groups: torch.Tensor          # [P, 2] i32: the group words of the generated molecule and of its ground truth; 0 for a pair that is not ok
+    status: torch.Tensor          # [P] u8: 0 ok, 2 a record of the pair is unusable, 3 invalid row
+
+    @property
+    def valid(self) -> torch.Tensor:
+        return self.status == 0
+
+
+def functional_groups(records: torch.Tensor, n_atoms, engine=None) -> FunctionalGroups:
+    """The functional groups and the aromatic atoms of every record of ``records [P, 1248] u8`` (GPU) in one launch of ``dsg_group_records``:
+    the 17 groups of the reference's ``compute_metrics.py:38-56`` as predicates on the record graph (``include/diffspectra_groups.h`` states
+    them), with aromaticity perceived by the project's own order-free rule - unpinned against RDKit, which cannot be run here.  Device tensors,
+    no synchronisation."""
+    from . import engine as E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    return FunctionalGroups(*(engine if engine is not None else E).group_records(records, n))
+
+
+def functional_group_similarity_batch(ref, prb, ref_index=None, engine=None) -> GroupSimilarity:
+    """The reference's "Functional Group Similarity" (``compute_metrics.py:117-144``) of every generated molecule and its ground truth
+    (``dsg_group_similarity_records``, ``csrc/ds_groups.hip``): the Jaccard index of the two sets of groups present, 1.0 when both are empty.
+    Every usable pair is scored; the reference scores only molecules that survived RDKit, and ``valence_batch(...).valid`` is the filter for
+    that.  Deviations are those of ``functional_groups``.  Arguments as ``graph_identity_batch``.  Device tensors, no synchronisation."""
+    common, either, groups, status = _pair_call("group_similarity_records", engine, ref, prb, ref_index)
+    c, u = common.double(), either.double()
+    sim = torch.where(either == 0, torch.ones_like(c), c / torch.where(either == 0, torch.ones_like(u), u))
+    sim = torch.where(status == 0, sim, torch.full_like(sim, float("nan")))
+    return GroupSimilarity(sim, common, either, groups, status)
+
+
+def topk_groups(similarity: torch.Tensor, status: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:
+    """Best-of-K reductions of ``functional_group_similarity_batch`` over the K consecutive candidates of every spectrum, shaped like
+    ``topk_morgan``: ``best [S] f64`` (the largest similarity among the ok candidates, NaN when none of the K is ok), ``best_index [S] i64`` (the
+    first candidate with it, -1 when none is ok) and ``mean_best`` (mean of ``best`` over the spectra that have one, a 0-dim f64 tensor; NaN
+    without any).  Plain torch reductions on the tensors' device."""
+    if top_k < 1 or similarity.numel() % top_k or status.shape != similarity.shape:
+        raise ValueError(f"{similarity.numel()} pairs (status: {status.numel()}) are not a whole number of top_k = {top_k} groups")
+    return topk_morgan(torch.where(status == 0, similarity.to(torch.float64), torch.full_like(similarity, float("nan"), dtype=torch.float64)), top_k)

@@ -31,6 +31,8 @@
  *   ds_geometry_count_records / cal_bond_distance, cal_bond_angle, cal_dihedral_angle          evaluation/cal_geometry.py:14-216
  *   ds_geometry_fill_records
  *   ds_mmd_1d_segments          compute_mmd                                                    evaluation/mmd.py:6-63
+ *   dsg_group_records /         identify_functional_groups, functional_group_similarity (diffspectra_groups.h)   compute_metrics.py:38-56,117-144
+ *   dsg_group_similarity_records
  *   ds_gemm / ds_spec_*   SpecFormer.forward                  models/specformer.py:77-120,167-200,279-309,345-425,457-470
  *
  * Data layout ("packed-ragged", symmetric pair storage — DESIGN.md §3):

@@ -57,6 +57,7 @@ def load_library() -> C.CDLL:
     abi.SETS.bind(lib)
     abi.VALENCE.bind(lib)
     abi.GROUPS.bind(lib)
+    abi.SCAFFOLD.bind(lib)
     abi.TILES.bind(lib)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
@@ -831,6 +832,24 @@ def group_similarity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec
                         prefix="dsg_")
 
 
+# ----------------------------------------------------------------------------------------- scaffolds, ring atoms, ring counts
+
+SCAFFOLD_CONSTS = abi.SCAFFOLD.consts     # include/diffspectra_scaffold.h
+SCAFFOLD_OK, SCAFFOLD_UNUSABLE = SCAFFOLD_CONSTS["DSK_OK"], SCAFFOLD_CONSTS["DSK_UNUSABLE"]
+
+
+def scaffold_masks(rec: torch.Tensor, n: torch.Tensor):
+    """``dsk_scaffold_masks``: the Bemis-Murcko scaffold atoms, the ring atoms and the ring count of every record (definitions in
+    ``include/diffspectra_scaffold.h``: the 2-core of the heavy graph plus its exocyclic atoms, ring bonds by reachability, the cyclomatic
+    number of the core; the scaffold rule restates RDKit's ``GetScaffoldForMol`` and is unpinned against RDKit).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(scaffold_mask [P] i32, ring_mask [P] i32, summary [P, 4] i32, status [P] u8)`` on
+    the current stream without synchronising: the masks hold a bit per atom, ``summary`` is (heavy atoms, scaffold atoms, rings, ring atoms),
+    status ``SCAFFOLD_UNUSABLE`` (3: n = 0, a type above 4, a bond byte above 3) zeroes the row.  Checked, never converted; no CPU path."""
+    i32 = (torch.int32, ())
+    return _record_call("scaffold_masks", [(rec, n)], None, [], [i32, i32, (torch.int32, (4,)), (torch.uint8, ())], prefix="dsk_")
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -1025,6 +1044,10 @@ class DmtEngine:
     def group_similarity_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None):
         """``engine.group_similarity_records`` on this engine's library."""
         return group_similarity_records(prb_rec, prb_n, ref_rec, ref_n, ref_index)
+
+    def scaffold_masks(self, rec, n):
+        """``engine.scaffold_masks`` on this engine's library (the scaffolds need no weights)."""
+        return scaffold_masks(rec, n)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

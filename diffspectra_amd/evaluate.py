@@ -122,6 +122,25 @@ def _functional_group_summary(run, table, top_k: int) -> Dict:
     return entry
 
 
+def _scaffold_summary(run, table, top_k: int, scaffold_fn, min_rings: int) -> Dict:
+    """The "Scaf" number of one finished run against the test table (``scaffold_fn``: ``get_scaffold_metric`` of its records) and, over the
+    pairs of ``_structure_summary``, whether every generated molecule shares the scaffold of its ground truth."""
+    from .structure_metrics import scaffold_identity_batch, topk_identity
+    dev = run.records_by_slot.device
+    ref, prb = (table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms))
+    entry = dict(scaffold_fn(prb))
+    alike = scaffold_identity_batch(ref, prb, ref_index=run.slot_ds, min_rings=1, engine=run.eng)
+    ok = alike.status == 0
+    n_ok = int(ok.sum())
+    same = dict(same=alike.same, status=alike.status, rate=int(alike.same[ok].sum()) / n_ok if n_ok else None, undecided=int(alike.undecided))
+    if top_k > 1:
+        top = topk_identity(alike.same.to(torch.uint8), top_k)                   # 1 = same scaffold; a pair that is not ok is a miss
+        same["top_k"] = dict(hit=top["hit"], first_hit=top["first_hit"], acc_at_k=top["acc_at_k"])
+    entry["same_scaffold"] = same
+    entry["min_rings"] = min_rings
+    return entry
+
+
 def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = "eval",
                          metric_fns: Optional[Dict[str, Callable]] = None, structure_metrics: bool = False, known_records=None):
     """Sampling evaluation over the configured checkpoints; returns ``{ckpt: {'processed_mols', 'gt_pos', 'gt_rdmols',
@@ -162,8 +181,18 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     the test table, ``nearest`` / ``nearest_index`` (device tensors: every kept generated molecule's similarity to, and the table row of, its
     nearest test molecule), ``n_generated`` / ``n_test`` and, when ``known_records = (records [*, 1248] u8, n_atoms [*])`` of the training
     molecules is given, ``novelty`` (``structure_metrics.get_set_similarity_metric``, which states the deviations: the MOSES definitions are
-    restated and unpinned, one representative per constitution-level class stands for ``set(smiles)``, no RDKit sanitisation filter; FCD, Frag
-    and Scaf are not computed).  Without the flag the dict has no such key.
+    restated and unpinned, one representative per constitution-level class stands for ``set(smiles)``, no RDKit sanitisation filter; FCD and Frag
+    are not computed (Scaf: ``get_scaffold_metric``)).  Without the flag the dict has no such key.
+
+    With ``config.eval.scaffold`` true ``metrics['structure']['scaffold']`` is the "Scaf" number of the same line
+    (``evaluation/mose_metric.py:111-113``): the dict of ``structure_metrics.get_scaffold_metric`` of the generated records against ALL records
+    of the test table (``scaf``, the cosine similarity of the Bemis-Murcko scaffold counts; ``n_generated`` / ``n_test``, ``with_scaffold_*``,
+    ``distinct_*``, ``shared``, ``scaffold_class``, ``mean_rings``), with ``min_rings`` = ``config.eval.scaffold_min_rings`` when present, else
+    MOSES's 2, reported as ``min_rings``; and ``same_scaffold``: per slot, does the generated molecule share the scaffold of its ground truth
+    (``scaffold_identity_batch`` with ``min_rings=1``: ``same`` and ``status`` device tensors, ``rate`` over the ok pairs - ``None`` without
+    any -, ``undecided`` and, with K > 1, ``top_k`` with ``hit`` / ``first_hit`` / ``acc_at_k`` as ``topk_identity`` shapes them: a hit is any
+    candidate of the target that shares its scaffold).  The scaffold rule restates RDKit's and MOSES's as remembered and is unpinned against
+    both (``include/diffspectra_scaffold.h``).  Without the flag the dict has no such key.
 
     With ``config.eval.edm_metrics`` true ``metrics['structure']['metric_2d']`` and ``['metric_3d']`` are the reference's first two evaluation
     lines (``run_lib.py:371-387``): ``mol_stable``, ``atom_stable``, ``Validity``, ``Complete``, ``Unique`` and ``Novelty`` (against
@@ -207,6 +236,7 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     geometry_fn = None                            # the test side of the geometry MMD is extracted once, at the first checkpoint
     set_fn = None                                 # and so are the bit rows of the test molecules
     edm_fns = None
+    scaffold_fn = None                            # and the scaffolds of the test molecules
     for ckpt in checkpoint_ids(config):
         ckpt_path = os.path.join(workdir, "checkpoints", "checkpoint_{}.pth".format(ckpt))
         if not os.path.exists(ckpt_path):
@@ -238,6 +268,13 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                     known = None if known_records is None else (known_records[0].to(dev), known_records[1])
                     set_fn = get_set_similarity_metric((test_ds.gt_records.to(dev), test_ds.num_atom), known=known, engine=run.eng)
                 metrics["structure"]["set_similarity"] = set_fn((run.records_by_slot, torch.tensor(run.n_atoms)))
+            if getattr(config.eval, "scaffold", False):
+                from .structure_metrics import get_scaffold_metric
+                min_rings = int(getattr(config.eval, "scaffold_min_rings", 2))
+                if scaffold_fn is None:
+                    scaffold_fn = get_scaffold_metric((test_ds.gt_records.to(run.records_by_slot.device), test_ds.num_atom), min_rings=min_rings,
+                                                      engine=run.eng)
+                metrics["structure"]["scaffold"] = _scaffold_summary(run, test_ds, top_k, scaffold_fn, min_rings)
             if getattr(config.eval, "edm_metrics", False):
                 from .structure_metrics import get_edm_metric_2d, get_edm_metric_3d
                 if edm_fns is None:

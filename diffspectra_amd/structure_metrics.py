@@ -40,7 +40,15 @@ fingerprints into bit rows (``dss_fold_bits``), ``nearest_neighbour_similarity``
 ``internal_diversity`` reduce it, ``novelty`` is ``graph_classes`` on the known and the generated molecules together.  The MOSES definitions
 (``SNNMetric``; ``internal_diversity`` with p = 1, self-pairs included; 1024-bit radius-2 Morgan fingerprints) are restated from the package as
 remembered - MOSES is neither vendored by the reference nor runnable here, so parity with it is unpinned - and the fingerprints carry the
-deviations of ``morgan_similarity_batch``.  FCD, Frag and Scaf of that line are not reproduced.
+deviations of ``morgan_similarity_batch``.  FCD and Frag are not computed (Scaf: ``get_scaffold_metric``).
+
+How the ring systems of a generated set stand against the test set's is ``get_scaffold_metric``: the "Scaf" number of the same line
+(``evaluation/mose_metric.py:111-113``), the cosine similarity of the Bemis-Murcko scaffold counts.  ``scaffolds`` gives the per-molecule
+scaffold atoms, ring atoms and ring count (``dsk_scaffold_masks``, ``csrc/ds_scaffold.hip``; every definition in
+``include/diffspectra_scaffold.h``), ``scaffold_records`` the scaffold as a record of its own, ``scaffold_identity_batch`` the per-pair agreement.
+Deviations: the scaffold rule (the 2-core of the heavy graph plus the atoms multiply bonded to it) restates RDKit's ``GetScaffoldForMol`` and
+MOSES's ``compute_scaffolds`` as remembered and is unpinned against both; scaffold identity is constitution-level on Kekule orders unless
+``bond_orders=False``; there is no RDKit sanitisation filter.
 
 Whether the generated molecules are chemically sound is ``get_edm_metric_2d`` / ``get_edm_metric_3d``: the reference's first two evaluation lines,
 "Metric-3D || atom stability, mol stability, validity, complete" and "Metric-2D || ..., unique & valid, unique & valid & novelty"
@@ -653,7 +661,7 @@ def get_set_similarity_metric(test, known=None, n_bits: int = 1024, unique: bool
 
     ``unique=True`` keeps one representative - the lowest row - of every ``graph_classes`` class on both sides, where the reference takes
     ``list(set(smiles))``.  ``keep`` is an optional bool mask over the generated rows (the device-side stability mask, say): the reference's own
-    filter is RDKit sanitisation, which is not reproduced.  FCD, Frag and Scaf are not computed.  The MOSES definitions are restated from the
+    filter is RDKit sanitisation, which is not reproduced.  FCD and Frag are not computed (Scaf: ``get_scaffold_metric``).  The MOSES definitions are restated from the
     package as remembered and parity with MOSES is unpinned; identity is constitution-level (``graph_identity_batch``)."""
     from . import engine as E
     dev = test[0].device
@@ -866,3 +874,150 @@ def topk_groups(similarity: torch.Tensor, status: torch.Tensor, top_k: int) -> D
     if top_k < 1 or similarity.numel() % top_k or status.shape != similarity.shape:
         raise ValueError(f"{similarity.numel()} pairs (status: {status.numel()}) are not a whole number of top_k = {top_k} groups")
     return topk_morgan(torch.where(status == 0, similarity.to(torch.float64), torch.full_like(similarity, float("nan"), dtype=torch.float64)), top_k)
+
+
+# ------------------------------------------------------------------------------------------------------------------ scaffolds
+
+class Scaffolds(NamedTuple):
+    """Per-record device tensors of ``dsk_scaffold_masks``.  There is no ``core_mask``: the core is the scaffold without its exocyclic atoms,
+    and which scaffold atoms are exocyclic (outside the core) cannot be told from these four outputs without reading the record again; the
+    ring atoms are the part of the core that the outputs do name."""
+    scaffold_mask: torch.Tensor   # [P] i32: bit i = atom i belongs to the scaffold (the 2-core of the heavy graph plus its exocyclic atoms)
+    ring_mask: torch.Tensor       # [P] i32: bit i = atom i is a ring atom
+    summary: torch.Tensor         # [P, 4] i32: heavy atoms, scaffold atoms, rings, ring atoms
+    status: torch.Tensor          # [P] u8: 0 ok, 3 unusable (n = 0, a type above 4, a bond byte above 3): every other output of the row is 0
+
+    @property
+    def usable(self) -> torch.Tensor:
+        return self.status == 0
+
+    @property
+    def rings(self) -> torch.Tensor:
+        """``[P] i32``: the cyclomatic number of the core - RDKit's ``RingInfo.NumRings()`` of a molecule."""
+        return self.summary[:, 2]
+
+    def has_scaffold(self, min_rings: int = 2) -> torch.Tensor:
+        """``[P] bool``: the scaffold is non-empty and has at least ``min_rings`` rings (MOSES's ``compute_scaffold``; its default is 2)."""
+        return self.usable & (self.scaffold_mask != 0) & (self.rings >= min_rings)
+
+
+class ScaffoldIdentity(NamedTuple):
+    """What ``scaffold_identity_batch`` returns."""
+    same: torch.Tensor            # [P] bool: both molecules have no scaffold, or both have one and they are the same labelled graph
+    status: torch.Tensor          # [P] u8: 0 ok, 3 a record of the pair is unusable (``DSK_UNUSABLE``) or the row is invalid (``ref_index`` outside)
+    undecided: torch.Tensor       # 0-dim i64: the pairs whose scaffold comparison ran out of its budget; they count as different
+
+
+def scaffolds(records: torch.Tensor, n_atoms, engine=None) -> Scaffolds:
+    """The Bemis-Murcko scaffold atoms, the ring atoms and the ring count of every record of ``records [P, 1248] u8`` (GPU) in one launch of
+    ``dsk_scaffold_masks`` (``csrc/ds_scaffold.hip``; every definition in ``include/diffspectra_scaffold.h``): the scaffold is the 2-core of the
+    heavy graph plus the atoms multiply bonded to it - RDKit's ``GetScaffoldForMol`` restated, unpinned against RDKit, which cannot be run
+    here.  Device tensors, no synchronisation."""
+    from . import engine as E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    return Scaffolds(*(engine if engine is not None else E).scaffold_masks(records, n))
+
+
+def _scaffold_side(records, n, bond_orders, engine):
+    """``(Scaffolds, scaffold records, their atom counts)`` of a record table with ``n`` already ``[P] i32`` on the device: two launches."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    found = Scaffolds(*eng.scaffold_masks(records, n))
+    rec, count = eng.fragment_records(records, n, found.scaffold_mask, E.BONDS_RECORD, True)
+    if not bond_orders:
+        rec[:, shard._BOND].clamp_(max=1)
+    return found, rec, count
+
+
+def scaffold_records(records: torch.Tensor, n_atoms, bond_orders: bool = True, engine=None):
+    """``(records [P, 1248] u8, n_atoms [P] i32)`` of the scaffold of every molecule: its scaffold atoms (``scaffolds``) as a record of their own
+    (``dsv_fragment_records``) - heavy atoms only, in their original order, with the charges the reference applies to its RDKit atoms.
+    ``bond_orders=False`` sets every non-zero bond byte of the result to 1: the order-free framework, under which all Kekule drawings of a
+    ring system are one scaffold and an exocyclic ``=O`` becomes ``-O``.  An unusable or acyclic record gives 0 atoms.  No synchronisation."""
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    return _scaffold_side(records, n, bond_orders, engine)[1:]
+
+
+def scaffold_identity_batch(ref, prb, ref_index=None, min_rings: int = 1, bond_orders: bool = True, engine=None) -> ScaffoldIdentity:
+    """Does every generated molecule share the scaffold of its ground truth?  Arguments as ``graph_identity_batch``.  A molecule has a scaffold
+    iff ``Scaffolds.has_scaffold(min_rings)``.  Both molecules without one: same; exactly one without: different; otherwise the verdict of
+    ``graph_identity_batch`` on the two scaffold records (``scaffold_records(..., bond_orders)``), where an undecided verdict counts as
+    different and is counted in ``undecided``.  ``status`` is 0 for an ok pair and 3 for a pair with an unusable record (``DSK_UNUSABLE``) or
+    with ``ref_index`` outside the table (invalid); ``same`` is False there.  Device tensors, no synchronisation."""
+    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
+    dev = prb_rec.device
+    i32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    P, M = prb_rec.shape[0], ref_rec.shape[0]
+    idx = torch.arange(P, device=dev) if ref_index is None else torch.as_tensor(ref_index).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    r_found, r_rec, r_count = _scaffold_side(ref_rec, i32(ref_n), bond_orders, engine)
+    p_found, p_rec, p_count = _scaffold_side(prb_rec, i32(prb_n), bond_orders, engine)
+    inside = (idx >= 0) & (idx < M)
+    row = torch.where(inside, idx, torch.zeros_like(idx))
+    at = lambda t: t[row] if M else torch.zeros(P, dtype=t.dtype, device=dev)
+    ok = inside & at(r_found.usable) & p_found.usable
+    r_has, p_has = at(r_found.has_scaffold(min_rings)) & ok, p_found.has_scaffold(min_rings) & ok
+    verdict = graph_identity_batch((r_rec, r_count), (p_rec, p_count), ref_index=idx, engine=engine).verdict
+    both = r_has & p_has
+    same = ok & ((~r_has & ~p_has) | (both & (verdict == 1)))
+    from . import engine as E
+    status = torch.where(ok, torch.zeros_like(p_found.status), torch.full_like(p_found.status, E.SCAFFOLD_UNUSABLE))
+    return ScaffoldIdentity(same, status, (both & (verdict == 2)).sum())
+
+
+def get_scaffold_metric(test, min_rings: int = 2, unique: bool = True, bond_orders: bool = True, engine=None):
+    """The "Scaf" number of the reference's set metrics (``evaluation/mose_metric.py:111-113``; MOSES's ``compute_scaffolds``, ``ScafMetric`` and
+    ``cos_similarity``, restated from the package as remembered - parity with MOSES is unpinned) on record tensors: the cosine similarity of
+    the Bemis-Murcko scaffold counts of the generated and of the test molecules.  ``test`` is ``(records [*, 1248] u8 on the GPU, n_atoms [*])``
+    of the test molecules, analysed once, here.  Returns ``fn(generated, keep=None)``, ``generated`` another such pair; ``keep`` and ``unique``
+    mean what they mean in ``get_set_similarity_metric`` (one representative per ``graph_classes`` class of the MOLECULES).  ``fn`` gives a
+    dict: ``scaf`` (a Python float: with g_k and t_k the numbers of generated and of test molecules with scaffold k, ``sum g_k t_k /
+    sqrt(sum g_k^2 * sum t_k^2)`` from exact integers; NaN when either side has no scaffold), ``n_generated`` / ``n_test`` (molecules that
+    entered), ``with_scaffold_generated`` / ``with_scaffold_test`` (those that have a scaffold: non-empty, ``rings >= min_rings``),
+    ``distinct_generated`` / ``distinct_test`` / ``shared`` (numbers of scaffold classes), ``scaffold_class`` (i64 device tensor over the generated
+    rows that entered: the row of the class's lowest member in the table "test scaffolds, then generated scaffolds", -1 without a scaffold)
+    and ``mean_rings`` (a Python float over the usable generated rows that entered; NaN without any).
+
+    Deviations: two scaffolds are the same when ``graph_classes`` says so (atom type, applied charge, bond order), so two Kekule drawings of
+    a scaffold that no symmetry maps onto each other (2-cyclopropylpyridine) are two scaffolds - ``bond_orders=False`` compares order-free
+    frameworks instead, under which an exocyclic ``=O`` also equals ``-O``; there is no RDKit sanitisation
+    filter (``keep=`` takes the caller's mask); a record with several fragments contributes the scaffold of all of them together."""
+    import math
+    dev = test[0].device
+    i32 = lambda t, d: torch.as_tensor(t).to(device=d, dtype=torch.int32).reshape(-1).contiguous()
+
+    def side(rec, n):
+        """The rows that enter, what was found in them, and the scaffold records of those that have a scaffold."""
+        if unique:
+            rows = _class_representatives(rec, n, engine)
+            rec, n = rec[rows].contiguous(), n[rows].contiguous()
+        found, s_rec, s_n = _scaffold_side(rec, n, bond_orders, engine)
+        has = found.has_scaffold(min_rings)
+        rows = torch.nonzero(has).reshape(-1)
+        return found, has, s_rec[rows].contiguous(), s_n[rows].contiguous()
+
+    t_found, t_has, t_rec, t_n = side(test[0], i32(test[1], dev))
+    T = int(t_rec.shape[0])
+
+    def scaffold_metric(generated, keep=None):
+        g_rec, g_n = generated[0], i32(generated[1], generated[0].device)
+        if keep is not None:
+            rows = torch.nonzero(torch.as_tensor(keep).to(g_rec.device).bool().reshape(-1)).reshape(-1)
+            g_rec, g_n = g_rec[rows].contiguous(), g_n[rows].contiguous()
+        g_found, g_has, s_rec, s_n = side(g_rec, g_n)
+        G = int(s_rec.shape[0])
+        cls = graph_classes(torch.cat([t_rec.to(s_rec.device), s_rec]).contiguous(), torch.cat([t_n.to(s_n.device), s_n]).contiguous(), engine)
+
+        def count(ids):                                                          # molecules per scaffold class, at the class's own row
+            classes, members = torch.unique(ids, return_counts=True)
+            return torch.zeros(T + G, dtype=torch.int64, device=cls.device).index_put_((classes,), members)
+        t_count, g_count = count(cls[:T]), count(cls[T:])
+        dot, gg, tt = int((g_count * t_count).sum()), int((g_count * g_count).sum()), int((t_count * t_count).sum())
+        scaffold_class = torch.full((g_has.shape[0],), -1, dtype=torch.int64, device=cls.device)
+        scaffold_class[g_has] = cls[T:]
+        usable = g_found.usable
+        n_usable = int(usable.sum())
+        return dict(scaf=dot / math.sqrt(gg * tt) if gg and tt else float("nan"), n_generated=int(g_has.shape[0]), n_test=int(t_has.shape[0]),
+                    with_scaffold_generated=G, with_scaffold_test=T, distinct_generated=int((g_count > 0).sum()), distinct_test=int((t_count > 0).sum()),
+                    shared=int(((g_count > 0) & (t_count > 0)).sum()), scaffold_class=scaffold_class,
+                    mean_rings=int(g_found.rings[usable].to(torch.int64).sum()) / n_usable if n_usable else float("nan"))
+    return scaffold_metric

@@ -18,6 +18,7 @@
 
 #include "../../include/diffspectra_hip.h"
 #include "ds_records.h"
+#include "ds_refine.h"
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
@@ -37,57 +38,20 @@ struct Pair {                             // both molecules of a pair in LDS; ar
   unsigned char stack[MA][64];            // colours (ranks below 64) of every open level of the search, before its individualisation
   int cell[MA], atom[MA], cursor[MA];     // per level: the class that is split, its generated atom, the next ground-truth atom to try
   unsigned char inv[64], img[32];         // leaf: ground-truth atom of a colour; image of every generated atom
+  __device__ __forceinline__ const unsigned char* bonds(int side) const { return adj[side]; }
 };
 
-struct Ranked { int colour, eq_g, eq_r; bool leader; };
+using ds_refine::Ranked;                  // the joint ranking and the refinement of both molecules at once: ds_refine.h, PAIR = true
+using ds_refine::MISMATCH;
+using ds_refine::DISCRETE;
+using ds_refine::CELLS;
+constexpr ds_refine::Block SYNC{};        // one wave per workgroup: the workgroup barrier orders the pair's LDS traffic
 
-// Joint rank of `sig` over the active lanes of both sides: colour = lanes with a smaller signature (ties share a colour); eq_g / eq_r = atoms
-// of the generated / ground-truth side with this signature; leader = no lower atom of the own side has it.
-__device__ Ranked rank_jointly(Pair& S, unsigned long long sig, int n, int lane) {
-  const int idx = lane & 31;
-  const bool right = lane >= 32;
-  S.sig[lane] = sig;
-  __syncthreads();
-  Ranked r = {0, 0, 0, true};
-  for (int k = 0; k < n; ++k) {
-    const unsigned long long a = S.sig[k], b = S.sig[32 + k];
-    r.colour += (a < sig) + (b < sig);
-    r.eq_g += a == sig;
-    r.eq_r += b == sig;
-    if (k < idx && (right ? b : a) == sig) r.leader = false;
-  }
-  __syncthreads();
-  return r;
+__device__ __forceinline__ Ranked rank_jointly(Pair& S, unsigned long long sig, int n, int lane) {
+  return ds_refine::rank_jointly<true>(S, sig, n, lane, SYNC);
 }
-
-enum { MISMATCH = 0, DISCRETE = 1, CELLS = 2 };
-
-// Colour refinement to the stable colouring, both molecules at once.  Signature of an atom: its colour in the top 6 bits (so a round only
-// ever splits classes), below it the commutative sum over its bonded neighbours j of hash(colour_j) * (2 bond_ij + 1).  At most n + 1 rounds:
-// every round but the last adds a class and there are at most n.  Returns MISMATCH as soon as the sides' histograms differ, else DISCRETE
-// (every class one atom per side) or CELLS with `multi` = the generated atoms that share their class.
-__device__ int refine(Pair& S, int& colour, bool active, int n, int lane, unsigned long long& multi) {
-  const int idx = lane & 31, side = lane >> 5;
-  int classes = 0;
-  multi = 0ull;
-  for (int round = 0; round <= n; ++round) {
-    S.f[lane] = fmix((unsigned long long)colour + 1ull);
-    __syncthreads();
-    unsigned long long acc = 0ull;
-    if (active)
-      for (int j = 0; j < n; ++j) {
-        const unsigned b = S.adj[side][j * 32 + idx];
-        if (b) acc += S.f[side * 32 + j] * (unsigned long long)(2u * b + 1u);
-      }
-    const Ranked r = rank_jointly(S, ((unsigned long long)colour << 58) | (acc >> 6), n, lane);
-    if (active) colour = r.colour;
-    if (__ballot(active && r.eq_g != r.eq_r) != 0ull) return MISMATCH;
-    const int now = __popcll(__ballot(active && side == 0 && r.leader));
-    multi = __ballot(active && side == 0 && r.eq_g > 1);
-    if (now == classes) break;
-    classes = now;
-  }
-  return multi ? CELLS : DISCRETE;
+__device__ __forceinline__ int refine(Pair& S, int& colour, bool active, int n, int lane, unsigned long long& multi) {
+  return ds_refine::refine<true>(S, colour, active, n, lane, multi, SYNC);
 }
 
 // Leaf of the search: every colour names one atom per side, which is the only bijection this branch allows.  It is checked in full - it is a

@@ -58,6 +58,7 @@ def load_library() -> C.CDLL:
     abi.VALENCE.bind(lib)
     abi.GROUPS.bind(lib)
     abi.SCAFFOLD.bind(lib)
+    abi.SMILES.bind(lib)
     abi.TILES.bind(lib)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
@@ -850,6 +851,28 @@ def scaffold_masks(rec: torch.Tensor, n: torch.Tensor):
     return _record_call("scaffold_masks", [(rec, n)], None, [], [i32, i32, (torch.int32, (4,)), (torch.uint8, ())], prefix="dsk_")
 
 
+# ----------------------------------------------------------------------------------------- canonical SMILES
+
+SMILES_CONSTS = abi.SMILES.consts         # include/diffspectra_smiles.h
+SMILES_OK, SMILES_UNCERTIFIED, SMILES_OVERFLOW, SMILES_UNUSABLE = (SMILES_CONSTS["DSL_" + k] for k in ("OK", "UNCERTIFIED", "OVERFLOW", "UNUSABLE"))
+SMILES_TEXT_BYTES = SMILES_CONSTS["DSL_TEXT_BYTES"]
+
+
+def smiles_records(rec: torch.Tensor, n: torch.Tensor, max_nodes: int = 4096):
+    """``dsl_smiles_records``: the canonical SMILES string of every record (every definition in ``include/diffspectra_smiles.h``: hydrogens
+    folded into their neighbours, colour refinement with individualisation, the smallest certificate, a Kekule OpenSMILES subset; not
+    RDKit's canonical form).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(text [P, 384] u8, length [P] i32, status [P] u8, nodes [P] i32, atom_order
+    [P, 29] i32)`` on the current stream without synchronising: ``text`` is ASCII, zero after ``length``; status ``SMILES_OK`` (0),
+    ``SMILES_UNCERTIFIED`` (1: the search stopped at ``max_nodes`` individualisations; the string is valid, not canonical), ``SMILES_OVERFLOW``
+    (2: more than 99 ring numbers open or more than 384 bytes) or ``SMILES_UNUSABLE`` (3: n = 0, a type above 4, a bond byte above 3) - for 2
+    and 3 the row is empty; ``atom_order`` is the position of every record atom among the atoms of the string, -1 for folded hydrogens.
+    Checked, never converted; no CPU path."""
+    return _record_call("smiles_records", [(rec, n)], None, [_node_budget(max_nodes, GRAPH_MAX_NODES)],
+                        [(torch.uint8, (SMILES_TEXT_BYTES,)), (torch.int32, ()), (torch.uint8, ()), (torch.int32, ()), _MAP], prefix="dsl_")
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -1048,6 +1071,10 @@ class DmtEngine:
     def scaffold_masks(self, rec, n):
         """``engine.scaffold_masks`` on this engine's library (the scaffolds need no weights)."""
         return scaffold_masks(rec, n)
+
+    def smiles_records(self, rec, n, max_nodes: int = 4096):
+        """``engine.smiles_records`` on this engine's library (the strings need no weights)."""
+        return smiles_records(rec, n, max_nodes)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

@@ -141,6 +141,35 @@ def _scaffold_summary(run, table, top_k: int, scaffold_fn, min_rings: int) -> Di
     return entry
 
 
+def _smiles_summary(run, table, top_k: int, path: Optional[str] = None) -> Dict:
+    """The molecules of one finished run as text (``structure_metrics.smiles``): the generated strings by slot, the ground-truth strings of the
+    same slots, the reference's "Exact Match (SMILES)" over the pairs of ``_structure_summary``, and the file of ``config.eval.smiles_path``."""
+    from .shard import world_info
+    from .structure_metrics import smiles, smiles_exact_match, smiles_strings, topk_identity
+    dev = run.records_by_slot.device
+    gen = smiles(run.records_by_slot, torch.tensor(run.n_atoms), engine=run.eng)
+    truth = smiles(table.gt_records.to(dev), table.num_atom, engine=run.eng)
+    match = smiles_exact_match(truth, gen, ref_index=run.slot_ds)
+    generated, table_strings = smiles_strings(gen), smiles_strings(truth)
+    ground_truth = [table_strings[r] if 0 <= r < len(table_strings) else None for r in torch.as_tensor(run.slot_ds).reshape(-1).tolist()]
+    status = gen.status.cpu().tolist()
+    certified = [s for s, st in zip(generated, status) if st == 0]
+    ok = match.status == 0
+    n_ok = int(ok.sum())
+    entry = dict(generated=generated, ground_truth=ground_truth, same=match.same, status=gen.status, pair_status=match.status,
+                 exact_match=int(match.same.sum()) / n_ok if n_ok else None, unique=len(set(certified)) / len(certified) if certified else None,
+                 distinct=len(set(certified)), certified=len(certified), uncertified=status.count(1), overflow=status.count(2), unusable=status.count(3))
+    if top_k > 1:
+        top = topk_identity(match.same.to(torch.uint8), top_k)                   # 1 = the same string; a pair that is not certified is a miss
+        entry["top_k"] = dict(hit=top["hit"], first_hit=top["first_hit"], acc_at_k=top["acc_at_k"])
+    if path and world_info()[0] == 0:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            for slot, (g, t) in enumerate(zip(generated, ground_truth)):
+                f.write(f"{slot}\t{'' if g is None else g}\t{'' if t is None else t}\n")
+    return entry
+
+
 def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = "eval",
                          metric_fns: Optional[Dict[str, Callable]] = None, structure_metrics: bool = False, known_records=None):
     """Sampling evaluation over the configured checkpoints; returns ``{ckpt: {'processed_mols', 'gt_pos', 'gt_rdmols',
@@ -211,6 +240,17 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     topk_groups(...)`` (``structure_metrics.functional_group_similarity_batch``, which states the deviations: the project's own aromaticity
     rule, unpinned against RDKit; every usable pair is scored, with no RDKit filter).  Without the flag the dict has no such key.
 
+    With ``config.eval.smiles`` true ``metrics['structure']['smiles']`` holds the molecules as text, where the reference calls ``Chem.MolToSmiles``
+    (``run_lib.py:111-112``, ``compute_metrics.py:73-78,209-220``; ``dsl_smiles_records``): ``generated`` (one canonical SMILES string per slot,
+    ``None`` for an overflow or unusable record), ``ground_truth`` (the string of every slot's ground truth), ``same`` / ``status`` / ``pair_status``
+    (device tensors: the strings are certified and equal; the generated row's status 0 ok, 1 uncertified, 2 overflow, 3 unusable; the pair's),
+    ``exact_match`` (the reference's "Exact Match (SMILES)": the rate of ``same`` over the pairs with both sides certified, ``None`` without
+    any), ``unique`` (distinct strings over the certified generated rows, ``None`` without any; ``distinct`` and ``certified`` are the two
+    counts), ``uncertified`` / ``overflow`` / ``unusable`` (counts of generated rows) and, with K > 1, ``top_k`` with ``hit`` / ``first_hit`` /
+    ``acc_at_k`` as ``topk_identity`` shapes them.  With ``config.eval.smiles_path`` set, rank 0 also writes one ``slot<TAB>generated<TAB>ground
+    truth`` line per slot there (an empty field for ``None``).  The strings are canonical for this project, not RDKit's canonical form
+    (``include/diffspectra_smiles.h`` states the deviations).  Without the flag the dict has no such key.
+
     ``test_ds=None`` reads the reference's processed files under ``config.data.root`` (``run_lib.py:313`` ->
     ``build_dataset.py:31-42``: the 'test' entry of ``split_dict_diffspectra_qm9.pt``) into the device-resident table of
     ``qm9s_reader.ProcessedQM9S.packed_table`` - no PyG, no per-molecule Python."""
@@ -275,6 +315,8 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                     scaffold_fn = get_scaffold_metric((test_ds.gt_records.to(run.records_by_slot.device), test_ds.num_atom), min_rings=min_rings,
                                                       engine=run.eng)
                 metrics["structure"]["scaffold"] = _scaffold_summary(run, test_ds, top_k, scaffold_fn, min_rings)
+            if getattr(config.eval, "smiles", False):
+                metrics["structure"]["smiles"] = _smiles_summary(run, test_ds, top_k, getattr(config.eval, "smiles_path", None))
             if getattr(config.eval, "edm_metrics", False):
                 from .structure_metrics import get_edm_metric_2d, get_edm_metric_3d
                 if edm_fns is None:

@@ -72,6 +72,13 @@ against RDKit (fused perimeters, other ring sizes, O+ and S are not perceived); 
 graph with implicit hydrogens filled to the valence table of ``valence_batch``; sulfide and thiol are never present (no sulfur among the five
 types); and every usable pair is scored, where the reference sees only molecules that survived RDKit - ``valence_batch(...).valid`` filters.
 
+What the molecules are as TEXT is ``smiles`` / ``smiles_strings``: one canonical SMILES string per record (``dsl_smiles_records``,
+``csrc/ds_smiles.hip``; every definition in ``include/diffspectra_smiles.h``), which is what the reference gets from ``Chem.MolToSmiles``
+(``run_lib.py:111-112``, ``compute_metrics.py:73-78``, ``evaluation/mose_metric.py:12-21``); ``smiles_exact_match`` is its ``true_smi == pred_smi``
+(``compute_metrics.py:209-220``).  Deviations: the strings are canonical for THIS project, not RDKit's canonical form (compare them as
+molecules, never as text, with strings from elsewhere); the graph is the constitution-level one of ``graph_identity_batch`` with raw charge
+bytes; Kekule orders only, so two drawings of a ring give one string only where a symmetry maps one onto the other; any SMILES reader reads them.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -1021,3 +1028,71 @@ def get_scaffold_metric(test, min_rings: int = 2, unique: bool = True, bond_orde
                     shared=int(((g_count > 0) & (t_count > 0)).sum()), scaffold_class=scaffold_class,
                     mean_rings=int(g_found.rings[usable].to(torch.int64).sum()) / n_usable if n_usable else float("nan"))
     return scaffold_metric
+
+
+# ------------------------------------------------------------------------------------------------------------------ canonical SMILES
+
+class Smiles(NamedTuple):
+    """Per-record device tensors of ``dsl_smiles_records``."""
+    text: torch.Tensor            # [P, 384] u8: ASCII, zero after ``length``
+    length: torch.Tensor          # [P] i32
+    status: torch.Tensor          # [P] u8: 0 ok, 1 uncertified (valid string, not canonical: the search hit ``max_nodes``), 2 overflow, 3 unusable
+    nodes: torch.Tensor           # [P] i32 individualisations of the search (0: colour refinement alone ordered the atoms)
+    atom_order: torch.Tensor      # [P, 29] i32: position of every record atom among the atoms of the string, -1 for folded hydrogens and atoms >= n
+
+    @property
+    def certified(self) -> torch.Tensor:
+        return self.status == 0
+
+    @property
+    def has_text(self) -> torch.Tensor:
+        return self.status <= 1
+
+
+class SmilesMatch(NamedTuple):
+    """What ``smiles_exact_match`` returns."""
+    same: torch.Tensor            # [P] bool: both strings certified and equal byte for byte
+    status: torch.Tensor          # [P] u8: 0 both sides certified, else the larger of the two sides' statuses; 3 also for ``ref_index`` outside
+
+
+def smiles(records: torch.Tensor, n_atoms, max_nodes: int = 4096, engine=None) -> Smiles:
+    """The canonical SMILES string of every record of ``records [P, 1248] u8`` (GPU) in one launch of ``dsl_smiles_records``
+    (``csrc/ds_smiles.hip``; every definition in ``include/diffspectra_smiles.h``): plain hydrogens folded into their neighbours, the atoms ordered
+    by colour refinement with individualisation (at most ``max_nodes`` individualisations after the first leaf), a Kekule OpenSMILES subset
+    that any SMILES reader reads.  Canonical for this project - two usable records get the same certified string iff ``graph_identity_batch``
+    calls them identical - and NOT RDKit's canonical form.  Device tensors, no synchronisation; ``smiles_strings`` makes Python strings."""
+    from . import engine as E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    return Smiles(*(engine if engine is not None else E).smiles_records(records, n, max_nodes))
+
+
+def smiles_strings(result: Smiles) -> list:
+    """One ``str`` per row of a ``Smiles``, ``None`` for an overflow or unusable row: the one device-to-host copy of the text."""
+    text, length, status = result.text.cpu().numpy(), result.length.cpu().tolist(), result.status.cpu().tolist()
+    return [text[p, :length[p]].tobytes().decode("ascii") if status[p] <= 1 else None for p in range(len(status))]
+
+
+def smiles_exact_match(ref, prb, ref_index=None, max_nodes: int = 4096, engine=None) -> SmilesMatch:
+    """The reference's "Exact Match (SMILES)" (``true_smi == pred_smi``, ``compute_metrics.py:209-220``) per pair: ``ref`` and ``prb`` are ``(records
+    [*, 1248] u8, n_atoms [*])`` pairs on the GPU or ``Smiles`` results, ground truth first; ``ref_index [P]`` names the ground-truth row of every
+    generated molecule (``None``: row p).  ``same`` holds where both strings are certified (status 0) and equal byte for byte - for such pairs it
+    is the verdict of ``graph_identity_batch``; ``status`` is 0 there, else the larger status of the two sides, and 3 for a row outside the
+    table.  Device tensors, no synchronisation."""
+    side = lambda x: x if isinstance(x, Smiles) else smiles(x[0], x[1], max_nodes=max_nodes, engine=engine)
+    r, g = side(ref), side(prb)
+    dev = g.text.device
+    P, M = g.text.shape[0], r.text.shape[0]
+    if ref_index is None and M < P:
+        raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
+    idx = torch.arange(P, device=dev) if ref_index is None else torch.as_tensor(ref_index).to(device=dev, dtype=torch.int64).reshape(-1)
+    if idx.numel() != P:
+        raise ValueError(f"ref_index must name one ground-truth row per pair: {idx.numel()} for {P}")
+    inside = (idx >= 0) & (idx < M)
+    row = torch.where(inside, idx, torch.zeros_like(idx))
+    if M:
+        r_text, r_status = r.text.to(dev)[row], r.status.to(dev)[row]
+    else:
+        r_text, r_status = torch.zeros_like(g.text), torch.full_like(g.status, 3)
+    status = torch.where(inside, torch.maximum(r_status, g.status), torch.full_like(g.status, 3))
+    same = (status == 0) & (r_text == g.text).all(dim=1)
+    return SmilesMatch(same, status)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/diffspectra_hip.h"
+#include "../../include/diffspectra_step.h"
 #include "../../include/diffspectra_tiles.h"
 #include "ds_device.h"
 #include "ds_host.h"
@@ -89,10 +90,11 @@ __device__ __forceinline__ float rbf_feature(float x, int k, const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// Prologue: sinusoid features of the noise level (layers.py:283-288), [B,24] (17 used, rest 0).
-__global__ void k_time_feat(Ctx c, const float* __restrict__ noise_level) {
+// Prologue: sinusoid features of the noise level (layers.py:283-288), [rows,24] (17 used, rest 0); rows = B, or 1 in the uniform
+// prologue (ds_stage_time_uniform).
+__global__ void k_time_feat(Ctx c, const float* __restrict__ noise_level, int rows) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= c.L.B) return;
+  if (b >= rows) return;
   const float* w = GW(c, DS_GW_SIN_W);
   const float x = noise_level[b];
   float* f = c.ws.tfeat + (size_t)b * 24;
@@ -208,11 +210,24 @@ __global__ __launch_bounds__(256) void k_pair_init(Ctx c, const float* __restric
   const float* mean = GW(c, DS_GW_RBF_MEAN);
   const float* stdv = GW(c, DS_GW_RBF_STD);
   const float* astd = GW(c, DS_GW_RBF_ASTD);
-  for (int idx = tid; idx < T * 64; idx += 256) {
-    const int row = idx >> 6, k = idx & 63;
-    float v = 0.0f;
-    if (row0 + row < c.L.Pp) v = use_rbf ? rbf_feature(xs[row], k, mean, stdv, astd) : xs[row];  // zeros repeat (dmt.py:365)
-    X[row][4 + k] = v;
+  {   // 64 rows x 16 float4 pieces, one 16-lane DPP row per tile row (as k_edge_update stages its rows): a thread owns features
+      // 4 k4 .. 4 k4 + 3 of four rows and stores them as one 16-byte piece each (was: one feature of 16 rows, 16 four-byte stores)
+    const int k4 = tid & 15, rq = tid >> 4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int row = rq + 16 * u;
+      const float x = xs[row];
+      float4 v = make_float4(0, 0, 0, 0);
+      if (row0 + row < c.L.Pp) {
+        if (use_rbf) {
+          v.x = rbf_feature(x, 4 * k4, mean, stdv, astd); v.y = rbf_feature(x, 4 * k4 + 1, mean, stdv, astd);
+          v.z = rbf_feature(x, 4 * k4 + 2, mean, stdv, astd); v.w = rbf_feature(x, 4 * k4 + 3, mean, stdv, astd);
+        } else {
+          v = make_float4(x, x, x, x);   // zeros repeat (dmt.py:365)
+        }
+      }
+      *reinterpret_cast<float4*>(&X[row][4 + 4 * k4]) = v;
+    }
   }
   __syncthreads();
   const float* bias = GW(c, DS_GW_EDGE_EMB_B);
@@ -239,7 +254,11 @@ __global__ __launch_bounds__(256) void k_edge_geom(Ctx c, int blk) {
   // [x', rbf63 | e64] in the split-fp16 layout (ds_device.h): edge_emb runs on the f16 matrix pipe (the fp32 form was 256
   // 64-cycle MFMAs per workgroup, ~40 % of this kernel's time; now 96 32-cycle ones)
   __shared__ __attribute__((aligned(16))) _Float16 Xh[T][LDH];
-  __shared__ __attribute__((aligned(16))) float Y[T][64 + DS_LDP];
+  // the edge_emb product [T][64 + DS_LDP] lies over Xh, which is dead once every wave has its MFMAs behind it (a barrier of its own):
+  // 34.6 kB instead of 51.7 kB of LDS, four workgroups per CU instead of three - the kernel waits on memory (waves waiting 55 - 60 %
+  // of their cycles, VALU 14 - 18 % busy), so it gains by waves in flight, not by instructions saved
+  float (*Y)[64 + DS_LDP] = reinterpret_cast<float (*)[64 + DS_LDP]>(&Xh[0][0]);
+  static_assert(sizeof(float) * T * (64 + DS_LDP) <= sizeof(_Float16) * T * LDH, "Y fits in Xh");
   __shared__ __attribute__((aligned(16))) float xs[T];
   __shared__ int rmol[T];
   const int tid = threadIdx.x, row0 = blockIdx.x * T;
@@ -298,20 +317,21 @@ __global__ __launch_bounds__(256) void k_edge_geom(Ctx c, int blk) {
       split_store1(&Xh[row][0], 128, 64 + k, ev[j]);
     }
   }
-  {   // edge_emb (128 -> 64): wave w owns row tile w >> 1, column chunk w & 1; the whole weight chunk (8 k-blocks) is requested
-      // ahead of the barrier
+  {   // edge_emb (128 -> 64): wave w owns row tile w >> 1, column chunk w & 1; the first half of the weight chunk (4 of 8 k-blocks) is
+      // requested ahead of the barrier
     const int wv = tid >> 6, mt = wv >> 1, cc = wv & 1, lane = tid & 63;
     const WStreamH wse = wstream_h(BW(c, blk, DS_BW_EDGE_EMB_H), 64, 128, cc * 32);
-    WRingH<8> ring;
-    wring_h<8>(ring, wse, 0);
+    WRingH<4> ring;   // four k-blocks ahead, re-requested as they are consumed: 32 registers instead of 64 (four waves per SIMD)
+    wring_h<4>(ring, wse, 0);
     const float bcol = BW(c, blk, DS_BW_EDGE_EMB_B)[cc * 32 + (lane & 31)];
     __syncthreads();
     f32x16 acc[1], lo[1];
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[0][i] = bcol;
     acc_zero<1>(lo);
-    wave_mma_h_deep<1, false, 8, 8>(&Xh[mt * 32][0], 128, wse, ring, 0, acc, lo);
+    wave_mma_h_deep<1, false, 8, 4>(&Xh[mt * 32][0], 128, wse, ring, 0, acc, lo);
     split_finish<1>(acc, lo);
+    __syncthreads();   // Y overwrites Xh
 #pragma unroll
     for (int i = 0; i < 16; ++i) Y[mt * 32 + acc_row(i, lane >> 5)][cc * 32 + (lane & 31)] = acc[0][i];
   }
@@ -2131,30 +2151,44 @@ void ds_struct_sizes(int64_t* out) {
   out[3] = sizeof(ds_gemm_args);
 }
 
-int ds_stage_time(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* noise_level, const float* ctx_emb,
-                  void* stream) {
+// The step prologue.  rows = B: time_mlp of every molecule's noise level.  rows = 1 (ds_stage_time_uniform): all B noise levels are
+// equal, so time_mlp runs on noise_level[0] alone and k_temb_finish broadcasts the one row; only `+ ctx`, SiLU and the adaLN GEMM are
+// per molecule.  The single row goes through the GEMM tile form the B-row launch would take (dst::gemm_routed_as), so it carries
+// row 0's bits of that launch - and every row of it carries those, a row's result depending on nothing but the row.
+static int stage_time(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* noise_level, const float* ctx_emb,
+                      int rows, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Ctx c;
   if (!make_ctx(c, w, L, ws) || !noise_level) return DS_ERR_ARG;
   const int B = L->B;
   const int64_t* off = w->off + DS_NBLOCKS * DS_W_BLOCK_SLOTS;
-  hipLaunchKernelGGL(k_time_feat, dim3((B + 63) / 64), dim3(64), 0, s, c, noise_level);
+  hipLaunchKernelGGL(k_time_feat, dim3((rows + 63) / 64), dim3(64), 0, s, c, noise_level, rows);
   // time_mlp: Linear(17,1024) -> GELU -> Linear(1024,1024)  (dmt.py:252-257); tmid reuses ws->tmid, output in ws->ada scratch
   ds_gemm_args g{};
   g.A = ws->tfeat; g.lda = 24; g.Wp = w->base + off[DS_GW_TM1_W]; g.bias = w->base + off[DS_GW_TM1_B];
-  g.C = ws->tmid; g.ldc = 1024; g.M = B; g.K = 24; g.N = 1024; g.act = 2;
-  int st = ds_gemm(&g, stream);
+  g.C = ws->tmid; g.ldc = 1024; g.M = rows; g.K = 24; g.N = 1024; g.act = 2;
+  int st = dst::gemm_routed_as(&g, B, stream);
   if (st) return st;
-  float* tm3 = ws->ada;   // [B,1024] scratch inside the (larger) ada buffer, consumed before ada is produced
+  float* tm3 = ws->ada;   // [rows,1024] scratch inside the (larger) ada buffer, consumed before ada is produced
   g.A = ws->tmid; g.lda = 1024; g.Wp = w->base + off[DS_GW_TM3_W]; g.bias = w->base + off[DS_GW_TM3_B];
   g.C = tm3; g.K = 1024; g.act = 0;
-  st = ds_gemm(&g, stream);
+  st = dst::gemm_routed_as(&g, B, stream);
   if (st) return st;
   const size_t tot = (size_t)B * 1024;
-  hipLaunchKernelGGL(k_temb_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, c, (const float*)tm3, B, ctx_emb);
+  hipLaunchKernelGGL(k_temb_finish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, c, (const float*)tm3, rows, ctx_emb);
   // every *time_mlp Linear of the model in one GEMM: [B,1024] x [1024, DS_ADA_COLS]
   static_assert(ADAC % 32 == 0, "adaLN table width");
   return ds_gemm_split(ws->temb_silu, w->base + off[DS_GW_ADA_W], w->base + off[DS_GW_ADA_B], ws->ada, ADAC, B, 1024, ADAC, stream);
+}
+
+int ds_stage_time(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* noise_level, const float* ctx_emb,
+                  void* stream) {
+  return L ? stage_time(w, L, ws, noise_level, ctx_emb, L->B, stream) : DS_ERR_ARG;
+}
+
+int ds_stage_time_uniform(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* noise_level, const float* ctx_emb,
+                          void* stream) {
+  return stage_time(w, L, ws, noise_level, ctx_emb, 1, stream);
 }
 
 int ds_stage_init(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* xh, const float* edge_x,
@@ -2267,10 +2301,10 @@ int ds_set_node_tile(int rows) {   // -1: follow DIFFSPECTRA_NODE_TILE, else by 
   return prev;
 }
 
-int ds_forward(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* xh, const float* edge_x,
-               const float* cond_x, const float* cond_edge_x, const float* noise_level, const float* ctx_emb, float* out_xh,
-               float* out_edge, void* stream) {
-  int st = ds_stage_time(w, L, ws, noise_level, ctx_emb, stream);
+static int forward(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* xh, const float* edge_x, const float* cond_x,
+                   const float* cond_edge_x, const float* noise_level, const float* ctx_emb, float* out_xh, float* out_edge,
+                   bool uniform, void* stream) {
+  int st = uniform ? ds_stage_time_uniform(w, L, ws, noise_level, ctx_emb, stream) : ds_stage_time(w, L, ws, noise_level, ctx_emb, stream);
   if (st) return st;
   st = ds_stage_init(w, L, ws, xh, edge_x, cond_x, cond_edge_x, stream);
   if (st) return st;
@@ -2291,6 +2325,18 @@ int ds_forward(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const 
     }
   }
   return ds_stage_readout(w, L, ws, out_xh, out_edge, stream);
+}
+
+int ds_forward(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* xh, const float* edge_x,
+               const float* cond_x, const float* cond_edge_x, const float* noise_level, const float* ctx_emb, float* out_xh,
+               float* out_edge, void* stream) {
+  return forward(w, L, ws, xh, edge_x, cond_x, cond_edge_x, noise_level, ctx_emb, out_xh, out_edge, false, stream);
+}
+
+int ds_forward_uniform(const ds_weights* w, const ds_layout* L, ds_workspace* ws, const float* xh, const float* edge_x,
+                       const float* cond_x, const float* cond_edge_x, const float* noise_level, const float* ctx_emb, float* out_xh,
+                       float* out_edge, void* stream) {
+  return forward(w, L, ws, xh, edge_x, cond_x, cond_edge_x, noise_level, ctx_emb, out_xh, out_edge, true, stream);
 }
 
 int ds_profile_config(int kernel, int every, int max_samples) {

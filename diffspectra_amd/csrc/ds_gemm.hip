@@ -215,9 +215,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_big(GemmArgs g) {
   }
 }
 
-int gemm_dispatch(const GemmArgs& g, int act, hipStream_t s) {
+// route_rows: the row count that picks the tile form (g.M, except for dst::gemm_routed_as).  A row's result does not depend on how
+// many rows a launch has - both kernels clamp their loads to row M - 1 and guard their stores - but the two forms are not
+// held to the same bits, so a caller that needs the bits of a larger launch's rows names that launch's size.
+int gemm_dispatch(const GemmArgs& g, int act, hipStream_t s, int route_rows) {
   if (!g.A || !g.Wp || !g.C || g.M <= 0 || g.K <= 0 || g.N <= 0 || (g.cs && !g.csh)) return DS_ERR_ARG;
-  const bool big = g.M >= 512 && g.a_grp_rows <= 0 && g.c_grp_rows <= 0 && g.K % 64 == 0 && g.lda % 4 == 0 &&
+  const bool big = route_rows >= 512 && g.a_grp_rows <= 0 && g.c_grp_rows <= 0 && g.K % 64 == 0 && g.lda % 4 == 0 &&
                    (reinterpret_cast<uintptr_t>(g.A) & 15) == 0;
   using Kernel = void (*)(GemmArgs);   // one instantiation per activation code: 128-row tiles when big, else 64-row tiles
   static constexpr Kernel tile128[4] = {k_gemm_big<0>, k_gemm_big<1>, k_gemm_big<2>, k_gemm_big<3>};
@@ -228,12 +231,7 @@ int gemm_dispatch(const GemmArgs& g, int act, hipStream_t s) {
   return DST_CHECK_LAUNCH();
 }
 
-}  // namespace
-
-extern "C" {
-
-int ds_gemm(const ds_gemm_args* a, void* stream) {
-  if (!a) return DS_ERR_ARG;
+GemmArgs gemm_args(const ds_gemm_args* a) {
   GemmArgs g{};
   g.A = a->A; g.lda = a->lda; g.a_grp_rows = a->a_grp_rows; g.a_grp_stride = a->a_grp_stride;
   g.Wp = a->Wp; g.bias = a->bias;
@@ -241,7 +239,21 @@ int ds_gemm(const ds_gemm_args* a, void* stream) {
   g.M = a->M; g.K = a->K; g.N = a->N; g.Npad = (a->N + 31) & ~31;
   g.R = a->R; g.ldr = a->ldr; g.r_grp_rows = a->r_grp_rows;
   g.cs = a->col_scale; g.csh = a->col_shift; g.a_silu = a->a_silu;
-  return gemm_dispatch(g, a->act, (hipStream_t)stream);
+  return g;
+}
+
+}  // namespace
+
+int dst::gemm_routed_as(const ds_gemm_args* a, int route_rows, void* stream) {
+  if (!a || route_rows < a->M) return DS_ERR_ARG;
+  return gemm_dispatch(gemm_args(a), a->act, (hipStream_t)stream, route_rows);
+}
+
+extern "C" {
+
+int ds_gemm(const ds_gemm_args* a, void* stream) {
+  if (!a) return DS_ERR_ARG;
+  return gemm_dispatch(gemm_args(a), a->act, (hipStream_t)stream, a->M);
 }
 
 int ds_gemm_split(const void* A_split, const float* W_split, const float* bias, float* C, int64_t ldc, int32_t M, int32_t K,

@@ -41,4 +41,8 @@ bool allow_dynamic_lds(std::atomic<uint64_t>& done, Kernel* kernel, size_t bytes
   return true;
 }
 
+// ds_gemm of a->M rows through the tile form that a launch of route_rows >= a->M rows would take (ds_gemm.hip): the rows then carry
+// the bits they have inside that larger launch.  The uniform step prologue runs its one time-MLP row this way.
+int gemm_routed_as(const ds_gemm_args* a, int route_rows, void* stream);
+
 }  // namespace dst

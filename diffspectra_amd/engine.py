@@ -60,6 +60,7 @@ def load_library() -> C.CDLL:
     abi.SCAFFOLD.bind(lib)
     abi.SMILES.bind(lib)
     abi.TILES.bind(lib)
+    abi.STEP.bind(lib)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
     mine = [C.sizeof(t) for t in (DsWeights, DsLayout, DsWorkspace, DsGemmArgs)]
@@ -926,7 +927,9 @@ class DmtEngine:
         return self.spec.encode(context)
 
     def forward(self, L: Layout, ws: Workspace, xh, edge_x, noise_level, cond_x, cond_edge_x, ctx_emb,
-                out_xh=None, out_edge=None):
+                out_xh=None, out_edge=None, uniform_noise_level: bool = False):
+        """``uniform_noise_level``: the caller guarantees that all ``B`` noise levels are equal (a sampler's are: one noise level per
+        step), so the time MLP runs once on ``noise_level[0]`` instead of on ``B`` identical rows (``ds_forward_uniform``); same bits."""
         dev = self.device
         xh, edge_x, noise_level = _f32c(xh, dev), _f32c(edge_x, dev), _f32c(noise_level, dev)
         cond_x = None if cond_x is None else _f32c(cond_x, dev)
@@ -936,16 +939,20 @@ class DmtEngine:
             out_xh = torch.empty(L.B, L.N, 9, dtype=torch.float32, device=dev)
         if out_edge is None:
             out_edge = torch.empty(L.B, L.N, L.N, 2, dtype=torch.float32, device=dev)
-        st = self.lib.ds_forward(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(xh), ptr(edge_x), ptr(cond_x),
-                                 ptr(cond_edge_x), ptr(noise_level), ptr(ctx_emb), ptr(out_xh), ptr(out_edge),
-                                 _stream())
-        _check(st, "ds_forward")
+        entry = self.lib.ds_forward_uniform if uniform_noise_level else self.lib.ds_forward
+        st = entry(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(xh), ptr(edge_x), ptr(cond_x), ptr(cond_edge_x),
+                   ptr(noise_level), ptr(ctx_emb), ptr(out_xh), ptr(out_edge), _stream())
+        _check(st, "ds_forward_uniform" if uniform_noise_level else "ds_forward")
         return out_xh, out_edge
 
     # stage-level calls for the parity tests
     def stage_time(self, L, ws, noise_level, ctx_emb):
         _check(self.lib.ds_stage_time(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(noise_level), ptr(ctx_emb),
                                       _stream()), "ds_stage_time")
+
+    def stage_time_uniform(self, L, ws, noise_level, ctx_emb):
+        _check(self.lib.ds_stage_time_uniform(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(noise_level), ptr(ctx_emb),
+                                              _stream()), "ds_stage_time_uniform")
 
     def stage_init(self, L, ws, xh, edge_x, cond_x, cond_edge_x):
         _check(self.lib.ds_stage_init(C.byref(self.w), C.byref(L.c), C.byref(ws.c), ptr(xh), ptr(edge_x),

@@ -129,7 +129,8 @@ class AncestralSampler:
         prediction is written in place over the self-conditioning input (ds_stage_init has consumed it by then)."""
         eng, L, ws, g = st.eng, st.L, st.ws, st.graph
         eng.step_begin(g["table"], len(st.coef), g["step"], L.B, g["nl"])
-        eng.forward(L, ws, st.x, st.edge_x, g["nl"], g["pred"], g["edge_pred"], st.ctx, g["pred"], g["edge_pred"])
+        eng.forward(L, ws, st.x, st.edge_x, g["nl"], g["pred"], g["edge_pred"], st.ctx, g["pred"], g["edge_pred"],
+                    uniform_noise_level=True)                    # ds_step_begin fills g["nl"] with one value
         eng.sampler_step_philox_dev(L, g["table"], g["step"], float(self.sampling_temperature), st.seed, st.mol_ids, st.x,
                                     st.edge_x, g["pred"], g["edge_pred"], st.x_mean, st.edge_mean)
 
@@ -182,7 +183,8 @@ class AncestralSampler:
         for i in range(st.i, stop_eager):
             c_x, c_pred, sigma, _ = st.coef[i]
             cur = i & 1
-            eng.forward(L, ws, st.x, st.edge_x, st.nl_rows[i], st.cond_x, st.cond_edge_x, st.ctx, st.pred[cur], st.edge_pred[cur])
+            eng.forward(L, ws, st.x, st.edge_x, st.nl_rows[i], st.cond_x, st.cond_edge_x, st.ctx, st.pred[cur], st.edge_pred[cur],
+                        uniform_noise_level=True)                  # nl_rows[i] is one scalar expanded over the batch
             st.cond_x, st.cond_edge_x = st.pred[cur], st.edge_pred[cur]
             if self.cond_process_fn is not None:                   # sampling.py:590 ('ori' identity, 'clamp' in place)
                 st.cond_x, st.cond_edge_x = self.cond_process_fn(st.cond_x, st.cond_edge_x)

@@ -59,6 +59,7 @@ def load_library() -> C.CDLL:
     abi.GROUPS.bind(lib)
     abi.SCAFFOLD.bind(lib)
     abi.SMILES.bind(lib)
+    abi.SUBSTRUCTURE.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
     sizes = (C.c_int64 * 4)()
@@ -874,6 +875,38 @@ def smiles_records(rec: torch.Tensor, n: torch.Tensor, max_nodes: int = 4096):
                         [(torch.uint8, (SMILES_TEXT_BYTES,)), (torch.int32, ()), (torch.uint8, ()), (torch.int32, ()), _MAP], prefix="dsl_")
 
 
+# ----------------------------------------------------------------------------------------- substructure queries
+
+SUBSTRUCTURE_CONSTS = abi.SUBSTRUCTURE.consts       # include/diffspectra_substructure.h
+SUBSTRUCTURE_OK, SUBSTRUCTURE_UNUSABLE = SUBSTRUCTURE_CONSTS["DSQ_OK"], SUBSTRUCTURE_CONSTS["DSQ_UNUSABLE"]
+SUBSTRUCTURE_TRUNCATED, SUBSTRUCTURE_COUNT_CAP = SUBSTRUCTURE_CONSTS["DSQ_TRUNCATED"], SUBSTRUCTURE_CONSTS["DSQ_COUNT_CAP"]
+PATTERN_WORDS, MAX_PATTERNS = SUBSTRUCTURE_CONSTS["DSQ_PATTERN_WORDS"], SUBSTRUCTURE_CONSTS["DSQ_MAX_PATTERNS"]
+SUBSTRUCTURE_MAX_NODES, SUBSTRUCTURE_DEFAULT_NODES = SUBSTRUCTURE_CONSTS["DSQ_MAX_NODES"], SUBSTRUCTURE_CONSTS["DSQ_DEFAULT_NODES"]
+
+
+def substructure_records(rec: torch.Tensor, n: torch.Tensor, patterns: torch.Tensor, max_nodes: int = SUBSTRUCTURE_DEFAULT_NODES):
+    """``dsq_match_records``: every pattern of ``patterns [K, 32] i32`` (``smarts.compile_patterns``; K <= 256, K = 0 is legal) against every
+    record (every definition in ``include/diffspectra_substructure.h``: the hydrogen-folded matched graph, the per-atom properties, the eight
+    bond classes, the defined depth-first search with ``max_nodes`` assignments per start atom, in [1, 2^24]).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(count [P, K] u8, anchors [P, K] i32, cover [P, K] i32, aromatic_mask [P] i32,
+    aromatic_rings [P] i32, fragments [P] i32, status [P] u8)`` on the current stream without synchronising: ``count`` is the number of distinct
+    atom sets over the embeddings, saturating at 4, with bit 7 (``SUBSTRUCTURE_TRUNCATED``) set where a search stopped at its budget; ``anchors``
+    and ``cover`` hold a bit per record atom (the images of pattern atom 0, of any pattern atom); status ``SUBSTRUCTURE_UNUSABLE`` (2: n = 0, a type
+    above 4, a bond byte above 3) zeroes the row.  Checked, never converted; no CPU path."""
+    _want(patterns, "patterns", torch.int32, (None, PATTERN_WORDS))
+    K = patterns.shape[0]
+    if K > MAX_PATTERNS:
+        raise ValueError(f"patterns holds {K} patterns, at most {MAX_PATTERNS} go into one call")
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, int):
+        raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
+    if not 1 <= max_nodes <= SUBSTRUCTURE_MAX_NODES:
+        raise ValueError(f"max_nodes must lie in [1, {SUBSTRUCTURE_MAX_NODES}], got {max_nodes}")
+    i32 = (torch.int32, ())
+    return _record_call("match_records", [(rec, n)], None, [ptr(patterns) if K else None, K, max_nodes],
+                        [(torch.uint8, (K,)), (torch.int32, (K,)), (torch.int32, (K,)), i32, i32, i32, (torch.uint8, ())], prefix="dsq_", also=[patterns])
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -1082,6 +1115,10 @@ class DmtEngine:
     def smiles_records(self, rec, n, max_nodes: int = 4096):
         """``engine.smiles_records`` on this engine's library (the strings need no weights)."""
         return smiles_records(rec, n, max_nodes)
+
+    def substructure_records(self, rec, n, patterns, max_nodes: int = SUBSTRUCTURE_DEFAULT_NODES):
+        """``engine.substructure_records`` on this engine's library (the matcher needs no weights)."""
+        return substructure_records(rec, n, patterns, max_nodes)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

@@ -122,6 +122,22 @@ def _functional_group_summary(run, table, top_k: int) -> Dict:
     return entry
 
 
+def _maccs_summary(run, table, top_k: int, max_nodes: Optional[int] = None) -> Dict:
+    """The reference's "Tanimoto Similarity (MACCS)" line of one finished run (the pairs of ``_structure_summary``); ``max_nodes``: the search
+    budget per start atom, ``None`` for the header's default."""
+    from .structure_metrics import _host_sum, maccs_similarity_batch, topk_maccs
+    dev = run.records_by_slot.device
+    alike = maccs_similarity_batch(run.records_by_slot, torch.tensor(run.n_atoms), table.gt_records.to(dev), table.num_atom, ref_index=run.slot_ds,
+                                   max_nodes=max_nodes, engine=run.eng)
+    ok = alike.valid
+    n_ok = int(ok.sum())
+    entry = dict(tanimoto=alike.tanimoto, status=alike.status, mean=_host_sum(alike.tanimoto[ok]) / n_ok if n_ok else None, scored=n_ok,
+                 truncated=int((alike.truncated & ok).sum()))
+    if top_k > 1:
+        entry["top_k"] = topk_maccs(alike.tanimoto, alike.status, top_k)
+    return entry
+
+
 def _scaffold_summary(run, table, top_k: int, scaffold_fn, min_rings: int) -> Dict:
     """The "Scaf" number of one finished run against the test table (``scaffold_fn``: ``get_scaffold_metric`` of its records) and, over the
     pairs of ``_structure_summary``, whether every generated molecule shares the scaffold of its ground truth."""
@@ -240,6 +256,14 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     topk_groups(...)`` (``structure_metrics.functional_group_similarity_batch``, which states the deviations: the project's own aromaticity
     rule, unpinned against RDKit; every usable pair is scored, with no RDKit filter).  Without the flag the dict has no such key.
 
+    With ``config.eval.maccs`` true ``metrics['structure']['maccs']`` is the reference's "Tanimoto Similarity (MACCS)" (``compute_metrics.py:248-252``;
+    ``dsq_match_records`` with the key table of ``maccs.py``): ``tanimoto`` (f64 device tensor, one per slot: common / either of the 166 keys of
+    the generated molecule and of its ground truth, 1.0 when neither sets a key, NaN for a pair that is not ok), ``status`` (0 ok, 2 a record
+    of the pair is unusable, 3 invalid), ``mean`` over the ok pairs (summed on the host; ``None`` without any), ``scored`` (the ok pairs), ``truncated``
+    (the ok pairs with a search that stopped at its budget - ``config.eval.maccs_max_nodes`` assignments per start atom, the header's
+    default when absent; such keys are a lower bound) and, with K > 1, ``top_k = topk_maccs(...)``.  The key table restates RDKit's as remembered: parity with RDKit is unpinned
+    (``structure_metrics.maccs_similarity_batch``).  Without the flag the dict has no such key.
+
     With ``config.eval.smiles`` true ``metrics['structure']['smiles']`` holds the molecules as text, where the reference calls ``Chem.MolToSmiles``
     (``run_lib.py:111-112``, ``compute_metrics.py:73-78,209-220``; ``dsl_smiles_records``): ``generated`` (one canonical SMILES string per slot,
     ``None`` for an overflow or unusable record), ``ground_truth`` (the string of every slot's ground truth), ``same`` / ``status`` / ``pair_status``
@@ -296,6 +320,8 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
             metrics["structure"] = _structure_summary(run, test_ds, top_k)
             if getattr(config.eval, "functional_groups", False):
                 metrics["structure"]["functional_groups"] = _functional_group_summary(run, test_ds, top_k)
+            if getattr(config.eval, "maccs", False):
+                metrics["structure"]["maccs"] = _maccs_summary(run, test_ds, top_k, getattr(config.eval, "maccs_max_nodes", None))
             if getattr(config.eval, "sub_geometry", False):
                 from .structure_metrics import get_sub_geometry_metric
                 if geometry_fn is None:

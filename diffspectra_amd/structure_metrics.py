@@ -79,6 +79,12 @@ What the molecules are as TEXT is ``smiles`` / ``smiles_strings``: one canonical
 molecules, never as text, with strings from elsewhere); the graph is the constitution-level one of ``graph_identity_batch`` with raw charge
 bytes; Kekule orders only, so two drawings of a ring give one string only where a symmetry maps one onto the other; any SMILES reader reads them.
 
+Whether a molecule contains a substructure, how many times and on which atoms is ``substructure_search`` (``dsq_match_records``,
+``csrc/ds_substructure.hip``; every definition in ``include/diffspectra_substructure.h``): patterns are data, a SMARTS subset compiled by
+``smarts.py``.  On top of it ``maccs_keys`` / ``maccs_similarity_batch`` / ``topk_maccs`` give the 166 MACCS keys and the reference's "Tanimoto
+Similarity (MACCS)" (``compute_metrics.py:248-252``) from the key table of ``maccs.py``, which restates RDKit's as remembered: parity with RDKit
+is unpinned.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -1096,3 +1102,155 @@ def smiles_exact_match(ref, prb, ref_index=None, max_nodes: int = 4096, engine=N
     status = torch.where(inside, torch.maximum(r_status, g.status), torch.full_like(g.status, 3))
     same = (status == 0) & (r_text == g.text).all(dim=1)
     return SmilesMatch(same, status)
+
+
+# ------------------------------------------------------------------------------------------------------------------ substructure queries, MACCS
+
+class SubstructureMatches(NamedTuple):
+    """Per-record device tensors of ``dsq_match_records``; K patterns."""
+    count: torch.Tensor           # [P, K] u8: distinct atom sets over the embeddings (RDKit's uniquified match count), saturating at 4
+    truncated: torch.Tensor       # [P, K] bool: a search stopped at ``max_nodes``; the entry holds what was found before
+    anchors: torch.Tensor         # [P, K] i32: bit i = record atom i takes pattern atom 0 in some embedding
+    cover: torch.Tensor           # [P, K] i32: bit i = record atom i takes part in some embedding
+    aromatic_mask: torch.Tensor   # [P] i32: bit i = atom i is aromatic (the project's rule; unpinned against RDKit)
+    aromatic_rings: torch.Tensor  # [P] i32: distinct aromatic cycles (atom sets), saturating at 4
+    fragments: torch.Tensor       # [P] i32: connected components
+    status: torch.Tensor          # [P] u8: 0 ok, 2 unusable (n = 0, a type above 4, a bond byte above 3): the row is 0
+
+    def has(self, i: int) -> torch.Tensor:
+        """``[P] bool``: the record contains pattern ``i`` (False for an unusable record)."""
+        return self.count[:, i] > 0
+
+
+class MaccsKeys(NamedTuple):
+    """What ``maccs_keys`` returns."""
+    bits: torch.Tensor            # [P, 167] bool: column k = MACCS key k; column 0 is unused and False; an unusable row is all False
+    status: torch.Tensor          # [P] u8: 0 ok, 2 unusable
+    truncated: torch.Tensor       # [P] bool: some pattern's search stopped at the budget (the keys are then a lower bound)
+
+
+class MaccsSimilarity(NamedTuple):
+    """Per-pair tensors of ``maccs_similarity_batch``."""
+    common: torch.Tensor          # [P] i32: keys both molecules set; -1 for a pair that is not ok
+    either: torch.Tensor          # [P] i32: keys at least one of them sets; -1 for a pair that is not ok
+    tanimoto: torch.Tensor        # [P] f64: common / either, 1.0 when either = 0, NaN for a pair that is not ok
+    status: torch.Tensor          # [P] u8: 0 ok, 2 a record of the pair is unusable, 3 invalid row
+    truncated: torch.Tensor       # [P] bool: a search of either molecule stopped at the budget (its keys are a lower bound); False for an invalid row
+
+    @property
+    def valid(self) -> torch.Tensor:
+        return self.status == 0
+
+
+def _pattern_tensor(patterns, device) -> torch.Tensor:
+    """``[K, 32] i32`` on ``device`` from pattern texts (compiled by ``smarts.compile_patterns``), a numpy array or a tensor of compiled rows."""
+    from . import smarts
+    if isinstance(patterns, str):
+        patterns = [patterns]
+    if torch.is_tensor(patterns):
+        out = patterns
+    elif hasattr(patterns, "dtype"):
+        out = torch.from_numpy(patterns)
+    else:
+        out = torch.from_numpy(smarts.compile_patterns(list(patterns)))
+    if out.dtype != torch.int32 or out.dim() != 2 or out.shape[1] != smarts.WORDS:
+        raise ValueError(f"compiled patterns are int32 [K, {smarts.WORDS}], got {out.dtype} {list(out.shape)}")
+    return out.to(device).contiguous()
+
+
+def substructure_search(records: torch.Tensor, n_atoms, patterns, max_nodes: Optional[int] = None, engine=None) -> SubstructureMatches:
+    """Every pattern against every record of ``records [P, 1248] u8`` (GPU) in one launch of ``dsq_match_records`` (``csrc/ds_substructure.hip``;
+    every definition in ``include/diffspectra_substructure.h``).  ``patterns``: texts of the SMARTS subset of ``smarts.py``, or rows already
+    compiled by it (``int32 [K, 32]``); at most 256 per call.  ``max_nodes``: the assignments one start atom's search may make (``None``:
+    ``DSQ_DEFAULT_NODES``).  Matching runs on the hydrogen-folded graph with the project's aromaticity rule, unpinned against RDKit.  Device
+    tensors, no synchronisation."""
+    from . import engine as E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    words = _pattern_tensor(patterns, records.device)
+    budget = E.SUBSTRUCTURE_DEFAULT_NODES if max_nodes is None else max_nodes
+    count, anchors, cover, aromatic, rings, fragments, status = (engine if engine is not None else E).substructure_records(records, n, words, budget)
+    flag = E.SUBSTRUCTURE_TRUNCATED
+    return SubstructureMatches(torch.bitwise_and(count, flag - 1), torch.bitwise_and(count, flag) != 0, anchors, cover, aromatic, rings, fragments, status)
+
+
+_MACCS_TABLE = None
+
+
+def _maccs_table():
+    """The compiled MACCS patterns and how the keys read them, built once."""
+    global _MACCS_TABLE
+    if _MACCS_TABLE is None:
+        from . import maccs, smarts
+        texts, single, anchored = maccs.pattern_table()
+        _MACCS_TABLE = (torch.from_numpy(smarts.compile_patterns(texts)), single, anchored)
+    return _MACCS_TABLE
+
+
+def _popcount29(x: torch.Tensor) -> torch.Tensor:
+    """Set bits of atom masks (bits 0..28) as i64, by plain tensor ops."""
+    shifts = torch.arange(29, device=x.device, dtype=torch.int32)
+    return torch.bitwise_and(torch.bitwise_right_shift(x.to(torch.int32).unsqueeze(-1), shifts), 1).sum(dim=-1)
+
+
+def maccs_keys(records: torch.Tensor, n_atoms, max_nodes: Optional[int] = None, engine=None) -> MaccsKeys:
+    """The 166 MACCS keys of every record of ``records [P, 1248] u8`` (GPU): one ``substructure_search`` with the table of ``maccs.py`` and plain
+    tensor ops on its outputs.  Key k is column k of ``bits [P, 167]`` (column 0 unused), set iff the key's matches exceed its threshold: the
+    uniquified match count of a single pattern, the number of anchor atoms of a key that RDKit writes as one recursive atom, ``aromatic_rings >
+    1`` for key 125 and ``fragments > 1`` for key 166.  The table restates RDKit's ``MACCSkeys.smartsPatts`` as remembered: parity with RDKit is
+    UNPINNED (``maccs.py`` lists the deviations).  Device tensors, no synchronisation."""
+    from . import maccs
+    words, single, anchored = _maccs_table()
+    found = substructure_search(records, n_atoms, words, max_nodes=max_nodes, engine=engine)
+    dev = found.count.device
+    bits = torch.zeros(found.count.shape[0], maccs.NUM_KEYS + 1, dtype=torch.bool, device=dev)
+    keys = torch.tensor([k for k, _, _ in single], dtype=torch.int64, device=dev)
+    cols = torch.tensor([c for _, c, _ in single], dtype=torch.int64, device=dev)
+    more = torch.tensor([t for _, _, t in single], dtype=torch.int32, device=dev)
+    bits[:, keys] = found.count[:, cols].to(torch.int32) > more.unsqueeze(0)
+    for key, columns, threshold in anchored:
+        atoms = found.anchors[:, columns[0]]
+        for c in columns[1:]:
+            atoms = torch.bitwise_or(atoms, found.anchors[:, c])
+        bits[:, key] = _popcount29(atoms) > threshold
+    bits[:, 125] = found.aromatic_rings > 1
+    bits[:, 166] = found.fragments > 1
+    return MaccsKeys(bits, found.status, found.truncated.any(dim=1))
+
+
+def maccs_similarity_batch(prb, prb_n, ref, ref_n, ref_index=None, max_nodes: Optional[int] = None, engine=None) -> MaccsSimilarity:
+    """The reference's "Tanimoto Similarity (MACCS)" (``compute_metrics.py:248-252``) of every generated record ``prb [P, 1248] u8`` and its ground
+    truth among ``ref [M, 1248] u8`` (both on the GPU; ``ref_index [P]`` names the row, ``None``: row p for pair p - the record-pairs contract):
+    ``maccs_keys`` once per table, then tensor ops.  ``tanimoto`` = common / either as f64, 1.0 when neither molecule sets a key (the
+    convention of the functional-group line); a row outside the table is invalid (status 3) and reads nothing; a pair with an unusable record
+    has status 2.  Parity with RDKit's MACCS keys is UNPINNED (``maccs.py``).  Device tensors, no synchronisation."""
+    mine, theirs = maccs_keys(prb, prb_n, max_nodes=max_nodes, engine=engine), maccs_keys(ref, ref_n, max_nodes=max_nodes, engine=engine)
+    dev = mine.bits.device
+    P, M = mine.bits.shape[0], theirs.bits.shape[0]
+    if ref_index is None and M < P:
+        raise ValueError(f"without ref_index pair p reads ground-truth row p: {M} rows for {P} pairs")
+    idx = torch.arange(P, device=dev) if ref_index is None else torch.as_tensor(ref_index).to(device=dev, dtype=torch.int64).reshape(-1)
+    if idx.numel() != P:
+        raise ValueError(f"ref_index must name one ground-truth row per pair: {idx.numel()} for {P}")
+    inside = (idx >= 0) & (idx < M)
+    row = torch.where(inside, idx, torch.zeros_like(idx))
+    if M:
+        r_bits, r_status, r_cut = theirs.bits.to(dev)[row], theirs.status.to(dev)[row], theirs.truncated.to(dev)[row]
+    else:
+        r_bits, r_status, r_cut = torch.zeros_like(mine.bits), torch.zeros_like(mine.status), torch.zeros_like(mine.truncated)
+    status = torch.where(inside, torch.maximum(mine.status, r_status), torch.full_like(mine.status, 3))
+    ok = status == 0
+    minus = torch.full((P,), -1, dtype=torch.int32, device=dev)
+    common = torch.where(ok, (mine.bits & r_bits).sum(dim=1).to(torch.int32), minus)
+    either = torch.where(ok, (mine.bits | r_bits).sum(dim=1).to(torch.int32), minus)
+    c, u = common.double(), either.double()
+    sim = torch.where(either == 0, torch.ones_like(c), c / torch.where(either == 0, torch.ones_like(u), u))
+    return MaccsSimilarity(common, either, torch.where(ok, sim, torch.full_like(sim, float("nan"))), status, inside & (mine.truncated | r_cut))
+
+
+def topk_maccs(tanimoto: torch.Tensor, status: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:
+    """Best-of-K reductions of ``maccs_similarity_batch`` over the K consecutive candidates of every spectrum, shaped like ``topk_morgan``: ``best
+    [S] f64`` (the largest similarity among the ok candidates, NaN when none of the K is ok), ``best_index [S] i64`` (the first candidate with it,
+    -1 when none is ok) and ``mean_best`` (a 0-dim f64 tensor; NaN without any).  Plain torch reductions on the tensors' device."""
+    if top_k < 1 or tanimoto.numel() % top_k or status.shape != tanimoto.shape:
+        raise ValueError(f"{tanimoto.numel()} pairs (status: {status.numel()}) are not a whole number of top_k = {top_k} groups")
+    return topk_morgan(torch.where(status == 0, tanimoto.to(torch.float64), torch.full_like(tanimoto, float("nan"), dtype=torch.float64)), top_k)

@@ -7,24 +7,18 @@
 // inside the cycle, the count with it outside, the partner).  A lane's ring-bond test and cycle search read other atoms' words inside divergent
 // loops, so they read LDS and never shuffle; the wave-wide masks (elements, X, Ht, aromatic atoms, group bits) are ballots and one OR
 // reduction outside divergent code.  Integers only, no atomics, no early exit: a wave without a record takes part in the workgroup's
-// barriers and writes nothing.
+// barriers and writes nothing.  From ds_perceive.h: the record scan, applied_charge and max_valence, the electron rule with ring_bond for the
+// double bond, the walk over the cycles each atom is the lowest of, the wave OR.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/diffspectra_groups.h"
-#include "ds_bonds.h"
-#include "ds_records.h"
+#include "ds_perceive.h"
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-using ds_rec::MA;
-using ds_rec::uniform_i;
-constexpr unsigned ALL = ~0u;             // keep mask of ds_rec::load_bonds: every atom (the rows below are read up to n only)
-constexpr int MAX_ORDER = 3, MAX_TYPE = 4;
-constexpr int H = 0, C = 1, N = 2, O = 3, F = 4;
-constexpr unsigned NONE = 3u;             // electron code of "no candidate"; the counts are 0, 1, 2
-constexpr int NO_PARTNER = 31;            // a bit no member mask holds: an atom without a double bond reads its "outside" count, which equals the other
+using namespace ds_perceive;
 
 struct Wave {                             // one record's staging area
   unsigned char adj[MA * 32];             // symmetric bond orders over original atom indices, diagonal 0
@@ -37,136 +31,44 @@ struct Found {                            // wave-uniform
   bool usable;
 };
 
-__device__ __forceinline__ unsigned low32(unsigned long long ballot) { return (unsigned)ballot; }   // atoms live in lanes 0..28
-
-// Is the cycle with the member mask `members` aromatic: every member a candidate for it, six electrons in all.
-__device__ __forceinline__ bool six_electrons(const Wave& S, unsigned members) {
-  unsigned sum = 0u;
-  bool all = true;
-  for (unsigned m = members; m; m &= m - 1u) {                                   // 5 or 6 members
-    const unsigned w = S.electrons[__ffs((int)m) - 1];
-    const unsigned e = ((members >> (w >> 4)) & 1u) ? (w & 3u) : ((w >> 2) & 3u);
-    all &= e != NONE;
-    sum += e;
-  }
-  return all && sum == 6u;
-}
-
 // Groups and aromatic atoms of record `mine` (not touched when n = 0: a wave without a record, or with an invalid pair, passes n = 0).  Holds
 // three workgroup barriers, which every wave of the workgroup reaches: nothing in here returns early.
 __device__ __forceinline__ Found analyse(Wave& S, const unsigned char* __restrict__ mine, int n, int lane) {
-  const bool active = lane < n;
-  int type = 0, raw = 0;
-  if (active) {
-    type = mine[DS_REC_TYPE + lane];
-    raw = (int)(signed char)mine[DS_REC_FC + lane];
-  }
-  bool bad = type > MAX_TYPE;
-  const int t = min(type, MAX_TYPE);      // a table index whatever the byte; a type above 4 makes the record unusable
-  if (n > 0) ds_rec::load_bonds(S.adj, mine, ALL, lane);
-  __syncthreads();
-  int val = 0;
-  unsigned nb = 0u, nb1 = 0u, nb2 = 0u, nb3 = 0u;
-  if (active)
-    for (int j = 0; j < n; ++j) {
-      const unsigned b = S.adj[lane * 32 + j];
-      bad |= b > (unsigned)MAX_ORDER;
-      val += (int)b;
-      nb |= (b ? 1u : 0u) << j;
-      nb1 |= (b == 1u ? 1u : 0u) << j;
-      nb2 |= (b == 2u ? 1u : 0u) << j;
-      nb3 |= (b == 3u ? 1u : 0u) << j;
-    }
-  const bool usable = n > 0 && __ballot(active && bad) == 0ull;
-  const bool on = usable && active;
-  if (!on) nb = nb1 = nb2 = nb3 = 0u;     // an unusable record has no atoms from here on: every mask is 0 and every loop below is empty
+  const Atom A = scan(S.adj, mine, n, lane, ds_refine::Block{});
+  const bool usable = usable_record(A, n), on = usable && A.active;
+  const int t = min(A.type, MAX_TYPE);    // a table index whatever the byte; a type above 4 makes the record unusable
+  // an unusable record has no atoms from here on: every mask is 0 and every loop below is empty
+  const unsigned nb = on ? A.nb : 0u, nb1 = on ? A.nb1 : 0u, nb2 = on ? A.nb2 : 0u, nb3 = on ? A.nb3 : 0u;
+  const unsigned me = lane < 32 ? 1u << lane : 0u;
 
   const unsigned isH = low32(__ballot(on && t == H)), isC = low32(__ballot(on && t == C)), isN = low32(__ballot(on && t == N)),
                  isO = low32(__ballot(on && t == O)), isF = low32(__ballot(on && t == F));
-  const int q = ((t == C || t == N) && (raw == 1 || raw == -1)) || (t == O && raw == -1) ? raw : 0;       // N+1, N-1, C+1, O-1, C-1
-  const int vmax = ds_bonds::c_valence[t] + (t == C ? -abs(q) : (t == N || t == O) ? q : 0);
-  const int hi = max(0, vmax - val);
+  const int q = applied_charge(t, A.raw);
+  const int hi = max(0, max_valence(t, q) - A.val);
   const int D = __popc(nb), dbl = __popc(nb2), trp = __popc(nb3);
   const int X = D + hi, Ht = __popc(nb & isH) + hi;
 
-  // the electron word: the counts that do not depend on the cycle now, the ring-bond flag of the double bond below
-  unsigned e_in = NONE, e_out = NONE;
-  int partner = NO_PARTNER;
-  bool wants_ring = false;
-  if (on && trp == 0 && dbl <= 1 && X <= 3) {
-    if (dbl == 1) {
-      if ((t == C && X == 3 && q == 0) || (t == N && ((X == 2 && q == 0) || (X == 3 && q == 1)))) {
-        e_in = 1u;
-        partner = __ffs((int)nb2) - 1;
-        wants_ring = true;
-      }
-    } else if (t == C) {
-      if (X == 3 && q == -1) e_in = e_out = 2u;
-      else if (X == 3 && q == 1) e_in = e_out = 0u;
-    } else if (t == N) {
-      if ((X == 3 && q == 0) || (X == 2 && q == -1)) e_in = e_out = 2u;
-    } else if (t == O) {
-      if (X == 2 && q == 0) e_in = e_out = 2u;
-    }
-  }
+  // the electron word: the counts that do not depend on the cycle now, the ring-bond test of the double bond below
+  Electrons e = electron_rule(on, t, q, X, dbl, trp, nb2);
   if (lane < 32) {
     S.any[lane] = nb;
     S.one[lane] = nb1;
   }
   __syncthreads();
-  if (wants_ring) {                       // the atoms reached from this one without its double bond: every atom is expanded once, the partner never
-    const unsigned goal = 1u << partner;
-    unsigned todo = nb & ~goal, reached = (1u << lane) | todo;
-    while (todo && !(reached & goal)) {
-      const int j = __ffs((int)todo) - 1;
-      todo &= todo - 1u;
-      const unsigned fresh = S.any[j] & ~reached;
-      reached |= fresh;
-      todo |= fresh;
-    }
-    e_out = (reached & goal) ? 1u : (((isN | isO) >> partner) & 1u) ? 0u : NONE;
-  }
-  if (lane < 32) S.electrons[lane] = e_in | (e_out << 2) | ((unsigned)partner << 4);
+  if (e.partner != NO_PARTNER) e.e_out = double_bond_outside(ring_bond(S.any, me, nb, 1u << e.partner), e.partner, isN | isO);
+  if (lane < 32) S.electrons[lane] = e.word();
   __syncthreads();
-  const unsigned candidates = low32(__ballot(e_in != NONE));
+  const unsigned candidates = low32(__ballot(e.e_in != NONE));
 
-  // cycles of 5 and 6 atoms with this lane's atom as their lowest: candidates have at most three neighbours, so 3 * 2 * 2 * 2 * 2 partial paths
-  // at the most; a cycle is met in both directions and taken in the one whose last atom is above its second
-  unsigned aromatic = 0u;
-  if (e_in != NONE) {
-    const unsigned me = 1u << lane, above = candidates & ~((me << 1) - 1u);
-    for (unsigned c1 = nb & above; c1; c1 &= c1 - 1u) {
-      const int a1 = __ffs((int)c1) - 1;
-      const unsigned m1 = me | (1u << a1);
-      for (unsigned c2 = S.any[a1] & above & ~m1; c2; c2 &= c2 - 1u) {
-        const int a2 = __ffs((int)c2) - 1;
-        const unsigned m2 = m1 | (1u << a2);
-        for (unsigned c3 = S.any[a2] & above & ~m2; c3; c3 &= c3 - 1u) {
-          const int a3 = __ffs((int)c3) - 1;
-          const unsigned m3 = m2 | (1u << a3);
-          for (unsigned c4 = S.any[a3] & above & ~m3; c4; c4 &= c4 - 1u) {
-            const int a4 = __ffs((int)c4) - 1;
-            const unsigned m4 = m3 | (1u << a4), n4 = S.any[a4];
-            if ((n4 & me) && a4 > a1 && six_electrons(S, m4)) aromatic |= m4;
-            for (unsigned c5 = n4 & above & ~m4; c5; c5 &= c5 - 1u) {
-              const int a5 = __ffs((int)c5) - 1;
-              const unsigned m5 = m4 | (1u << a5);
-              if ((S.any[a5] & me) && a5 > a1 && six_electrons(S, m5)) aromatic |= m5;
-            }
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) aromatic |= (unsigned)__shfl_xor((int)aromatic, o, 64);
-  aromatic = (unsigned)uniform_i((int)aromatic);
+  unsigned found = 0u;
+  if (e.e_in != NONE)
+    aromatic_cycles<true>(S.any, S.electrons, me, nb, candidates, [&](unsigned members, int, int) { found |= members; });
+  const unsigned aromatic = wave_or(found);
 
   // the predicates: "al" = not aromatic; wave-wide masks of what a neighbour has to be, then a test per lane and a ballot per group
   const unsigned alC = isC & ~aromatic, alO = isO & ~aromatic;
   const unsigned X1 = low32(__ballot(on && X == 1)), X2 = low32(__ballot(on && X == 2)), X3 = low32(__ballot(on && X == 3));
   const unsigned Ht0 = low32(__ballot(on && Ht == 0)), Ht1 = low32(__ballot(on && Ht == 1));
-  const unsigned me = lane < 32 ? 1u << lane : 0u;
   const bool al = on && !(aromatic & me);
   const bool sp2 = al && t == C && X == 3, carbonyl = (nb2 & alO) != 0u;
   const unsigned carbons = nb1 & isC;                                            // single-bonded C#
@@ -241,7 +143,7 @@ __global__ __launch_bounds__(64 * DSG_WAVES) void k_group_pairs(const unsigned c
 }
 
 static_assert(DSG_WAVES >= 1 && 64 * DSG_WAVES <= 1024, "a workgroup of whole waves");
-static_assert(MA <= 29 && DSG_NUM_GROUPS == 17, "atom masks and partner indices fit the electron word; bits 15 and 16 stay clear");
+static_assert(DSG_NUM_GROUPS == 17, "bits 15 and 16 of the group word stay clear");
 
 }  // namespace
 

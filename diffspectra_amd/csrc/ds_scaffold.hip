@@ -6,27 +6,23 @@
 // One wave64 per record, DSK_WAVES records per workgroup, an atom per lane.  LDS holds, per wave, the bond matrix of ds_rec::load_bonds and one
 // word per atom: its neighbours inside the core.  The pruning and the component growth are wave-wide (ballots, shuffles) and run outside
 // divergent code; a lane's ring-bond tests read other atoms' words inside divergent loops, so they read LDS and never shuffle.  Integers
-// only, no atomics, no early exit: a wave without a record takes part in the workgroup's barriers and writes nothing.
+// only, no atomics, no early exit: a wave without a record takes part in the workgroup's barriers and writes nothing.  From ds_perceive.h: the
+// record scan, reach for the ring test over the core, the component doubling, the wave sum.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/diffspectra_scaffold.h"
-#include "ds_records.h"
+#include "ds_perceive.h"
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-using ds_rec::MA;
-using ds_rec::uniform_i;
-constexpr unsigned ALL = ~0u;             // keep mask of ds_rec::load_bonds: every atom (the rows below are read up to n only)
-constexpr int MAX_ORDER = 3, MAX_TYPE = 4;
+using namespace ds_perceive;
 
 struct Wave {                             // one record's staging area
   unsigned char adj[MA * 32];             // symmetric bond orders over original atom indices, diagonal 0
   unsigned core[32];                      // bit j = atom j is a core neighbour of this core atom; 0 for an atom outside the core
 };
-
-__device__ __forceinline__ unsigned low32(unsigned long long ballot) { return (unsigned)ballot; }   // atoms live in lanes 0..28
 
 __global__ __launch_bounds__(64 * DSK_WAVES) void k_scaffold(const unsigned char* __restrict__ rec, const int32_t* __restrict__ n_atoms, int64_t P,
                                                              int32_t* __restrict__ scaffold_mask, int32_t* __restrict__ ring_mask,
@@ -38,27 +34,13 @@ __global__ __launch_bounds__(64 * DSK_WAVES) void k_scaffold(const unsigned char
   const int n = live ? ds_rec::atoms_of(n_atoms, p) : 0;            // a wave without a record passes n = 0 and touches no record
   const unsigned char* __restrict__ mine = rec + (live ? p : 0) * DS_RECORD_BYTES;
   Wave& W = S[wave];
-  const bool active = lane < n;
   const unsigned me = lane < 32 ? 1u << lane : 0u;
-
-  int type = 0;
-  if (active) type = mine[DS_REC_TYPE + lane];
-  bool bad = type > MAX_TYPE;
-  if (n > 0) ds_rec::load_bonds(W.adj, mine, ALL, lane);
-  __syncthreads();
-  unsigned nb = 0u, nb_multiple = 0u;                                // bonded by any order / by order >= 2
-  if (active)
-    for (int j = 0; j < n; ++j) {
-      const unsigned b = W.adj[lane * 32 + j];
-      bad |= b > (unsigned)MAX_ORDER;
-      nb |= (b ? 1u : 0u) << j;
-      nb_multiple |= (b >= 2u ? 1u : 0u) << j;
-    }
-  const bool usable = n > 0 && __ballot(active && bad) == 0ull;
-  const bool on = usable && active;
+  const Atom A = scan(W.adj, mine, n, lane, ds_refine::Block{});
+  const bool usable = usable_record(A, n), on = usable && A.active;
+  const unsigned nb = A.nb, nb_multiple = A.nb2 | A.nb3;             // bonded by any order / by order >= 2
 
   // the heavy graph: hydrogens and all their bonds go first
-  const unsigned heavy = low32(__ballot(on && type != 0));
+  const unsigned heavy = low32(__ballot(on && A.type != H));
   const unsigned hnb = (heavy & me) ? nb & heavy : 0u;
 
   // the 2-core: a round deletes every atom with at most one neighbour left; at most n rounds kill somebody
@@ -83,37 +65,16 @@ __global__ __launch_bounds__(64 * DSK_WAVES) void k_scaffold(const unsigned char
   bool ring_atom = false;
   for (unsigned far = cnb; far && !ring_atom; far &= far - 1u) {
     const int b = __ffs((int)far) - 1;
-    unsigned reached = 1u << b, todo = (W.core[b] & ~me) & ~reached;   // b expanded here, without its bond to me
-    reached |= todo;
-    while (todo && !(reached & me)) {
-      const int j = __ffs((int)todo) - 1;
-      todo &= todo - 1u;
-      const unsigned fresh = W.core[j] & ~reached;
-      reached |= fresh;
-      todo |= fresh & ~me;
-    }
-    ring_atom = (reached & me) != 0u;
+    const unsigned first = W.core[b] & ~me & ~(1u << b);             // b expanded here, without its bond to me
+    ring_atom = (reach(W.core, (1u << b) | first, first, me) & me) != 0u;
   }
   const unsigned ring_atoms = low32(__ballot(ring_atom));
 
   // components of the core: comp = the core atoms known to be connected to this one; a round ORs in what they know, so the reach doubles
-  unsigned comp = in_core ? (cnb | me) : 0u;
-  for (int reach = 1; reach < n; reach <<= 1) {
-    unsigned next = comp;
-    for (int j = 0; j < n; ++j) {
-      const unsigned cj = (unsigned)__shfl((int)comp, j, 64);
-      if ((comp >> j) & 1u) next |= cj;
-    }
-    const bool grew = __ballot(next != comp) != 0ull;
-    comp = next;
-    if (!grew) break;
-  }
-  const int components = __popcll(__ballot(in_core && __ffs((int)comp) - 1 == lane));
-  int ends = __popc(cnb);                                             // both ends of every core bond
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ends += __shfl_xor(ends, o, 64);
-  ends = uniform_i(ends);
-  const int rings = ends / 2 - __popc(core) + components;
+  const unsigned comp = components(in_core ? (cnb | me) : 0u, n);
+  const int parts = __popcll(__ballot(in_core && __ffs((int)comp) - 1 == lane));
+  const int ends = wave_sum(__popc(cnb));                             // both ends of every core bond
+  const int rings = ends / 2 - __popc(core) + parts;
 
   if (live) {
     const unsigned scaffold = core | exocyclic;
@@ -130,7 +91,6 @@ __global__ __launch_bounds__(64 * DSK_WAVES) void k_scaffold(const unsigned char
 }
 
 static_assert(DSK_WAVES >= 1 && 64 * DSK_WAVES <= 1024, "a workgroup of whole waves");
-static_assert(MA <= 29, "an atom mask fits a 32-bit word with lanes 29..31 clear");
 
 }  // namespace
 

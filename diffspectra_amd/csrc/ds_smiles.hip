@@ -6,22 +6,19 @@
 // Every wave works on its own LDS area and its loops have their own trip counts, so there is no workgroup barrier anywhere: the lanes of a
 // wave are ordered by ds_refine::Wave, and a wave without a record leaves at once.  The refinement is the single-molecule form of
 // ds_refine.h; the search is the iteration of k_graph_identity with one molecule: a stack of colourings in LDS, a cursor and the tried atoms
-// per level.  The walk over the canonical graph and the emission run in lane 0.  Integers only, no atomics.
+// per level.  The walk over the canonical graph and the emission run in lane 0.  Integers only, no atomics.  From ds_perceive.h: the record
+// scan (with the wave barrier), the plain-hydrogen fold test, the wave minimum.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/diffspectra_smiles.h"
-#include "ds_records.h"
-#include "ds_refine.h"
+#include "ds_perceive.h"
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-using ds_rec::MA;
-using ds_rec::uniform_i;
+using namespace ds_perceive;
 using ds_refine::DISCRETE;
-constexpr unsigned ALL = ~0u;             // keep mask of ds_rec::load_bonds: every atom (rows are read up to n only)
-constexpr int MAX_ORDER = 3, MAX_TYPE = 4;
 constexpr int TOKEN = 12;                 // an atom's text is at most "[" X "H" dd sign ddd "]" = 10 bytes
 constexpr int TEXT_WORDS = DSL_TEXT_BYTES / 4;
 constexpr unsigned short FREE = 0xffffu, PENDING = 0xfffeu;
@@ -43,8 +40,6 @@ struct Mol {                              // one record's staging area
   unsigned text[TEXT_WORDS];
   __device__ __forceinline__ const unsigned char* bonds(int) const { return adj; }
 };
-
-__device__ __forceinline__ unsigned low32(unsigned long long ballot) { return (unsigned)ballot; }   // atoms live in lanes 0..28
 
 // The walk and the emission, by one lane: m written atoms in canonical positions with the bond bytes canon[p * 32 + q].  Leaves W.vis (the
 // visit index of every position) and the text; returns its length, or -1 when more than DSL_MAX_RINGS numbers would be open at once.  Every
@@ -160,30 +155,20 @@ __global__ __launch_bounds__(64 * DSL_WAVES) void k_smiles(const unsigned char* 
   const int n = uniform_i(ds_rec::atoms_of(n_atoms, p));
   const unsigned char* __restrict__ mine = rec + p * DS_RECORD_BYTES;
   Mol& W = S[wave];
-  const bool active = lane < n;
   const unsigned me = lane < 32 ? 1u << lane : 0u;
 
-  int type = 0, fc = 0;
-  if (active) { type = mine[DS_REC_TYPE + lane]; fc = mine[DS_REC_FC + lane]; }
-  bool bad = type > MAX_TYPE;
   for (int w = lane; w < TEXT_WORDS; w += 64) W.text[w] = 0u;
-  if (n > 0) ds_rec::load_bonds(W.adj, mine, ALL, lane);
-  sync();
-  unsigned nb = 0u;                                                  // bonded by any order
-  if (active)
-    for (int j = 0; j < n; ++j) {
-      const unsigned b = W.adj[lane * 32 + j];
-      bad |= b > (unsigned)MAX_ORDER;
-      nb |= (b ? 1u : 0u) << j;
-    }
-  const bool usable = n > 0 && __ballot(active && bad) == 0ull;
+  const Atom A = scan(W.adj, mine, n, lane, sync);
+  const bool active = A.active, usable = usable_record(A, n);
+  const int type = A.type, fc = A.raw & 0xff;                        // the charge byte as the label key holds it
+  const unsigned nb = A.nb;                                          // bonded by any order
 
   int out_length = 0, out_status = DSL_UNUSABLE, used = 0, place = -1;
   if (usable) {
     // the written graph: fold the plain hydrogens into their neighbours, by ballots
-    const unsigned hydrogens = low32(__ballot(active && type == 0));
+    const unsigned hydrogens = low32(__ballot(active && type == H));
     const int only = nb ? __ffs((int)nb) - 1 : 0;
-    const bool fold = active && type == 0 && fc == 0 && __popc(nb) == 1 && W.adj[lane * 32 + only] == 1 && (nb & ~hydrogens) != 0u;
+    const bool fold = plain_hydrogen(active, type, A.raw, nb, hydrogens) && W.adj[lane * 32 + only] == 1;
     const unsigned folded = low32(__ballot(fold));
     const unsigned written = low32(__ballot(active)) & ~folded;
     const bool on = (written & me) != 0u;
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(64 * DSL_WAVES) void k_smiles(const unsigned char* 
 
     // the atom's text
     if (on) {
-      const int charge = (int)(signed char)fc;
+      const int charge = A.raw;
       const int implied = type == 1 ? (sum <= 4 ? 4 - sum : 0) : type == 2 ? (sum <= 3 ? 3 - sum : sum <= 5 ? 5 - sum : 0)
                         : type == 3 ? (sum <= 2 ? 2 - sum : 0) : type == 4 ? (sum <= 1 ? 1 - sum : 0) : 0;
       const unsigned char sym = type == 0 ? 'H' : type == 1 ? 'C' : type == 2 ? 'N' : type == 3 ? 'O' : 'F';
@@ -263,10 +248,7 @@ __global__ __launch_bounds__(64 * DSL_WAVES) void k_smiles(const unsigned char* 
       } else {
         if (depth >= MA) break;                                      // (cannot happen: every level makes one more atom a cell of its own)
         // open a level on the lowest cell with several atoms
-        int c = (on && ((multi >> lane) & 1ull)) ? colour : 64;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c = min(c, __shfl_xor(c, o, 64));
-        c = uniform_i(c);
+        const int c = (int)wave_min((on && ((multi >> lane) & 1ull)) ? (unsigned)colour : 64u);
         if (lane < 32) W.stack[depth][lane] = (unsigned char)colour;
         if (lane == 0) { W.cell[depth] = c; W.cursor[depth] = 0; W.tried[depth] = 0u; }
         sync();
@@ -342,7 +324,6 @@ __global__ __launch_bounds__(64 * DSL_WAVES) void k_smiles(const unsigned char* 
 }
 
 static_assert(DSL_WAVES >= 1 && 64 * DSL_WAVES <= 1024, "a workgroup of whole waves");
-static_assert(MA <= 29, "an atom mask fits a 32-bit word with lanes 29..31 clear");
 static_assert(DSL_TEXT_BYTES % 4 == 0, "the text leaves as whole dwords");
 static_assert(MA * 32 <= (int)sizeof(((Mol*)nullptr)->stack), "the canonical bond bytes fit the search stack");
 

@@ -3,10 +3,11 @@
 // include/diffspectra_substructure.h states every definition (the matched graph, the per-atom properties, the eight bond classes, the pattern
 // words, the search order and its node count); DESIGN.md section 20 has the figures.
 //
-// One wave64 per record, DSQ_WAVES per workgroup, an atom per lane.  The prologue runs once per record and restates the perception of
-// ds_groups.hip with two additions: a lane walks the cycles through its OWN atom (not only those it is the lowest atom of), so that it learns
-// its aromatic-bond neighbours without a scatter, and it keeps the distinct atom sets of the cycles it is the lowest atom of.  LDS holds, per
-// wave, the bond matrix, the neighbour masks of the perception, the eight class masks of every atom, the pattern in flight with one ballot per
+// One wave64 per record, DSQ_WAVES per workgroup, an atom per lane.  The prologue runs once per record on the perception of ds_perceive.h (the
+// record scan, applied_charge and max_valence, the fold test, ring_bond for every bond, reach for the fragments, the electron rule, the wave
+// reductions), with the cycle walk in its other form: a lane walks the cycles through its OWN atom (not only those it is the lowest atom of),
+// so that it learns its aromatic-bond neighbours without a scatter, and it keeps the distinct atom sets of the cycles it is the lowest atom
+// of.  LDS holds, per wave, the bond matrix, the neighbour masks of the perception, the eight class masks of every atom, the pattern in flight with one ballot per
 // pattern atom, and the lanes' search stacks (candidate mask and image per depth) at [depth * 32 + lane]: lanes 0..28 of one depth row sit on
 // 29 different banks, and a dynamically indexed register array would go to scratch.  The waves of a workgroup walk the K patterns together
 // (workgroup barriers around the staging of a pattern); the searches between two barriers diverge freely.  Integers only, no atomics, no
@@ -15,19 +16,12 @@
 #include <stdint.h>
 
 #include "../../include/diffspectra_substructure.h"
-#include "ds_bonds.h"
-#include "ds_records.h"
+#include "ds_perceive.h"
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-using ds_rec::MA;
-using ds_rec::uniform_i;
-constexpr unsigned ALL = ~0u;             // keep mask of ds_rec::load_bonds
-constexpr int MAX_ORDER = 3, MAX_TYPE = 4;
-constexpr int H = 0, C = 1, N = 2, O = 3, F = 4;
-constexpr unsigned NONE = 3u;             // electron code of "no candidate"
-constexpr int NO_PARTNER = 31;
+using namespace ds_perceive;
 constexpr unsigned EMPTY = ~0u;           // a slot of a "four smallest" list that holds nothing: above every atom mask
 constexpr int PA = DSQ_MAX_PATTERN_ATOMS;
 
@@ -42,20 +36,6 @@ struct Wave {                             // one record's staging area
   unsigned cand[PA * 32];                 // [depth * 32 + lane]: the candidates not yet tried
   unsigned img[PA * 32];                  // [depth * 32 + lane]: the record atom assigned
 };
-
-__device__ __forceinline__ unsigned low32(unsigned long long ballot) { return (unsigned)ballot; }   // atoms live in lanes 0..28
-
-__device__ __forceinline__ unsigned wave_or(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= (unsigned)__shfl_xor((int)v, o, 64);
-  return (unsigned)uniform_i((int)v);
-}
-
-__device__ __forceinline__ unsigned wave_min(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o, 64));
-  return (unsigned)uniform_i((int)v);
-}
 
 // The four smallest distinct values a lane has seen, ascending; named members, so they stay in registers.
 struct Smallest {
@@ -90,18 +70,6 @@ __device__ __forceinline__ int distinct_capped(const Smallest& mine) {
   return count;
 }
 
-__device__ __forceinline__ bool six_electrons(const Wave& S, unsigned members) {
-  unsigned sum = 0u;
-  bool all = true;
-  for (unsigned m = members; m; m &= m - 1u) {                                   // 5 or 6 members
-    const unsigned w = S.electrons[__ffs((int)m) - 1];
-    const unsigned e = ((members >> (w >> 4)) & 1u) ? (w & 3u) : ((w >> 2) & 3u);
-    all &= e != NONE;
-    sum += e;
-  }
-  return all && sum == 6u;
-}
-
 // the matchable atoms that atom `a` reaches over a bond whose class lies in `set`
 __device__ __forceinline__ unsigned reached_by(const Wave& S, int a, unsigned set) {
   unsigned m = 0u;
@@ -117,40 +85,18 @@ struct Record {                           // what the prologue leaves: wave-unif
 
 // Holds three workgroup barriers, which every wave of the workgroup reaches.  n = 0: a wave without a record; `mine` is not touched.
 __device__ __forceinline__ Record prologue(Wave& S, const unsigned char* __restrict__ mine, int n, int lane) {
-  const bool active = lane < n;
-  int type = 0, raw = 0;
-  if (active) {
-    type = mine[DS_REC_TYPE + lane];
-    raw = (int)(signed char)mine[DS_REC_FC + lane];
-  }
-  bool bad = type > MAX_TYPE;
-  const int t = min(type, MAX_TYPE);
-  if (n > 0) ds_rec::load_bonds(S.adj, mine, ALL, lane);
-  __syncthreads();
-  int val = 0;
-  unsigned nb = 0u, nb1 = 0u, nb2 = 0u, nb3 = 0u;
-  if (active)
-    for (int j = 0; j < n; ++j) {
-      const unsigned b = S.adj[lane * 32 + j];
-      bad |= b > (unsigned)MAX_ORDER;
-      val += (int)b;
-      nb |= (b ? 1u : 0u) << j;
-      nb1 |= (b == 1u ? 1u : 0u) << j;
-      nb2 |= (b == 2u ? 1u : 0u) << j;
-      nb3 |= (b == 3u ? 1u : 0u) << j;
-    }
-  const bool usable = n > 0 && __ballot(active && bad) == 0ull;
-  const bool on = usable && active;
-  if (!on) nb = nb1 = nb2 = nb3 = 0u;     // an unusable record has no atoms from here on
+  const Atom A = scan(S.adj, mine, n, lane, ds_refine::Block{});
+  const bool usable = usable_record(A, n), on = usable && A.active;
+  const int t = min(A.type, MAX_TYPE);
+  // an unusable record has no atoms from here on
+  const unsigned nb = on ? A.nb : 0u, nb1 = on ? A.nb1 : 0u, nb2 = on ? A.nb2 : 0u, nb3 = on ? A.nb3 : 0u;
 
   const unsigned isH = low32(__ballot(on && t == H)), isN = low32(__ballot(on && t == N)), isO = low32(__ballot(on && t == O));
-  const int q = ((t == C || t == N) && (raw == 1 || raw == -1)) || (t == O && raw == -1) ? raw : 0;
-  const int vmax = ds_bonds::c_valence[t] + (t == C ? -abs(q) : (t == N || t == O) ? q : 0);
-  const int hi = max(0, vmax - val);
-  const int D = __popc(nb), dbl = __popc(nb2), trp = __popc(nb3);
-  const int X = D + hi, Ht = __popc(nb & isH) + hi;
-  const bool folded = on && t == H && raw == 0 && D == 1 && nb1 == nb && !(nb & isH);
-  const unsigned matchable = low32(__ballot(on && !folded));
+  const int q = applied_charge(t, A.raw);
+  const int hi = max(0, max_valence(t, q) - A.val);
+  const int dbl = __popc(nb2), trp = __popc(nb3);
+  const int X = __popc(nb) + hi, Ht = __popc(nb & isH) + hi;
+  const unsigned matchable = low32(__ballot(on && !(plain_hydrogen(on, t, A.raw, nb, isH) && nb1 == nb)));
   const unsigned me = lane < 32 ? 1u << lane : 0u;
   const bool node = (matchable & me) != 0u;
   if (lane < 32) {
@@ -163,88 +109,30 @@ __device__ __forceinline__ Record prologue(Wave& S, const unsigned char* __restr
   unsigned ring_nb = 0u;
   for (unsigned left = nb; left; left &= left - 1u) {
     const unsigned goal = left & (0u - left);
-    unsigned todo = nb & ~goal, reached = me | todo;
-    while (todo && !(reached & goal)) {
-      const int j = __ffs((int)todo) - 1;
-      todo &= todo - 1u;
-      const unsigned fresh = S.any[j] & ~reached;
-      reached |= fresh;
-      todo |= fresh;
-    }
-    if (reached & goal) ring_nb |= goal;
+    if (ring_bond(S.any, me, nb, goal)) ring_nb |= goal;
   }
   // fragments: the lowest atom a matchable atom reaches in the matched graph is its own in one atom per component
   unsigned lowest = me;
   if (node) {
-    unsigned todo = me, reached = me;
-    while (todo) {
-      const int j = __ffs((int)todo) - 1;
-      todo &= todo - 1u;
-      const unsigned fresh = S.matched[j] & ~reached;
-      reached |= fresh;
-      todo |= fresh;
-    }
+    const unsigned reached = reach(S.matched, me, me, 0u);
     lowest = reached & (0u - reached);
   }
   const int fragments = __popc(low32(__ballot(node && lowest == me)));
 
-  unsigned e_in = NONE, e_out = NONE;
-  int partner = NO_PARTNER;
-  if (on && trp == 0 && dbl <= 1 && X <= 3) {
-    if (dbl == 1) {
-      if ((t == C && X == 3 && q == 0) || (t == N && ((X == 2 && q == 0) || (X == 3 && q == 1)))) {
-        e_in = 1u;
-        partner = __ffs((int)nb2) - 1;
-        e_out = (ring_nb & nb2) ? 1u : (((isN | isO) >> partner) & 1u) ? 0u : NONE;
-      }
-    } else if (t == C) {
-      if (X == 3 && q == -1) e_in = e_out = 2u;
-      else if (X == 3 && q == 1) e_in = e_out = 0u;
-    } else if (t == N) {
-      if ((X == 3 && q == 0) || (X == 2 && q == -1)) e_in = e_out = 2u;
-    } else if (t == O) {
-      if (X == 2 && q == 0) e_in = e_out = 2u;
-    }
-  }
-  if (lane < 32) S.electrons[lane] = e_in | (e_out << 2) | ((unsigned)partner << 4);
+  Electrons e = electron_rule(on, t, q, X, dbl, trp, nb2);
+  if (e.partner != NO_PARTNER) e.e_out = double_bond_outside((ring_nb & nb2) != 0u, e.partner, isN | isO);
+  if (lane < 32) S.electrons[lane] = e.word();
   __syncthreads();
-  const unsigned candidates = low32(__ballot(e_in != NONE));
+  const unsigned candidates = low32(__ballot(e.e_in != NONE));
 
-  // cycles of 5 and 6 atoms through this lane's atom over candidates (at most three neighbours each: 3 * 2 * 2 * 2 * 2 partial paths), each
-  // taken in the direction whose last atom is above its second; the cycles this atom is the lowest of feed the ring count
+  // the cycles through this lane's atom; those it is the lowest atom of feed the ring count
   unsigned arom_nb = 0u;
   Smallest rings;
-  if (e_in != NONE) {
-    const unsigned others = candidates & ~me, below = me - 1u;
-    for (unsigned c1 = nb & others; c1; c1 &= c1 - 1u) {
-      const int a1 = __ffs((int)c1) - 1;
-      const unsigned m1 = me | (1u << a1);
-      for (unsigned c2 = S.any[a1] & others & ~m1; c2; c2 &= c2 - 1u) {
-        const int a2 = __ffs((int)c2) - 1;
-        const unsigned m2 = m1 | (1u << a2);
-        for (unsigned c3 = S.any[a2] & others & ~m2; c3; c3 &= c3 - 1u) {
-          const int a3 = __ffs((int)c3) - 1;
-          const unsigned m3 = m2 | (1u << a3);
-          for (unsigned c4 = S.any[a3] & others & ~m3; c4; c4 &= c4 - 1u) {
-            const int a4 = __ffs((int)c4) - 1;
-            const unsigned m4 = m3 | (1u << a4), n4 = S.any[a4];
-            if ((n4 & me) && a4 > a1 && six_electrons(S, m4)) {
-              arom_nb |= (1u << a1) | (1u << a4);
-              if (!(m4 & below)) rings.insert(m4);
-            }
-            for (unsigned c5 = n4 & others & ~m4; c5; c5 &= c5 - 1u) {
-              const int a5 = __ffs((int)c5) - 1;
-              const unsigned m5 = m4 | (1u << a5);
-              if ((S.any[a5] & me) && a5 > a1 && six_electrons(S, m5)) {
-                arom_nb |= (1u << a1) | (1u << a5);
-                if (!(m5 & below)) rings.insert(m5);
-              }
-            }
-          }
-        }
-      }
-    }
-  }
+  if (e.e_in != NONE)
+    aromatic_cycles<false>(S.any, S.electrons, me, nb, candidates, [&](unsigned members, int second, int last) {
+      arom_nb |= (1u << second) | (1u << last);
+      if (!(members & (me - 1u))) rings.insert(members);
+    });
   const unsigned aromatic = low32(__ballot(arom_nb != 0u));
   const int n_rings = distinct_capped(rings);
 
@@ -376,9 +264,9 @@ __global__ __launch_bounds__(64 * DSQ_WAVES) void k_substructure(const unsigned 
 }
 
 static_assert(DSQ_WAVES >= 1 && 64 * DSQ_WAVES <= 1024, "a workgroup of whole waves");
-static_assert(MA <= 29 && PA <= 14 && DSQ_WORD_ATOM + PA <= DSQ_WORD_LINK && DSQ_WORD_LINK + PA <= DSQ_WORD_CLOSURE &&
+static_assert(PA <= 14 && DSQ_WORD_ATOM + PA <= DSQ_WORD_LINK && DSQ_WORD_LINK + PA <= DSQ_WORD_CLOSURE &&
                   DSQ_WORD_CLOSURE + DSQ_MAX_CLOSURES <= DSQ_PATTERN_WORDS,
-              "atom masks fit 32 bits; the pattern's fields fit its words");
+              "the pattern's fields fit its words");
 static_assert(DSQ_BIT_CHARGE + 3 <= 32 && DSQ_COUNT_CAP == 4 && DSQ_COUNT_CAP < DSQ_TRUNCATED, "six property fields in one word; four slots per lane");
 
 }  // namespace

@@ -6,21 +6,18 @@
 // One wave64 per record, DSV_WAVES records per workgroup, an atom per lane.  LDS holds the bond matrix of ds_rec::load_bonds (and, for the
 // extractor, three 32-byte tables: type, charge to write, original atom of every kept rank); everything else lives in registers: an atom's
 // neighbours are a 29-bit mask, and the components grow by ORing the masks of the atoms reached so far, read with wave shuffles.  No
-// atomics, no early exit: a wave whose record lies beyond P takes part in the workgroup's barriers and writes nothing.
+// atomics, no early exit: a wave whose record lies beyond P takes part in the workgroup's barriers and writes nothing.  From ds_perceive.h:
+// the record scan, applied_charge and max_valence, the component doubling, the wave maximum.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/diffspectra_valence.h"
-#include "ds_bonds.h"
-#include "ds_records.h"
+#include "ds_perceive.h"
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-using ds_rec::MA;
-using ds_rec::uniform_i;
-constexpr unsigned ALL = ~0u;             // keep mask of ds_rec::load_bonds: every atom (the rows below are read up to n only)
-constexpr int MAX_ORDER = 3, MAX_TYPE = 4;
+using namespace ds_perceive;
 constexpr int REC_WORDS = DS_RECORD_BYTES / 4;
 
 // allowed_fc_bonds of the header as bit sets over the valences 0..4: [element][charge + 1]; a charge outside -1..+1 reads the entry for 0,
@@ -32,50 +29,28 @@ struct Wave {                             // one record's staging area
   unsigned char type[32], fc[32], src[32];
 };
 
-struct Atom {                             // what a lane knows of its atom once the record is read (n and usable are wave-uniform)
-  int n;
-  bool usable, active;
-  int type, raw, q, val;                  // type byte, raw and applied charge, valence
-  unsigned nbr;                           // bit j = bonded to atom j
-};
-
-// Reads record `mine` (not touched when n = 0: a wave without a record passes n = 0) and leaves the orders among atoms < n in S.adj.  Holds the
-// one workgroup barrier between writing and reading S.adj; bonds_from is the same for the whole launch, so every wave reaches it.
+// The record as ds_perceive::scan reads it, or, with the bonds from the distances, the same with the orders of ds_bonds::order_of in S.adj and
+// no charges.  Holds the one workgroup barrier between writing and reading S.adj; bonds_from is the same for the whole launch, so every wave
+// reaches it.
 __device__ __forceinline__ Atom read_atoms(Wave& S, const unsigned char* __restrict__ mine, int n, int bonds_from, int lane) {
-  Atom A = {n, false, lane < n, 0, 0, 0, 0, 0u};
-  bool bad = false;
+  if (bonds_from == DSV_BONDS_RECORD) return scan(S.adj, mine, n, lane, ds_refine::Block{});
+  Atom A = {lane < n, false, 0, 0, 0, 0u, 0u, 0u, 0u};
   if (A.active) A.type = mine[DS_REC_TYPE + lane];
-  bad = A.type > MAX_TYPE;
-  const int t = min(A.type, MAX_TYPE);    // a table index whatever the byte; a type above 4 makes the record unusable
-  if (bonds_from == DSV_BONDS_RECORD) {
-    if (A.active) A.raw = (int)(signed char)mine[DS_REC_FC + lane];
-    if (n > 0) ds_rec::load_bonds(S.adj, mine, ALL, lane);
-    __syncthreads();
-    if (A.active)
-      for (int j = 0; j < n; ++j) {
-        const unsigned b = S.adj[lane * 32 + j];
-        bad |= b > (unsigned)MAX_ORDER;
-        A.val += (int)b;
-        A.nbr |= (b ? 1u : 0u) << j;
-      }
-    const int c = A.raw;
-    A.q = ((t == 1 || t == 2) && (c == 1 || c == -1)) || (t == 3 && c == -1) ? c : 0;        // atom_fc_num: N+1, N-1, C+1, O-1, C-1
-  } else {
-    const float* __restrict__ xyz = reinterpret_cast<const float*>(mine + DS_REC_POS);
-    float px = 0.0f, py = 0.0f, pz = 0.0f;
-    if (A.active) { px = xyz[lane * 3]; py = xyz[lane * 3 + 1]; pz = xyz[lane * 3 + 2]; }
-    for (int j = 0; j < n; ++j) {         // every lane takes part in the shuffles
-      const float qx = __shfl(px, j, 64), qy = __shfl(py, j, 64), qz = __shfl(pz, j, 64);
-      const int tj = __shfl(t, j, 64);
-      int order = 0;
-      if (A.active && j != lane) order = ds_bonds::order_of(t, tj, ds_bonds::scaled_distance(px - qx, py - qy, pz - qz));
-      A.val += order;
-      A.nbr |= (order ? 1u : 0u) << j;
-      if (A.active) S.adj[lane * 32 + j] = (unsigned char)order;
-    }
-    __syncthreads();
+  const int t = min(A.type, MAX_TYPE);
+  const float* __restrict__ xyz = reinterpret_cast<const float*>(mine + DS_REC_POS);
+  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  if (A.active) { px = xyz[lane * 3]; py = xyz[lane * 3 + 1]; pz = xyz[lane * 3 + 2]; }
+  for (int j = 0; j < n; ++j) {           // every lane takes part in the shuffles
+    const float qx = __shfl(px, j, 64), qy = __shfl(py, j, 64), qz = __shfl(pz, j, 64);
+    const int tj = __shfl(t, j, 64);
+    int order = 0;
+    if (A.active && j != lane) order = ds_bonds::order_of(t, tj, ds_bonds::scaled_distance(px - qx, py - qy, pz - qz));
+    A.val += order;
+    A.nb |= (order ? 1u : 0u) << j;
+    if (A.active) S.adj[lane * 32 + j] = (unsigned char)order;
   }
-  A.usable = n > 0 && __ballot(A.active && bad) == 0ull;
+  __syncthreads();
+  A.bad = A.type > MAX_TYPE;
   return A;
 }
 
@@ -89,7 +64,7 @@ __global__ __launch_bounds__(64 * DSV_WAVES) void k_valence(const unsigned char*
   const bool live = p < P;
   const int n = live ? ds_rec::atoms_of(n_atoms, p) : 0;
   const Atom A = read_atoms(S[wave], rec + (live ? p : 0) * DS_RECORD_BYTES, n, bonds_from, lane);
-  const int t = min(A.type, MAX_TYPE);
+  const int t = min(A.type, MAX_TYPE);         // a table index whatever the byte; a type above 4 makes the record unusable
 
   bool stable, valid;
   if (bonds_from == DSV_BONDS_RECORD) {
@@ -98,42 +73,27 @@ __global__ __launch_bounds__(64 * DSV_WAVES) void k_valence(const unsigned char*
   } else {
     stable = A.val == ds_bonds::c_valence[t];
   }
-  const int vmax = ds_bonds::c_valence[t] + (t == 1 ? -abs(A.q) : (t == 2 || t == 3) ? A.q : 0);
-  valid = A.val <= vmax;
-  const bool on = A.usable && A.active;
+  valid = A.val <= max_valence(t, applied_charge(t, A.raw));
+  const bool usable = usable_record(A, n), on = usable && A.active;
   const unsigned stable_bits = (unsigned)__ballot(on && stable), valid_bits = (unsigned)__ballot(on && valid);
 
-  // components: comp = the atoms known to be connected to this one; a round ORs in what they know, so the reach doubles
-  unsigned comp = on ? (A.nbr | (1u << (lane & 31))) : 0u;
-  for (int reach = 1; reach < n; reach <<= 1) {
-    unsigned next = comp;
-    for (int j = 0; j < n; ++j) {
-      const unsigned cj = (unsigned)__shfl((int)comp, j, 64);
-      if ((comp >> j) & 1u) next |= cj;
-    }
-    const bool grew = __ballot(next != comp) != 0ull;
-    comp = next;
-    if (!grew) break;
-  }
+  const unsigned comp = components(on ? (A.nb | (1u << (lane & 31))) : 0u, n);
   const int lowest = __ffs((int)comp) - 1;                                     // -1 for a lane without an atom
   const int fragments = __popcll(__ballot(on && lowest == lane));
-  int best = on ? (__popc(comp) << 5) | (31 - lowest) : 0;                     // most atoms first, then the lowest first atom
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
-  best = uniform_i(best);
+  const int best = wave_max(on ? (__popc(comp) << 5) | (31 - lowest) : 0);     // most atoms first, then the lowest first atom
   const unsigned largest = best ? (unsigned)uniform_i(__shfl((int)comp, 31 - (best & 31), 64)) : 0u;
 
   if (live) {
     if (lane < MA) valence[p * MA + lane] = (unsigned char)(on ? A.val : 0);
     if (lane < 4) {
       const int v = lane == 0 ? n : lane == 1 ? __popc(stable_bits) : lane == 2 ? fragments : best >> 5;
-      summary[p * 4 + lane] = A.usable ? v : 0;
+      summary[p * 4 + lane] = usable ? v : 0;
     }
     if (lane == 0) {
       stable_mask[p] = (int32_t)stable_bits;
       valid_mask[p] = (int32_t)valid_bits;
       largest_mask[p] = (int32_t)largest;
-      status[p] = (unsigned char)(A.usable ? DSV_OK : DSV_UNUSABLE);
+      status[p] = (unsigned char)(usable ? DSV_OK : DSV_UNUSABLE);
     }
   }
 }
@@ -149,11 +109,11 @@ __global__ __launch_bounds__(64 * DSV_WAVES) void k_fragment(const unsigned char
   const unsigned char* __restrict__ mine = rec + (live ? p : 0) * DS_RECORD_BYTES;
   Wave& W = S[wave];
   const Atom A = read_atoms(W, mine, n, bonds_from, lane);
-  const unsigned kept = A.usable ? (unsigned)keep[p] & ((1u << n) - 1u) : 0u;  // n <= 29
+  const unsigned kept = usable_record(A, n) ? (unsigned)keep[p] & ((1u << n) - 1u) : 0u;  // n <= 29
   const int m = __popc(kept);
   if (lane < 32) {
     W.type[lane] = (unsigned char)(A.active ? A.type : 0);
-    W.fc[lane] = (unsigned char)(charge_rule ? A.q : A.raw);                   // both 0 when the orders come from the distances
+    W.fc[lane] = (unsigned char)(charge_rule ? applied_charge(min(A.type, MAX_TYPE), A.raw) : A.raw);   // both 0 with the orders from the distances
     if ((kept >> lane) & 1u) W.src[__popc(kept & ((1u << lane) - 1u))] = (unsigned char)lane;
   }
   __syncthreads();

@@ -1,5 +1,5 @@
 """The one description of the C-ABI on the Python side: the headers (``include/diffspectra_hip.h`` for sampling, ``include/diffspectra_train.h``
-for training, ``include/diffspectra_sets.h`` for the set-against-set analytics, ``include/diffspectra_valence.h`` for the valence analytics, ``include/diffspectra_groups.h`` for the functional groups, ``include/diffspectra_scaffold.h`` for the scaffolds, ``include/diffspectra_smiles.h`` for the SMILES strings, ``include/diffspectra_substructure.h`` for the substructure matcher,``include/diffspectra_tiles.h`` for the launch-form switches, ``include/diffspectra_step.h`` for the uniform-step entry points) are read here and nowhere else.  ``engine`` and ``train_engine`` build their ctypes types and ``struct`` packers from what this
+for training, ``include/diffspectra_sets.h`` for the set-against-set analytics, ``include/diffspectra_valence.h`` for the valence analytics, ``include/diffspectra_groups.h`` for the functional groups, ``include/diffspectra_scaffold.h`` for the scaffolds, ``include/diffspectra_smiles.h`` for the SMILES strings, ``include/diffspectra_substructure.h`` for the substructure matcher, ``include/diffspectra_stereo.h`` for the stereo-aware identity, ``include/diffspectra_tiles.h`` for the launch-form switches, ``include/diffspectra_step.h`` for the uniform-step entry points) are read here and nowhere else.  ``engine`` and ``train_engine`` build their ctypes types and ``struct`` packers from what this
 module parsed, so a struct is described once, in its header; the library reports its ``sizeof``s and the loaders compare.  The function
 prototypes are read too: ``Header.bind`` gives every export its ``argtypes``, so a call site passes plain Python numbers and data pointers and
 ctypes refuses a call with too few arguments or with one of the wrong kind."""
@@ -40,7 +40,7 @@ def ptr(t):
 
 class Header:
     """One parsed header: ``enums`` {enum name: enumerator names in order}, ``consts`` {name: int} of the enumerators and of every ``#define``
-    that evaluates to an integer, ``structs`` {struct name: [(field, struct code)]} of every ``typedef struct``, ``prototypes`` {function
+    that evaluates to an integer, ``reals`` {name: float} of every ``#define`` of a decimal literal, ``structs`` {struct name: [(field, struct code)]} of every ``typedef struct``, ``prototypes`` {function
     name: Prototype} of every exported function."""
 
     def __init__(self, file_name: str, text: str = None):
@@ -68,6 +68,7 @@ class Header:
                         self.consts[k] = int(eval(v, {"__builtins__": {}}, self.consts))
                     except Exception:
                         pass
+        self.reals: Dict[str, float] = {k: float(v) for k, v in re.findall(r"#define\s+(\w+)\s+(\d+\.\d+(?:[eE][-+]?\d+)?)\s*$", self.text, flags=re.M)}
         self.structs = {name: self._fields(body) for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}", self.text, flags=re.S)}
         self.prototypes = {name: Prototype(name, ret, self._params(name, params))
                            for ret, name, params in re.findall(r"^\s*(int|void)\s+(\w+)\s*\(([^()]*)\)\s*;", self.text, flags=re.M)}
@@ -134,5 +135,6 @@ GROUPS = Header("diffspectra_groups.h")
 SCAFFOLD = Header("diffspectra_scaffold.h")
 SMILES = Header("diffspectra_smiles.h")
 SUBSTRUCTURE = Header("diffspectra_substructure.h")
+STEREO = Header("diffspectra_stereo.h")
 TILES = Header("diffspectra_tiles.h")
 STEP = Header("diffspectra_step.h")

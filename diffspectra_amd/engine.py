@@ -60,6 +60,7 @@ def load_library() -> C.CDLL:
     abi.SCAFFOLD.bind(lib)
     abi.SMILES.bind(lib)
     abi.SUBSTRUCTURE.bind(lib)
+    abi.STEREO.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
     sizes = (C.c_int64 * 4)()
@@ -907,6 +908,58 @@ def substructure_records(rec: torch.Tensor, n: torch.Tensor, patterns: torch.Ten
                         [(torch.uint8, (K,)), (torch.int32, (K,)), (torch.int32, (K,)), i32, i32, i32, (torch.uint8, ())], prefix="dsq_", also=[patterns])
 
 
+# ----------------------------------------------------------------------------------------- stereo-aware identity
+
+STEREO_CONSTS = abi.STEREO.consts         # include/diffspectra_stereo.h
+STEREO_DIFFERENT, STEREO_IDENTICAL, STEREO_UNDECIDED, STEREO_INVALID, STEREO_MIRROR, STEREO_STEREOISOMER, STEREO_UNASSIGNED = (
+    STEREO_CONSTS["DSC_" + k] for k in ("DIFFERENT", "IDENTICAL", "UNDECIDED", "INVALID", "MIRROR", "STEREOISOMER", "UNASSIGNED"))
+STEREO_MIN_VOLUME, STEREO_MIN_PLANARITY = abi.STEREO.reals["DSC_MIN_VOLUME"], abi.STEREO.reals["DSC_MIN_PLANARITY"]
+STEREO_OK, STEREO_UNUSABLE, STEREO_NUM_MASKS = STEREO_CONSTS["DSC_OK"], STEREO_CONSTS["DSC_UNUSABLE"], STEREO_CONSTS["DSC_NUM_MASKS"]
+
+
+def _stereo_thresholds(min_volume, min_planarity):
+    """The two thresholds as floats, ``None`` = the header's default; a NaN or a negative one raises."""
+    out = []
+    for name, value, default in (("min_volume", min_volume, STEREO_MIN_VOLUME), ("min_planarity", min_planarity, STEREO_MIN_PLANARITY)):
+        value = default if value is None else float(value)
+        if not value >= 0.0:
+            raise ValueError(f"{name} must be a number >= 0, got {value}")
+        out.append(value)
+    return out
+
+
+def stereo_identity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                            ref_index: Optional[torch.Tensor] = None, max_nodes: int = 4096, min_volume: Optional[float] = None,
+                            min_planarity: Optional[float] = None, exhaustive: bool = False):
+    """``dsc_stereo_identity_records``: is the generated molecule of each of P pairs the same labelled graph as its ground truth AND the same
+    stereoisomer, read from the records' positions (every definition in ``include/diffspectra_stereo.h``: twins and ordinals, tetrahedral
+    and E/Z sites with the thresholds ``min_volume`` / ``min_planarity`` - ``None``: the header's 0.5 / 0.5 -, same and mirror isomorphisms).
+
+    The tensors are those of ``match_records``.  Returns the device tensors ``(verdict [P] u8, nodes [P] i32, found [P, 3] i32, sites [P, 4]
+    i32, map [P, 29] i32)``, enqueued on the current stream without synchronising: verdict ``STEREO_DIFFERENT`` (0), ``STEREO_IDENTICAL`` (1),
+    ``STEREO_UNDECIDED`` (2: the search needed more than ``max_nodes`` tries), ``STEREO_INVALID`` (3), ``STEREO_MIRROR`` (4: an enantiomer),
+    ``STEREO_STEREOISOMER`` (5: a diastereomer or E/Z isomer) or ``STEREO_UNASSIGNED`` (6: same constitution, a site too flat to tell);
+    ``found`` = isomorphisms, same, mirror met until the search stopped (``exhaustive=True``: it stops only when none is left); ``sites`` =
+    tetrahedral and E/Z sites of the generated molecule, unassigned sites of it and of the ground truth; ``map`` = the isomorphism behind the
+    verdict.  The arguments are checked, never converted."""
+    if not isinstance(exhaustive, (bool, int)) or exhaustive not in (0, 1):
+        raise TypeError(f"exhaustive must be a bool, got {exhaustive!r}")
+    return _record_call("stereo_identity_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index,
+                        [_node_budget(max_nodes, GRAPH_MAX_NODES), *_stereo_thresholds(min_volume, min_planarity), int(exhaustive)],
+                        [(torch.uint8, ()), (torch.int32, ()), (torch.int32, (3,)), (torch.int32, (4,)), _MAP], prefix="dsc_")
+
+
+def stereo_sites(rec: torch.Tensor, n: torch.Tensor, min_volume: Optional[float] = None, min_planarity: Optional[float] = None):
+    """``dsc_stereo_sites``: the twins and the stereo sites of every record (definitions in ``include/diffspectra_stereo.h``).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(masks [P, 7] i32, volume [P, 29] f64, status [P] u8)`` on the current stream
+    without synchronising: the rows of ``masks`` hold a bit per atom (tetrahedral site, assigned, V > 0; end of an E/Z site, assigned, cis;
+    twin - the header's ``DSC_MASK_*`` order), ``volume`` is V of every tetrahedral site and NaN elsewhere, status ``STEREO_UNUSABLE`` (3: n = 0,
+    a type above 4, a bond byte above 3) zeroes the masks.  Checked, never converted; no CPU path."""
+    return _record_call("stereo_sites", [(rec, n)], None, _stereo_thresholds(min_volume, min_planarity),
+                        [(torch.int32, (STEREO_NUM_MASKS,)), (torch.float64, (MAX_ATOMS,)), (torch.uint8, ())], prefix="dsc_")
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -1119,6 +1172,15 @@ class DmtEngine:
     def substructure_records(self, rec, n, patterns, max_nodes: int = SUBSTRUCTURE_DEFAULT_NODES):
         """``engine.substructure_records`` on this engine's library (the matcher needs no weights)."""
         return substructure_records(rec, n, patterns, max_nodes)
+
+    def stereo_identity_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, max_nodes: int = 4096, min_volume=None,
+                                min_planarity=None, exhaustive: bool = False):
+        """``engine.stereo_identity_records`` on this engine's library (the comparison needs no weights)."""
+        return stereo_identity_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, max_nodes, min_volume, min_planarity, exhaustive)
+
+    def stereo_sites(self, rec, n, min_volume=None, min_planarity=None):
+        """``engine.stereo_sites`` on this engine's library (the perception needs no weights)."""
+        return stereo_sites(rec, n, min_volume, min_planarity)
 
     def post_process(self, L, xh, edge_x):
         dev = self.device

@@ -138,6 +138,25 @@ def _maccs_summary(run, table, top_k: int, max_nodes: Optional[int] = None) -> D
     return entry
 
 
+def _stereo_summary(run, table, top_k: int, min_volume: Optional[float] = None, min_planarity: Optional[float] = None) -> Dict:
+    """The stereo-aware Top-1 / Top-K of one finished run (the pairs of ``_structure_summary``): ``dsc_stereo_identity_records`` per slot, and
+    how many of the slots' ground truths are chiral.  The thresholds: ``None`` for the header's defaults."""
+    from .structure_metrics import chirality, stereo_identity_batch, topk_identity
+    dev = run.records_by_slot.device
+    ref, prb = (table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms))
+    same = stereo_identity_batch(ref, prb, ref_index=run.slot_ds, min_volume=min_volume, min_planarity=min_planarity, engine=run.eng)
+    P = same.verdict.numel()
+    rate = lambda hit: float(hit.double().mean()) if P else 0.0
+    slot_rows = torch.as_tensor(run.slot_ds).to(device=dev, dtype=torch.int64)
+    targets = chirality(ref[0], ref[1], min_volume=min_volume, min_planarity=min_planarity, engine=run.eng).chiral[slot_rows]
+    entry = dict(verdict=same.verdict, identity_rate=rate(same.identical), constitution_rate=rate(same.same_constitution),
+                 enantiomer_rate=rate(same.mirror), stereoisomer_rate=rate(same.stereoisomer), unassigned=int(same.unassigned.sum()),
+                 undecided=int(same.undecided.sum()), sites=same.sites, chiral_targets=rate(targets == 1))
+    if top_k > 1:
+        entry["top_k"] = topk_identity(same.verdict, top_k)
+    return entry
+
+
 def _scaffold_summary(run, table, top_k: int, scaffold_fn, min_rings: int) -> Dict:
     """The "Scaf" number of one finished run against the test table (``scaffold_fn``: ``get_scaffold_metric`` of its records) and, over the
     pairs of ``_structure_summary``, whether every generated molecule shares the scaffold of its ground truth."""
@@ -264,6 +283,17 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     default when absent; such keys are a lower bound) and, with K > 1, ``top_k = topk_maccs(...)``.  The key table restates RDKit's as remembered: parity with RDKit is unpinned
     (``structure_metrics.maccs_similarity_batch``).  Without the flag the dict has no such key.
 
+    With ``config.eval.stereo`` true ``metrics['structure']['stereo']`` is the stereo-aware Top-1 (``dsc_stereo_identity_records``; the reference's
+    Top-1 compares InChIKeys, ``compute_metrics.py:222-230``, which ``metrics['structure']['graph']`` does at constitution level only): ``verdict``
+    (u8 device tensor, one per slot: 0 different, 1 identical, 2 undecided, 3 invalid, 4 mirror image, 5 another stereoisomer, 6 a site too
+    flat to tell), ``identity_rate`` (verdict 1 over all slots), ``constitution_rate`` (1, 4, 5 or 6: what ``graph`` calls identical),
+    ``enantiomer_rate`` (4), ``stereoisomer_rate`` (5), ``unassigned`` and ``undecided`` (counts: how much hangs on the two thresholds and on the
+    budget), ``sites`` (i32 device tensor [slots, 4]: tetrahedral and E/Z sites of the generated molecule, unassigned sites of it and of its
+    ground truth), ``chiral_targets`` (the fraction of the slots whose ground truth is chiral: a tetrahedral site and no mirror automorphism) and,
+    with K > 1, ``top_k = topk_identity(verdict, K)``.  ``config.eval.stereo_min_volume`` / ``stereo_min_planarity`` replace the header's 0.5 /
+    0.5; they are definitions, nobody has measured how generated molecules distribute around them.  Four-coordinate centres and double bonds
+    only, no InChI normalisation, parity with RDKit / InChI unpinned (``include/diffspectra_stereo.h``).  Without the flag the dict has no such key.
+
     With ``config.eval.smiles`` true ``metrics['structure']['smiles']`` holds the molecules as text, where the reference calls ``Chem.MolToSmiles``
     (``run_lib.py:111-112``, ``compute_metrics.py:73-78,209-220``; ``dsl_smiles_records``): ``generated`` (one canonical SMILES string per slot,
     ``None`` for an overflow or unusable record), ``ground_truth`` (the string of every slot's ground truth), ``same`` / ``status`` / ``pair_status``
@@ -322,6 +352,9 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                 metrics["structure"]["functional_groups"] = _functional_group_summary(run, test_ds, top_k)
             if getattr(config.eval, "maccs", False):
                 metrics["structure"]["maccs"] = _maccs_summary(run, test_ds, top_k, getattr(config.eval, "maccs_max_nodes", None))
+            if getattr(config.eval, "stereo", False):
+                metrics["structure"]["stereo"] = _stereo_summary(run, test_ds, top_k, getattr(config.eval, "stereo_min_volume", None),
+                                                                 getattr(config.eval, "stereo_min_planarity", None))
             if getattr(config.eval, "sub_geometry", False):
                 from .structure_metrics import get_sub_geometry_metric
                 if geometry_fn is None:

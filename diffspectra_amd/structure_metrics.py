@@ -1254,3 +1254,91 @@ def topk_maccs(tanimoto: torch.Tensor, status: torch.Tensor, top_k: int) -> Dict
     if top_k < 1 or tanimoto.numel() % top_k or status.shape != tanimoto.shape:
         raise ValueError(f"{tanimoto.numel()} pairs (status: {status.numel()}) are not a whole number of top_k = {top_k} groups")
     return topk_morgan(torch.where(status == 0, tanimoto.to(torch.float64), torch.full_like(tanimoto, float("nan"), dtype=torch.float64)), top_k)
+
+
+# ------------------------------------------------------------------------------------------------------------------ stereo-aware identity
+
+class StereoIdentity(NamedTuple):
+    """Per-pair device tensors of ``dsc_stereo_identity_records``."""
+    verdict: torch.Tensor     # [P] u8: 0 different, 1 identical, 2 undecided, 3 invalid row (as ``GraphIdentity``), 4 mirror image, 5 another stereoisomer, 6 unassigned
+    nodes: torch.Tensor       # [P] i32 search nodes used
+    found: torch.Tensor       # [P, 3] i32 isomorphisms, same, mirror met until the search stopped
+    sites: torch.Tensor       # [P, 4] i32 tetrahedral sites and E/Z sites of the generated molecule, unassigned sites of it and of the ground truth
+    map: torch.Tensor         # [P, 29] i32 the isomorphism behind verdict 1, 4, 5 or 6 (ground-truth atom of every generated atom), else -1
+
+    @property
+    def identical(self) -> torch.Tensor:
+        return self.verdict == 1
+
+    @property
+    def mirror(self) -> torch.Tensor:
+        return self.verdict == 4
+
+    @property
+    def stereoisomer(self) -> torch.Tensor:
+        return self.verdict == 5
+
+    @property
+    def unassigned(self) -> torch.Tensor:
+        return self.verdict == 6
+
+    @property
+    def undecided(self) -> torch.Tensor:
+        return self.verdict == 2
+
+    @property
+    def same_constitution(self) -> torch.Tensor:
+        """An isomorphism of the labelled graphs was found: what ``graph_identity_batch`` calls identical."""
+        return (self.verdict == 1) | (self.verdict >= 4)
+
+
+class StereoSites(NamedTuple):
+    """Per-record device tensors of ``dsc_stereo_sites``; every mask holds a bit per atom."""
+    tetra_site: torch.Tensor      # [P] i32 four-coordinate centres without twin neighbours
+    tetra_assigned: torch.Tensor  # [P] i32 ... whose |V| reaches ``min_volume``
+    tetra_positive: torch.Tensor  # [P] i32 ... with V > 0
+    ez_site: torch.Tensor         # [P] i32 both ends of every E/Z double bond
+    ez_assigned: torch.Tensor     # [P] i32 ... that is planar enough
+    ez_cis: torch.Tensor          # [P] i32 ... whose lowest substituents are cis
+    twin: torch.Tensor            # [P] i32 atoms with a twin
+    volume: torch.Tensor          # [P, 29] f64 V of every tetrahedral site, NaN elsewhere
+    status: torch.Tensor          # [P] u8 0 ok, 3 unusable (masks 0)
+
+
+class Chirality(NamedTuple):
+    """What ``chirality`` returns, per record."""
+    chiral: torch.Tensor          # [P] u8: 1 a tetrahedral site and no mirror automorphism, 0 achiral or without such a site, 2 unassigned or undecided
+    automorphisms: torch.Tensor   # [P] i32 automorphisms of the ordinal-labelled graph, -1 where the search ran out of its budget
+
+
+def stereo_identity_batch(ref, prb, ref_index=None, max_nodes: int = 4096, min_volume: Optional[float] = None, min_planarity: Optional[float] = None,
+                          exhaustive: bool = False, engine=None) -> StereoIdentity:
+    """Identity of every generated molecule with its ground truth as a labelled graph AND as a stereoisomer, read from the positions of the
+    records (``dsc_stereo_identity_records``; every definition in ``include/diffspectra_stereo.h``): tetrahedral centres by the sign of a
+    volume, double bonds by cis / trans, ``min_volume`` / ``min_planarity`` (``None``: the header's 0.5 / 0.5) below which a site is unassigned.
+    Closer to the InChIKey comparison of the reference's Top-1 than ``graph_identity_batch``, with stated deviations: no tautomer / charge
+    normalisation, four-coordinate centres only (no three-coordinate N, no allenes, no helicity), perception by twins, parity with RDKit /
+    InChI unpinned.  ``ref`` and ``prb`` are ``(records [*, 1248] u8, n_atoms [*])`` pairs on the GPU, ground truth first as in
+    ``graph_identity_batch``; ``ref_index [P]`` names the ground-truth row of every generated molecule (``None``: row p).  ``topk_identity`` works
+    on the verdict unchanged.  Device tensors, no synchronisation."""
+    return StereoIdentity(*_pair_call("stereo_identity_records", engine, ref, prb, ref_index, max_nodes, min_volume, min_planarity, exhaustive))
+
+
+def stereo_sites(records: torch.Tensor, n_atoms, min_volume: Optional[float] = None, min_planarity: Optional[float] = None, engine=None) -> StereoSites:
+    """The twins and the stereo sites of every record of ``records [P, 1248] u8`` (GPU) in one launch of ``dsc_stereo_sites``.  Device tensors,
+    no synchronisation."""
+    from . import engine as E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    masks, volume, status = (engine if engine is not None else E).stereo_sites(records, n, min_volume, min_planarity)
+    return StereoSites(*masks.unbind(dim=1), volume, status)
+
+
+def chirality(records: torch.Tensor, n_atoms, max_nodes: int = 4096, min_volume: Optional[float] = None, min_planarity: Optional[float] = None,
+              engine=None) -> Chirality:
+    """Is every molecule of ``records`` chiral in the sense of ``include/diffspectra_stereo.h``: it has a tetrahedral site and none of its
+    automorphisms is a mirror (every record against itself, all automorphisms enumerated).  A meso compound is achiral; a molecule whose
+    only stereo sites are double bonds is achiral.  Device tensors, no synchronisation."""
+    own = stereo_identity_batch((records, n_atoms), (records, n_atoms), None, max_nodes, min_volume, min_planarity, True, engine)
+    decided = own.verdict == 1
+    chiral = torch.where(decided, ((own.sites[:, 0] > 0) & (own.found[:, 2] == 0)).to(torch.uint8), torch.full_like(own.verdict, 2))
+    return Chirality(chiral, torch.where(own.verdict == 2, torch.full_like(own.found[:, 0], -1), own.found[:, 0]))

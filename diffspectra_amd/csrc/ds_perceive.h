@@ -1,8 +1,9 @@
 // diffspectra_amd - perception of one result record by one wave64, an atom per lane: what the per-record evaluation kernels share
-// (ds_valence.hip, ds_groups.hip, ds_scaffold.hip, ds_smiles.hip, ds_substructure.hip).  The definitions are those of the public headers:
-// applied charges and the valence check in include/diffspectra_valence.h, ring bonds and the candidate / electron rule in
-// include/diffspectra_groups.h, the plain-hydrogen fold in include/diffspectra_smiles.h.  Everything here is inlined into its caller, which
-// keeps its own LDS struct and passes the arrays: a result that a caller does not read costs it nothing.
+// (ds_valence.hip, ds_groups.hip, ds_scaffold.hip, ds_smiles.hip, ds_substructure.hip, ds_brics.hip).  The definitions are those of the
+// public headers: applied charges and the valence check in include/diffspectra_valence.h, ring bonds and the candidate / electron rule in
+// include/diffspectra_groups.h, the plain-hydrogen fold in include/diffspectra_smiles.h, the matched graph in
+// include/diffspectra_substructure.h.  Everything here is inlined into its caller, which keeps its own LDS struct and passes the arrays: a
+// result that a caller does not read costs it nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -200,6 +201,65 @@ __device__ __forceinline__ void aromatic_cycles(const unsigned (&any)[32], const
       }
     }
   }
+}
+
+// The matched graph of include/diffspectra_substructure.h as one lane sees it, for the kernels that run on it (ds_substructure.hip,
+// ds_brics.hip): the fold, the ring bonds of every bond and the aromatic-bond neighbours from the cycles through the lane's OWN atom (not only
+// those it is the lowest atom of), so that a lane learns them without a scatter.  From these a caller forms the bond classes of its atom:
+// kind single / double / triple = nb1 / nb2 / nb3 without arom_nb, aromatic = arom_nb, each among `matchable`, by ring = ring_nb.
+struct Matched {
+  bool usable, on, node;                  // the record is usable / and this lane holds an atom / and that atom is matchable
+  int t, q, hi;                           // type (a table index), applied charge, implicit hydrogens
+  unsigned nb, nb1, nb2, nb3;             // bonded by any order / by order 1 / 2 / 3; 0 in an unusable record
+  unsigned isH, isN, isO;                 // the atoms of these elements
+  unsigned matchable, ring_nb, arom_nb;   // matchable atoms (wave-uniform); the neighbours over a ring bond, over an aromatic bond
+};
+
+// Holds three workgroup barriers, which every wave of the workgroup reaches.  n = 0: a wave without a record; `mine` is not touched.  Leaves
+// adj, any (neighbours by any order), matched (the same among matchable atoms, 0 for a folded hydrogen) and the electron words in the
+// caller's LDS.  closed(members) is called for every aromatic cycle through the lane's atom.
+template <class Closed>
+__device__ __forceinline__ Matched matched_graph(unsigned char* __restrict__ adj, unsigned (&any)[32], unsigned (&matched)[32], unsigned (&electrons)[32],
+                                                 const unsigned char* __restrict__ mine, int n, int lane, Closed closed) {
+  const Atom A = scan(adj, mine, n, lane, ds_refine::Block{});
+  const bool usable = usable_record(A, n), on = usable && A.active;
+  const int t = min(A.type, MAX_TYPE);
+  // an unusable record has no atoms from here on
+  const unsigned nb = on ? A.nb : 0u, nb1 = on ? A.nb1 : 0u, nb2 = on ? A.nb2 : 0u, nb3 = on ? A.nb3 : 0u;
+
+  const unsigned isH = low32(__ballot(on && t == H)), isN = low32(__ballot(on && t == N)), isO = low32(__ballot(on && t == O));
+  const int q = applied_charge(t, A.raw);
+  const int hi = max(0, max_valence(t, q) - A.val);
+  const int dbl = __popc(nb2), trp = __popc(nb3);
+  const int X = __popc(nb) + hi;
+  const unsigned matchable = low32(__ballot(on && !(plain_hydrogen(on, t, A.raw, nb, isH) && nb1 == nb)));
+  const unsigned me = lane < 32 ? 1u << lane : 0u;
+  const bool node = (matchable & me) != 0u;
+  if (lane < 32) {
+    any[lane] = nb;
+    matched[lane] = node ? nb & matchable : 0u;
+  }
+  __syncthreads();
+
+  // ring bonds: neighbour j is reached without the bond to it; every atom is expanded once per neighbour
+  unsigned ring_nb = 0u;
+  for (unsigned left = nb; left; left &= left - 1u) {
+    const unsigned goal = left & (0u - left);
+    if (ring_bond(any, me, nb, goal)) ring_nb |= goal;
+  }
+  Electrons e = electron_rule(on, t, q, X, dbl, trp, nb2);
+  if (e.partner != NO_PARTNER) e.e_out = double_bond_outside((ring_nb & nb2) != 0u, e.partner, isN | isO);
+  if (lane < 32) electrons[lane] = e.word();
+  __syncthreads();
+  const unsigned candidates = low32(__ballot(e.e_in != NONE));
+
+  unsigned arom_nb = 0u;
+  if (e.e_in != NONE)
+    aromatic_cycles<false>(any, electrons, me, nb, candidates, [&](unsigned members, int second, int last) {
+      arom_nb |= (1u << second) | (1u << last);
+      closed(members);
+    });
+  return {usable, on, node, t, q, hi, nb, nb1, nb2, nb3, isH, isN, isO, usable ? matchable : 0u, ring_nb, arom_nb};
 }
 
 static_assert(MA <= 29, "an atom mask fits a 32-bit word with lanes 29..31 clear; a partner index fits the electron word");

@@ -85,32 +85,17 @@ struct Record {                           // what the prologue leaves: wave-unif
 
 // Holds three workgroup barriers, which every wave of the workgroup reaches.  n = 0: a wave without a record; `mine` is not touched.
 __device__ __forceinline__ Record prologue(Wave& S, const unsigned char* __restrict__ mine, int n, int lane) {
-  const Atom A = scan(S.adj, mine, n, lane, ds_refine::Block{});
-  const bool usable = usable_record(A, n), on = usable && A.active;
-  const int t = min(A.type, MAX_TYPE);
-  // an unusable record has no atoms from here on
-  const unsigned nb = on ? A.nb : 0u, nb1 = on ? A.nb1 : 0u, nb2 = on ? A.nb2 : 0u, nb3 = on ? A.nb3 : 0u;
-
-  const unsigned isH = low32(__ballot(on && t == H)), isN = low32(__ballot(on && t == N)), isO = low32(__ballot(on && t == O));
-  const int q = applied_charge(t, A.raw);
-  const int hi = max(0, max_valence(t, q) - A.val);
-  const int dbl = __popc(nb2), trp = __popc(nb3);
-  const int X = __popc(nb) + hi, Ht = __popc(nb & isH) + hi;
-  const unsigned matchable = low32(__ballot(on && !(plain_hydrogen(on, t, A.raw, nb, isH) && nb1 == nb)));
   const unsigned me = lane < 32 ? 1u << lane : 0u;
-  const bool node = (matchable & me) != 0u;
-  if (lane < 32) {
-    S.any[lane] = nb;
-    S.matched[lane] = node ? nb & matchable : 0u;
-  }
-  __syncthreads();
+  // the cycles through this lane's atom; those it is the lowest atom of feed the ring count
+  Smallest rings;
+  const Matched M = matched_graph(S.adj, S.any, S.matched, S.electrons, mine, n, lane, [&](unsigned members) {
+    if (!(members & (me - 1u))) rings.insert(members);
+  });
+  const bool usable = M.usable, node = M.node;
+  const int t = M.t, q = M.q;
+  const unsigned nb = M.nb, matchable = M.matchable, ring_nb = M.ring_nb, arom_nb = M.arom_nb;
+  const int X = __popc(nb) + M.hi, Ht = __popc(nb & M.isH) + M.hi;
 
-  // ring bonds: neighbour j is reached without the bond to it; every atom is expanded once per neighbour
-  unsigned ring_nb = 0u;
-  for (unsigned left = nb; left; left &= left - 1u) {
-    const unsigned goal = left & (0u - left);
-    if (ring_bond(S.any, me, nb, goal)) ring_nb |= goal;
-  }
   // fragments: the lowest atom a matchable atom reaches in the matched graph is its own in one atom per component
   unsigned lowest = me;
   if (node) {
@@ -118,28 +103,13 @@ __device__ __forceinline__ Record prologue(Wave& S, const unsigned char* __restr
     lowest = reached & (0u - reached);
   }
   const int fragments = __popc(low32(__ballot(node && lowest == me)));
-
-  Electrons e = electron_rule(on, t, q, X, dbl, trp, nb2);
-  if (e.partner != NO_PARTNER) e.e_out = double_bond_outside((ring_nb & nb2) != 0u, e.partner, isN | isO);
-  if (lane < 32) S.electrons[lane] = e.word();
-  __syncthreads();
-  const unsigned candidates = low32(__ballot(e.e_in != NONE));
-
-  // the cycles through this lane's atom; those it is the lowest atom of feed the ring count
-  unsigned arom_nb = 0u;
-  Smallest rings;
-  if (e.e_in != NONE)
-    aromatic_cycles<false>(S.any, S.electrons, me, nb, candidates, [&](unsigned members, int second, int last) {
-      arom_nb |= (1u << second) | (1u << last);
-      if (!(members & (me - 1u))) rings.insert(members);
-    });
   const unsigned aromatic = low32(__ballot(arom_nb != 0u));
   const int n_rings = distinct_capped(rings);
 
   // the eight class masks of this atom and its property word
   if (lane < 32) {
     const unsigned keep = node ? matchable : 0u, plain = keep & ~arom_nb;
-    const unsigned kind[4] = {nb1 & plain, nb2 & plain, nb3 & plain, arom_nb & keep};
+    const unsigned kind[4] = {M.nb1 & plain, M.nb2 & plain, M.nb3 & plain, arom_nb & keep};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       S.cls[k * 32 + lane] = kind[k] & ~ring_nb;

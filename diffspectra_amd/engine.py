@@ -61,6 +61,7 @@ def load_library() -> C.CDLL:
     abi.SMILES.bind(lib)
     abi.SUBSTRUCTURE.bind(lib)
     abi.STEREO.bind(lib)
+    abi.BRICS.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
     sizes = (C.c_int64 * 4)()
@@ -854,6 +855,58 @@ def scaffold_masks(rec: torch.Tensor, n: torch.Tensor):
     return _record_call("scaffold_masks", [(rec, n)], None, [], [i32, i32, (torch.int32, (4,)), (torch.uint8, ())], prefix="dsk_")
 
 
+# ----------------------------------------------------------------------------------------- BRICS cuts and fragments
+
+BRICS_CONSTS = abi.BRICS.consts           # include/diffspectra_brics.h
+BRICS_OK, BRICS_UNUSABLE = BRICS_CONSTS["DSB_OK"], BRICS_CONSTS["DSB_UNUSABLE"]
+BRICS_MAX_CUTS, BRICS_ATTACH_TYPE, BRICS_AROMATIC_ORDER = (BRICS_CONSTS["DSB_" + k] for k in ("MAX_CUTS", "ATTACH_TYPE", "AROMATIC_ORDER"))
+
+
+def brics_records(rec: torch.Tensor, n: torch.Tensor):
+    """``dsb_brics_records``: the BRICS environments of every atom, the cut bonds with their labels and the fragment of every atom (every
+    definition in ``include/diffspectra_brics.h``: thirteen environments and forty rules on the hydrogen-folded graph of the substructure
+    matcher, restated from RDKit's ``BRICS.py`` as remembered and unpinned against RDKit).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(env [P, 29] i32, cuts [P, 28, 4] u8, fragment_of [P, 29] u8, summary [P, 4] i32,
+    status [P] u8)`` on the current stream without synchronising: bit e of ``env`` = the atom is in L_e; a row of ``cuts`` is (a, b, label of a,
+    label of b) with a < b, ascending, 0xff where unused; ``fragment_of`` is 0xff for atoms >= n; ``summary`` is (matchable atoms, cuts,
+    fragments, atoms of the largest fragment); status ``BRICS_UNUSABLE`` (3: n = 0, a type above 4, a bond byte above 3) zeroes the row
+    (``cuts`` and ``fragment_of``: 0xff).  Checked, never converted; no CPU path."""
+    return _record_call("brics_records", [(rec, n)], None, [],
+                        [(torch.int32, (MAX_ATOMS,)), (torch.uint8, (BRICS_MAX_CUTS, 4)), (torch.uint8, (MAX_ATOMS,)), (torch.int32, (4,)), (torch.uint8, ())],
+                        prefix="dsb_")
+
+
+def brics_fragment_records(rec: torch.Tensor, n: torch.Tensor, first: torch.Tensor, rows: int, aromatic: bool = True):
+    """``dsb_brics_fragment_records``: every BRICS fragment as a record of its own, with its attachment points (type byte 5, the label in the
+    charge byte).  ``first [P] i64``: the exclusive prefix sum of ``brics_records(...)[3][:, 2]``; ``rows``: the number of output rows F, the
+    total of that column (a row outside [0, F) is never written).  ``aromatic`` writes aromatic bonds as order 4 instead of their Kekule order.
+
+    -> the device tensors ``(out_rec [F, 1248] u8, out_n [F] i32, out_owner [F] i64, out_source [F, 29] u8)`` on the current stream without
+    synchronising; rows that no fragment is written to are zero (``out_source``: 0xff).  Checked, never converted; no CPU path."""
+    if not isinstance(aromatic, bool):
+        raise TypeError(f"aromatic must be a bool, got {type(aromatic).__name__}")
+    if isinstance(rows, bool) or not isinstance(rows, int):
+        raise TypeError(f"rows must be an int, got {type(rows).__name__}")
+    if rows < 0:
+        raise ValueError(f"rows must not be negative, got {rows}")
+    _want(rec, "rec", torch.uint8, (None, RECORD_BYTES))
+    _want(n, "n", torch.int32, (rec.shape[0],))
+    _want(first, "first", torch.int64, (rec.shape[0],))
+    tensors = [rec, n, first]
+    dev = rec.device
+    if dev.type != "cuda" or any(t.device != dev for t in tensors):
+        raise RuntimeError("brics_fragment_records needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    lib = load_library()
+    out = (torch.zeros(rows, RECORD_BYTES, dtype=torch.uint8, device=dev), torch.zeros(rows, dtype=torch.int32, device=dev),
+           torch.zeros(rows, dtype=torch.int64, device=dev), torch.full((rows, MAX_ATOMS), 0xff, dtype=torch.uint8, device=dev))
+    if rows and rec.shape[0]:                                                   # nothing to write otherwise, and an empty tensor has no address
+        with torch.cuda.device(dev):
+            st = lib.dsb_brics_fragment_records(ptr(rec), ptr(n), rec.shape[0], ptr(first), rows, int(aromatic), *(ptr(t) for t in out), _stream())
+        _check(st, "dsb_brics_fragment_records")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- canonical SMILES
 
 SMILES_CONSTS = abi.SMILES.consts         # include/diffspectra_smiles.h
@@ -1164,6 +1217,14 @@ class DmtEngine:
     def scaffold_masks(self, rec, n):
         """``engine.scaffold_masks`` on this engine's library (the scaffolds need no weights)."""
         return scaffold_masks(rec, n)
+
+    def brics_records(self, rec, n):
+        """``engine.brics_records`` on this engine's library (the BRICS analysis needs no weights)."""
+        return brics_records(rec, n)
+
+    def brics_fragment_records(self, rec, n, first, rows: int, aromatic: bool = True):
+        """``engine.brics_fragment_records`` on this engine's library."""
+        return brics_fragment_records(rec, n, first, rows, aromatic)
 
     def smiles_records(self, rec, n, max_nodes: int = 4096):
         """``engine.smiles_records`` on this engine's library (the strings need no weights)."""

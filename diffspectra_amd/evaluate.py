@@ -245,8 +245,8 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     the test table, ``nearest`` / ``nearest_index`` (device tensors: every kept generated molecule's similarity to, and the table row of, its
     nearest test molecule), ``n_generated`` / ``n_test`` and, when ``known_records = (records [*, 1248] u8, n_atoms [*])`` of the training
     molecules is given, ``novelty`` (``structure_metrics.get_set_similarity_metric``, which states the deviations: the MOSES definitions are
-    restated and unpinned, one representative per constitution-level class stands for ``set(smiles)``, no RDKit sanitisation filter; FCD and Frag
-    are not computed (Scaf: ``get_scaffold_metric``)).  Without the flag the dict has no such key.
+    restated and unpinned, one representative per constitution-level class stands for ``set(smiles)``, no RDKit sanitisation filter; FCD is
+    not computed (Scaf: ``get_scaffold_metric``, Frag: ``get_fragment_metric``)).  Without the flag the dict has no such key.
 
     With ``config.eval.scaffold`` true ``metrics['structure']['scaffold']`` is the "Scaf" number of the same line
     (``evaluation/mose_metric.py:111-113``): the dict of ``structure_metrics.get_scaffold_metric`` of the generated records against ALL records
@@ -257,6 +257,13 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     any -, ``undecided`` and, with K > 1, ``top_k`` with ``hit`` / ``first_hit`` / ``acc_at_k`` as ``topk_identity`` shapes them: a hit is any
     candidate of the target that shares its scaffold).  The scaffold rule restates RDKit's and MOSES's as remembered and is unpinned against
     both (``include/diffspectra_scaffold.h``).  Without the flag the dict has no such key.
+
+    With ``config.eval.fragments`` true ``metrics['structure']['fragments']`` is the "Frag" number of the same line
+    (``evaluation/mose_metric.py:88-128``): the dict of ``structure_metrics.get_fragment_metric`` of the generated records against ALL records of
+    the test table (``frag``, the cosine similarity of the BRICS fragment counts; ``n_generated`` / ``n_test``, ``fragments_*``, ``distinct_*``,
+    ``shared``, ``mean_cuts``, ``fragment_class`` with ``owner``).  The BRICS rules restate RDKit's and MOSES's as remembered and are unpinned against
+    both; the project's aromaticity, labelled-graph identity, no sanitisation filter (``include/diffspectra_brics.h``).  Without the flag the dict
+    has no such key.
 
     With ``config.eval.edm_metrics`` true ``metrics['structure']['metric_2d']`` and ``['metric_3d']`` are the reference's first two evaluation
     lines (``run_lib.py:371-387``): ``mol_stable``, ``atom_stable``, ``Validity``, ``Complete``, ``Unique`` and ``Novelty`` (against
@@ -331,6 +338,7 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     set_fn = None                                 # and so are the bit rows of the test molecules
     edm_fns = None
     scaffold_fn = None                            # and the scaffolds of the test molecules
+    fragment_fn = None                            # and their BRICS fragments
     for ckpt in checkpoint_ids(config):
         ckpt_path = os.path.join(workdir, "checkpoints", "checkpoint_{}.pth".format(ckpt))
         if not os.path.exists(ckpt_path):
@@ -374,6 +382,11 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                     scaffold_fn = get_scaffold_metric((test_ds.gt_records.to(run.records_by_slot.device), test_ds.num_atom), min_rings=min_rings,
                                                       engine=run.eng)
                 metrics["structure"]["scaffold"] = _scaffold_summary(run, test_ds, top_k, scaffold_fn, min_rings)
+            if getattr(config.eval, "fragments", False):
+                from .structure_metrics import get_fragment_metric
+                if fragment_fn is None:
+                    fragment_fn = get_fragment_metric((test_ds.gt_records.to(run.records_by_slot.device), test_ds.num_atom), engine=run.eng)
+                metrics["structure"]["fragments"] = fragment_fn((run.records_by_slot, torch.tensor(run.n_atoms)))
             if getattr(config.eval, "smiles", False):
                 metrics["structure"]["smiles"] = _smiles_summary(run, test_ds, top_k, getattr(config.eval, "smiles_path", None))
             if getattr(config.eval, "edm_metrics", False):

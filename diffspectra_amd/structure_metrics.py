@@ -40,7 +40,7 @@ fingerprints into bit rows (``dss_fold_bits``), ``nearest_neighbour_similarity``
 ``internal_diversity`` reduce it, ``novelty`` is ``graph_classes`` on the known and the generated molecules together.  The MOSES definitions
 (``SNNMetric``; ``internal_diversity`` with p = 1, self-pairs included; 1024-bit radius-2 Morgan fingerprints) are restated from the package as
 remembered - MOSES is neither vendored by the reference nor runnable here, so parity with it is unpinned - and the fingerprints carry the
-deviations of ``morgan_similarity_batch``.  FCD and Frag are not computed (Scaf: ``get_scaffold_metric``).
+deviations of ``morgan_similarity_batch``.  FCD is not computed (Scaf: ``get_scaffold_metric``, Frag: ``get_fragment_metric``).
 
 How the ring systems of a generated set stand against the test set's is ``get_scaffold_metric``: the "Scaf" number of the same line
 (``evaluation/mose_metric.py:111-113``), the cosine similarity of the Bemis-Murcko scaffold counts.  ``scaffolds`` gives the per-molecule
@@ -49,6 +49,14 @@ scaffold atoms, ring atoms and ring count (``dsk_scaffold_masks``, ``csrc/ds_sca
 Deviations: the scaffold rule (the 2-core of the heavy graph plus the atoms multiply bonded to it) restates RDKit's ``GetScaffoldForMol`` and
 MOSES's ``compute_scaffolds`` as remembered and is unpinned against both; scaffold identity is constitution-level on Kekule orders unless
 ``bond_orders=False``; there is no RDKit sanitisation filter.
+
+How the building blocks of a generated set stand against the test set's is ``get_fragment_metric``: the "Frag" number of the same line
+(``evaluation/mose_metric.py:88-128``), the cosine similarity of the BRICS fragment counts.  ``brics`` gives the per-molecule environments,
+cut bonds with their labels and fragments (``dsb_brics_records``, ``csrc/ds_brics.hip``; every definition in ``include/diffspectra_brics.h``),
+``brics_fragment_records`` every fragment as a record of its own with its attachment points.  Deviations: the environments and rules restate
+RDKit's ``BRICS.py`` and MOSES's ``compute_fragments`` as remembered and are unpinned against both; the project's aromaticity rule is used;
+fragment identity is that of the labelled graph, not of a SMILES string; there is no RDKit sanitisation filter; sulfur never occurs; a bond
+that fits a rule in both orientations gives both ends the rule's first label.
 
 Whether the generated molecules are chemically sound is ``get_edm_metric_2d`` / ``get_edm_metric_3d``: the reference's first two evaluation lines,
 "Metric-3D || atom stability, mol stability, validity, complete" and "Metric-2D || ..., unique & valid, unique & valid & novelty"
@@ -674,7 +682,7 @@ def get_set_similarity_metric(test, known=None, n_bits: int = 1024, unique: bool
 
     ``unique=True`` keeps one representative - the lowest row - of every ``graph_classes`` class on both sides, where the reference takes
     ``list(set(smiles))``.  ``keep`` is an optional bool mask over the generated rows (the device-side stability mask, say): the reference's own
-    filter is RDKit sanitisation, which is not reproduced.  FCD and Frag are not computed (Scaf: ``get_scaffold_metric``).  The MOSES definitions are restated from the
+    filter is RDKit sanitisation, which is not reproduced.  FCD is not computed (Scaf: ``get_scaffold_metric``, Frag: ``get_fragment_metric``).  The MOSES definitions are restated from the
     package as remembered and parity with MOSES is unpinned; identity is constitution-level (``graph_identity_batch``)."""
     from . import engine as E
     dev = test[0].device
@@ -1034,6 +1042,137 @@ def get_scaffold_metric(test, min_rings: int = 2, unique: bool = True, bond_orde
                     shared=int(((g_count > 0) & (t_count > 0)).sum()), scaffold_class=scaffold_class,
                     mean_rings=int(g_found.rings[usable].to(torch.int64).sum()) / n_usable if n_usable else float("nan"))
     return scaffold_metric
+
+
+# ------------------------------------------------------------------------------------------------------------------ BRICS fragments
+
+# The labels and the rules of include/diffspectra_brics.h: (x, y, bond order), in the order in which a bond takes its labels.  The sulfur
+# environments L11 and L12 and their six rules are left out: a record holds no sulfur.
+BRICS_LABELS = (1, 3, 4, 5, 6, 7, 8, 9, 10, 13, 14, 15, 16)
+BRICS_RULES = ((1, 3, 1), (1, 5, 1), (1, 10, 1),
+               (3, 4, 1), (3, 13, 1), (3, 14, 1), (3, 15, 1), (3, 16, 1),
+               (4, 5, 1),
+               (5, 14, 1), (5, 16, 1), (5, 13, 1), (5, 15, 1),
+               (6, 13, 1), (6, 14, 1), (6, 15, 1), (6, 16, 1),
+               (7, 7, 2),
+               (8, 9, 1), (8, 10, 1), (8, 13, 1), (8, 14, 1), (8, 15, 1), (8, 16, 1),
+               (9, 13, 1), (9, 14, 1), (9, 15, 1), (9, 16, 1),
+               (10, 13, 1), (10, 14, 1), (10, 15, 1), (10, 16, 1),
+               (13, 14, 1), (13, 15, 1), (13, 16, 1),
+               (14, 14, 1), (14, 15, 1), (14, 16, 1),
+               (15, 16, 1),
+               (16, 16, 1))
+
+
+class Brics(NamedTuple):
+    """Per-record device tensors of ``dsb_brics_records``."""
+    env: torch.Tensor             # [P, 29] i32: bit e = the atom is in BRICS environment L_e; 0 for a folded hydrogen and for atoms >= n
+    cuts: torch.Tensor            # [P, 28, 4] u8: (a, b, label of a, label of b) with a < b, ascending; unused rows 0xff
+    fragment_of: torch.Tensor     # [P, 29] u8: the fragment of every atom, 0xff for atoms >= n
+    summary: torch.Tensor         # [P, 4] i32: matchable atoms, cuts, fragments, atoms of the largest fragment with its hydrogens
+    status: torch.Tensor          # [P] u8: 0 ok, 3 unusable (n = 0, a type above 4, a bond byte above 3): cuts and fragment_of 0xff, the rest 0
+
+    @property
+    def usable(self) -> torch.Tensor:
+        return self.status == 0
+
+    @property
+    def n_cuts(self) -> torch.Tensor:
+        return self.summary[:, 1]
+
+    @property
+    def n_fragments(self) -> torch.Tensor:
+        return self.summary[:, 2]
+
+
+def brics(records: torch.Tensor, n_atoms, engine=None) -> Brics:
+    """The BRICS environments, cut bonds with their labels and fragments of every record of ``records [P, 1248] u8`` (GPU) in one launch of
+    ``dsb_brics_records`` (``csrc/ds_brics.hip``; every definition in ``include/diffspectra_brics.h``).  The environments and the rules restate
+    RDKit's ``BRICS.py`` as remembered and are unpinned against RDKit, which cannot be run here; they run on the hydrogen-folded graph of
+    ``substructure_search`` with the project's aromaticity; sulfur never occurs; a bond that fits a rule in both orientations gives both ends
+    the rule's first label.  Device tensors, no synchronisation."""
+    from . import engine as E
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    return Brics(*(engine if engine is not None else E).brics_records(records, n))
+
+
+def _brics_side(records, n, aromatic, engine):
+    """``(Brics, fragment records, their atom counts, owner, source)`` of a record table with ``n`` already ``[P] i32`` on the device: two
+    launches, a ``torch.cumsum`` on the device and one read of the total between them."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    found = Brics(*eng.brics_records(records, n))
+    counts = found.n_fragments.to(torch.int64)
+    ends = torch.cumsum(counts, 0)
+    total = int(ends[-1]) if counts.numel() else 0
+    return (found, *eng.brics_fragment_records(records, n, (ends - counts).contiguous(), total, aromatic))
+
+
+def brics_fragment_records(records: torch.Tensor, n_atoms, aromatic: bool = True, engine=None):
+    """``(frag_rec [F, 1248] u8, frag_n [F] i32, owner [F] i64, source [F, 29] u8)``: every BRICS fragment of every record as a record of its
+    own (``dsb_brics_fragment_records``), the fragments of record 0 first.  A fragment record holds the fragment's atoms in their original
+    order, hydrogens included, with applied charges, and then one attachment point per cut end: type byte 5, the BRICS label of the atom it
+    is attached to in the charge byte, the position of the atom across the cut.  ``aromatic=True`` writes aromatic bonds as order 4, so both
+    Kekule drawings of a ring give one fragment; ``False`` keeps the Kekule orders.  ``owner`` is the record a fragment comes from, ``source``
+    the original atom of every atom of the row (0xff beyond ``frag_n``).  Such records are outside the alphabet of the other analytics, which
+    call them unusable; ``graph_classes`` compares raw bytes and decides their identity.  One read of the fragment total sizes the output."""
+    n = torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+    return _brics_side(records, n, aromatic, engine)[1:]
+
+
+def get_fragment_metric(test, unique: bool = True, aromatic: bool = True, engine=None):
+    """The "Frag" number of the reference's set metrics (``evaluation/mose_metric.py:88-128``; MOSES's ``compute_fragments``, ``FragMetric`` and
+    ``cos_similarity``, restated from the package as remembered - parity with MOSES is unpinned) on record tensors: the cosine similarity of
+    the BRICS fragment counts of the generated and of the test molecules.  ``test`` is ``(records [*, 1248] u8 on the GPU, n_atoms [*])`` of the
+    test molecules, analysed once, here.  Returns ``fn(generated, keep=None)``, ``generated`` another such pair; ``keep`` and ``unique`` mean what
+    they mean in ``get_set_similarity_metric`` (one representative per ``graph_classes`` class of the MOLECULES).  ``fn`` gives a dict: ``frag`` (a
+    Python float: with g_k and t_k the numbers of FRAGMENTS of class k on each side - every occurrence counts, a molecule without a cut
+    contributes itself - ``sum g_k t_k / sqrt(sum g_k^2 * sum t_k^2)`` from exact integers; NaN when a side has no fragment), ``n_generated`` /
+    ``n_test`` (molecules that entered), ``fragments_generated`` / ``fragments_test``, ``distinct_generated`` / ``distinct_test`` / ``shared`` (numbers
+    of fragment classes), ``mean_cuts`` (a Python float over the usable generated rows that entered; NaN without any), ``fragment_class`` (i64
+    device tensor over the generated fragments: the row of the class's lowest member in the table "test fragments, then generated fragments")
+    and ``owner`` (i64: the generated row, among those that entered, that each of these fragments comes from).
+
+    Deviations: the BRICS rules are as remembered and unpinned against RDKit and MOSES; aromaticity is the project's rule; two fragments are the
+    same when ``graph_classes`` says so (the labelled graph with its attachment labels, not the SMILES) - with ``aromatic=False`` on Kekule
+    orders, so that two drawings of a ring are two fragments; there is no RDKit sanitisation filter (``keep=`` takes the caller's mask);
+    sulfur never occurs; a bond that fits a rule in both orientations gives both ends the rule's first label."""
+    import math
+    dev = test[0].device
+    i32 = lambda t, d: torch.as_tensor(t).to(device=d, dtype=torch.int32).reshape(-1).contiguous()
+
+    def side(rec, n):
+        """What was found in the rows that enter, and their fragment records."""
+        if unique:
+            rows = _class_representatives(rec, n, engine)
+            rec, n = rec[rows].contiguous(), n[rows].contiguous()
+        return _brics_side(rec, n, aromatic, engine)[:4]
+
+    t_found, t_rec, t_n, _ = side(test[0], i32(test[1], dev))
+    T = int(t_rec.shape[0])
+
+    def fragment_metric(generated, keep=None):
+        g_rec, g_n = generated[0], i32(generated[1], generated[0].device)
+        if keep is not None:
+            rows = torch.nonzero(torch.as_tensor(keep).to(g_rec.device).bool().reshape(-1)).reshape(-1)
+            g_rec, g_n = g_rec[rows].contiguous(), g_n[rows].contiguous()
+        g_found, f_rec, f_n, owner = side(g_rec, g_n)
+        G = int(f_rec.shape[0])
+        cls = graph_classes(torch.cat([t_rec.to(f_rec.device), f_rec]).contiguous(), torch.cat([t_n.to(f_n.device), f_n]).contiguous(), engine)
+
+        def count(ids):                                                          # fragments per class, at the class's own row
+            classes, members = torch.unique(ids, return_counts=True)
+            return torch.zeros(T + G, dtype=torch.int64, device=cls.device).index_put_((classes,), members)
+        t_count, g_count = count(cls[:T]), count(cls[T:])
+        dot, gg, tt = int((g_count * t_count).sum()), int((g_count * g_count).sum()), int((t_count * t_count).sum())
+        usable = g_found.usable
+        n_usable = int(usable.sum())
+        return dict(frag=dot / math.sqrt(gg * tt) if gg and tt else float("nan"), n_generated=int(g_found.status.shape[0]),
+                    n_test=int(t_found.status.shape[0]), fragments_generated=G, fragments_test=T, distinct_generated=int((g_count > 0).sum()),
+                    distinct_test=int((t_count > 0).sum()), shared=int(((g_count > 0) & (t_count > 0)).sum()),
+                    mean_cuts=int(g_found.n_cuts[usable].to(torch.int64).sum()) / n_usable if n_usable else float("nan"),
+                    fragment_class=cls[T:], owner=owner)
+    return fragment_metric
 
 
 # ------------------------------------------------------------------------------------------------------------------ canonical SMILES

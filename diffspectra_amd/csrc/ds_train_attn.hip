@@ -93,6 +93,13 @@ __device__ __forceinline__ int perm_index(int tile, int r, int c, int C) {
   const int s = r >> 4, r16 = r & 15, hh = (r16 >> 2) & 1, j = (r16 >> 3) * 4 + (r16 & 3);
   return ((((tile * 2 + s) * 2 + hh) * C + c) << 3) + j;
 }
+// acc + fp32(a * b): the product is ROUNDED before it is added (no fused multiply-add), so that adding a layer's contribution to a loaded
+// gradient (accumulate = 1) gives bit for bit the sum of the loaded value and what accumulate = 0 writes.
+__device__ __forceinline__ float add_product(float acc, float a, float b) {
+#pragma clang fp contract(off)
+  const float t = a * b;
+  return acc + t;
+}
 __device__ __forceinline__ unsigned short bf16_bits(float v) {
   const __bf16 b = (__bf16)v;
   return __builtin_bit_cast(unsigned short, b);
@@ -288,7 +295,7 @@ __global__ __launch_bounds__(SFA_NW * 64) void k_sfa_bwd_q(QkvPtrs qkv, int nl, 
         f32x4_t w = {0.0f, 0.0f, 0.0f, 0.0f};
         if (accumulate) w = *reinterpret_cast<f32x4_t*>(g);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] += scale * (j == 0 ? dq[e] : j == 1 ? dq[4 + e] : dq[8 + e]);
+        for (int e = 0; e < 4; ++e) w[e] = add_product(w[e], scale, j == 0 ? dq[e] : j == 1 ? dq[4 + e] : dq[8 + e]);
         *reinterpret_cast<f32x4_t*>(g) = w;
       }
   }
@@ -416,12 +423,20 @@ __global__ __launch_bounds__(SFA_NW * 64, SFA_K_MINB) void k_sfa_bwd_kv(QkvPtrs 
         f32x4_t u = {0.0f, 0.0f, 0.0f, 0.0f};
         if (accumulate) u = *reinterpret_cast<f32x4_t*>(g);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] += LN2 * (j == 0 ? dkc[e] : j == 1 ? dkc[4 + e] : dkc[8 + e]);   // Q^T carried scale * log2 e
+        for (int e = 0; e < 4; ++e) u[e] = add_product(u[e], LN2, j == 0 ? dkc[e] : j == 1 ? dkc[4 + e] : dkc[8 + e]);   // Q^T carried scale * log2 e
         *reinterpret_cast<f32x4_t*>(g) = u;
       }
     }
   }
 }
+
+// Dynamic LDS of the key-side backward, the largest of the three kernels: it must fit in 64 KB, which holds for L <= 384 (12 tiles: 62976
+// bytes; 13 tiles: 68224).  The forward applies the same condition: a tape the backward cannot consume is never produced.
+size_t sfa_bwd_kv_lds(int L) {
+  const int NT = (L + 31) / 32, LP = NT * 32;
+  return (size_t)(LP * KLD + NT * 4 * 32 * 8 + NT * 4 * DK * 8) * 2 + (size_t)LP * 4;
+}
+constexpr size_t SFA_LDS_MAX = 64 * 1024;
 
 }  // namespace
 
@@ -432,6 +447,7 @@ int dst_spec_attn_flash_fwd(const float* qkv0, const float* qkv1, const float* q
   if (n_layers < 1 || n_layers > 3 || !qkv0 || (n_layers > 1 && !qkv1) || (n_layers > 2 && !qkv2) || !stats || !out || B <= 0 || L <= 0 || L > 512 ||
       H * dk != DM || dk != DK)
     return DS_ERR_ARG;
+  if (sfa_bwd_kv_lds(L) > SFA_LDS_MAX) return DS_ERR_ARG;
   const int NT = (L + 31) / 32, LP = NT * 32;
   const size_t lds = (size_t)(LP * KLD + NT * 4 * DK * 8) * 2;
   QkvPtrs q{{qkv0, qkv1, qkv2}};
@@ -450,8 +466,8 @@ int dst_spec_attn_flash_bwd(const float* qkv0, const float* qkv1, const float* q
   GradPtrs g{{dqkv0, dqkv1, dqkv2}};
   hipStream_t s = (hipStream_t)stream;
   const size_t lds_q = (size_t)(LP * KLD + LP * DK + NT * 4 * 32 * 8) * 2;
-  const size_t lds_kv = (size_t)(LP * KLD + NT * 4 * 32 * 8 + NT * 4 * DK * 8) * 2 + (size_t)LP * 4;
-  if (lds_kv > 64 * 1024) return DS_ERR_ARG;
+  const size_t lds_kv = sfa_bwd_kv_lds(L);
+  if (lds_kv > SFA_LDS_MAX) return DS_ERR_ARG;
   if (part < 0 || part > 2) return DS_ERR_ARG;
   if (part != 2) hipLaunchKernelGGL(k_sfa_bwd_q<SFA_NW_Q>, dim3(B * H), dim3(SFA_NW_Q * 64), lds_q, s, q, (int)n_layers, stats, out, dout, g, (int)L, (int)H, scale, (int)(accumulate != 0));
   if (part != 1) hipLaunchKernelGGL(k_sfa_bwd_kv<SFA_NW_K>, dim3(B * H), dim3(SFA_NW_K * 64), lds_kv, s, q, (int)n_layers, stats, out, dout, g, (int)L, (int)H, scale, (int)(accumulate != 0));

@@ -248,7 +248,9 @@ int dst_spec_attn_bwd(const float* qkv, const float* scores, const float* stats,
  * gradient to the q and k columns of dqkv0 .. dqkv(l) (the gradient the reference chains through `prev`) and writes the v columns of
  * dqkv(l).  The caller runs the layers last to first: accumulate = 0 for the FIRST call (the last layer: it ASSIGNS the q and k columns of
  * every buffer, which therefore need no zeroing and are not read), 1 for the others.  part: 0 = the whole backward; 1 = the query side
- * (q columns) only, 2 = the key side (k and v columns) only - the two touch disjoint columns and may run on two streams. */
+ * (q columns) only, 2 = the key side (k and v columns) only - the two touch disjoint columns and may run on two streams.
+ * Limits: H = 16, dk = 8, L <= 384 (the key-side backward keeps its tables of ceil(L / 32) tiles in 64 KB of LDS); BOTH entry points
+ * return DS_ERR_ARG beyond that and write nothing. */
 int dst_spec_attn_flash_fwd(const float* qkv0, const float* qkv1, const float* qkv2, int32_t n_layers, float* stats, float* out, int32_t B,
                             int32_t L, int32_t H, int32_t dk, float scale, void* stream);
 int dst_spec_attn_flash_bwd(const float* qkv0, const float* qkv1, const float* qkv2, int32_t n_layers, const float* stats, const float* out,

@@ -25,6 +25,17 @@ def _bn_eval(sd, name, x):
                         sd[name + ".weight"], sd[name + ".bias"], training=False, eps=1e-5).transpose(1, 2)
 
 
+def residual_attention(q, k_t, v, scale, prev=None):
+    """The residual-score attention of one layer (:401-404,418-424): q, v [B,H,L,dk], k_t [B,H,dk,L], prev = the previous layer's
+    pre-softmax scores [B,H,L,L] or None → (output [B,L,H*dk] in front of to_out, this layer's pre-softmax scores)."""
+    scores = torch.matmul(q, k_t) * scale                                                       # :401
+    if prev is not None:
+        scores = scores + prev                                                                  # :404
+    attn = F.softmax(scores, dim=-1)                                                            # :418
+    B, n_heads, L, dk = q.shape
+    return torch.matmul(attn, v).transpose(1, 2).contiguous().view(B, L, n_heads * dk), scores  # :422,365
+
+
 def specformer_forward(sd, spectra, spectra_version="allspectra", patch_len=(20, 50, 50),
                        stride=(10, 25, 25), prefix="cond_encoder.", n_layers=3, n_heads=16):
     """spectra: list [uv, ir, raman] of [B,1,L] (allspectra) or one [B,1,L] tensor → [B, 256]."""
@@ -50,13 +61,8 @@ def specformer_forward(sd, spectra, spectra_version="allspectra", patch_len=(20,
         q = _lin(sd, base + "self_attn.W_Q", z).view(B, L, n_heads, dk).transpose(1, 2)        # :353
         k = _lin(sd, base + "self_attn.W_K", z).view(B, L, n_heads, dk).permute(0, 2, 3, 1)    # :354
         v = _lin(sd, base + "self_attn.W_V", z).view(B, L, n_heads, dk).transpose(1, 2)        # :355
-        scores = torch.matmul(q, k) * sd[base + "self_attn.sdp_attn.scale"]                    # :401
-        if prev is not None:
-            scores = scores + prev                                                              # :404
-        attn = F.softmax(scores, dim=-1)                                                        # :418
-        o = torch.matmul(attn, v).transpose(1, 2).contiguous().view(B, L, n_heads * dk)         # :422,365
+        o, prev = residual_attention(q, k, v, sd[base + "self_attn.sdp_attn.scale"], prev)
         o = _lin(sd, base + "self_attn.to_out.0", o)                                            # :366
-        prev = scores
         z = _bn_eval(sd, base + "norm_attn.1", z + o)                                           # :292-294
         f = _lin(sd, base + "ff.3", F.gelu(_lin(sd, base + "ff.0", z)))                         # :300
         z = _bn_eval(sd, base + "norm_ffn.1", z + f)                                            # :302-304

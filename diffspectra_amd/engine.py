@@ -62,6 +62,7 @@ def load_library() -> C.CDLL:
     abi.SUBSTRUCTURE.bind(lib)
     abi.STEREO.bind(lib)
     abi.BRICS.bind(lib)
+    abi.MOBILE.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
     sizes = (C.c_int64 * 4)()
@@ -471,7 +472,7 @@ def graph_identity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: 
                            ref_index: Optional[torch.Tensor] = None, max_nodes: int = 4096):
     """``ds_graph_identity_records``: is the generated molecule of each of P pairs the SAME labelled graph (atom type, formal charge, bond
     order) as its ground truth, whatever the conformation - constitution-level identity, not InChIKey identity (no stereo layer, no
-    tautomer / charge normalisation; see the header).
+    tautomer / charge normalisation: ``normal_records`` rewrites the records for that; see the header).
 
     The tensors are those of ``match_records``.  Returns the device tensors ``(verdict [P] u8, nodes [P] i32, map [P, 29] i32)``, enqueued on
     the current stream without synchronising: verdict ``GRAPH_IDENTICAL`` (1: ``map`` is a checked isomorphism), ``GRAPH_DIFFERENT`` (0: proven),
@@ -907,6 +908,54 @@ def brics_fragment_records(rec: torch.Tensor, n: torch.Tensor, first: torch.Tens
     return out
 
 
+# ----------------------------------------------------------------------------------------- mobile hydrogens and the normal form
+
+MOBILE_CONSTS = abi.MOBILE.consts         # include/diffspectra_mobile.h
+MOBILE_OK, MOBILE_UNDECIDED, MOBILE_UNUSABLE, MOBILE_OVERFLOW = (MOBILE_CONSTS["DSM_" + k] for k in ("OK", "UNDECIDED", "UNUSABLE", "OVERFLOW"))
+MOBILE_MAX_NODES, MOBILE_MAX_GROUPS = MOBILE_CONSTS["DSM_MAX_NODES"], MOBILE_CONSTS["DSM_MAX_GROUPS"]
+MOBILE_GROUP_TYPE, MOBILE_PROTON_TYPE = MOBILE_CONSTS["DSM_GROUP_TYPE"], MOBILE_CONSTS["DSM_PROTON_TYPE"]
+MOBILE_DEFAULT_NODES = 4096               # far above what a molecule of 29 atoms spends
+
+
+def _mobile_budget(max_nodes):
+    if max_nodes is None:
+        return MOBILE_DEFAULT_NODES
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, int):
+        raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
+    if not 1 <= max_nodes <= MOBILE_MAX_NODES:
+        raise ValueError(f"max_nodes must lie in [1, {MOBILE_MAX_NODES}], got {max_nodes}")
+    return max_nodes
+
+
+def mobile_records(rec: torch.Tensor, n: torch.Tensor, max_nodes: Optional[int] = None):
+    """``dsm_mobile_records``: the mobile-hydrogen groups, fixed hydrogens, residual charges and proton balance of every record (every
+    definition in ``include/diffspectra_mobile.h``: a restatement of InChI's mobile-H and (de)protonation normalisation as remembered, unpinned
+    against InChI).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(fixed_h [P, 29] u8, q_res [P, 29] i8, group_of [P, 29] u8, group_h [P, 14] u8,
+    summary [P, 4] i32, nodes [P] i32, status [P] u8)`` on the current stream without synchronising: ``fixed_h`` is 0xff for a folded hydrogen
+    and for atoms >= n and 0 for a group member; ``group_of`` and ``group_h`` are 0xff where there is no group; ``summary`` is (kept atoms, groups,
+    mobile H in all, proton balance); status ``MOBILE_UNUSABLE`` (3) or ``MOBILE_UNDECIDED`` (2: the path search needed more than ``max_nodes``,
+    default 4096) makes the three byte outputs 0xff and zeroes the rest.  Checked, never converted; no CPU path."""
+    i8 = (torch.uint8, (MAX_ATOMS,))
+    return _record_call("mobile_records", [(rec, n)], None, [_mobile_budget(max_nodes)],
+                        [i8, (torch.int8, (MAX_ATOMS,)), i8, (torch.uint8, (MOBILE_MAX_GROUPS,)), (torch.int32, (4,)), (torch.int32, ()), (torch.uint8, ())],
+                        prefix="dsm_")
+
+
+def normal_records(rec: torch.Tensor, n: torch.Tensor, max_nodes: Optional[int] = None):
+    """``dsm_normal_records``: every record in the normal form of ``include/diffspectra_mobile.h`` - kept atoms with charge byte ``fixed H +
+    16 * (q_res + 1)``, every bond as byte 1, one group node (type byte 6, the mobile H in the charge byte) bonded to the members of every
+    mobile group and a proton node (type byte 7, the balance in the charge byte) when the balance is not 0 - so that ``graph_identity_records``
+    and ``graph_hash_records`` on the rows decide identity up to tautomers, acid / base forms and Kekule drawings.
+
+    -> the device tensors ``(out_rec [P, 1248] u8, out_n [P] i32, out_source [P, 29] u8, status [P] u8)`` on the current stream without
+    synchronising; a row whose status is not ``MOBILE_OK`` (``MOBILE_OVERFLOW`` = 4: more than 29 nodes) is zero with ``out_n`` 0 and
+    ``out_source`` 0xff.  Checked, never converted; no CPU path."""
+    return _record_call("normal_records", [(rec, n)], None, [_mobile_budget(max_nodes)],
+                        [(torch.uint8, (RECORD_BYTES,)), (torch.int32, ()), (torch.uint8, (MAX_ATOMS,)), (torch.uint8, ())], prefix="dsm_")
+
+
 # ----------------------------------------------------------------------------------------- canonical SMILES
 
 SMILES_CONSTS = abi.SMILES.consts         # include/diffspectra_smiles.h
@@ -1225,6 +1274,14 @@ class DmtEngine:
     def brics_fragment_records(self, rec, n, first, rows: int, aromatic: bool = True):
         """``engine.brics_fragment_records`` on this engine's library."""
         return brics_fragment_records(rec, n, first, rows, aromatic)
+
+    def mobile_records(self, rec, n, max_nodes: Optional[int] = None):
+        """``engine.mobile_records`` on this engine's library (the mobile-hydrogen analysis needs no weights)."""
+        return mobile_records(rec, n, max_nodes)
+
+    def normal_records(self, rec, n, max_nodes: Optional[int] = None):
+        """``engine.normal_records`` on this engine's library."""
+        return normal_records(rec, n, max_nodes)
 
     def smiles_records(self, rec, n, max_nodes: int = 4096):
         """``engine.smiles_records`` on this engine's library (the strings need no weights)."""

@@ -157,6 +157,22 @@ def _stereo_summary(run, table, top_k: int, min_volume: Optional[float] = None, 
     return entry
 
 
+def _mobile_summary(run, table, top_k: int, max_nodes: int = 4096) -> Dict:
+    """Top-1 / Top-K up to mobile hydrogens, acid / base forms and Kekule drawings of one finished run (the pairs of ``_structure_summary``):
+    ``mobile_identity_batch`` per slot."""
+    from .structure_metrics import mobile_identity_batch, topk_identity
+    dev = run.records_by_slot.device
+    ref, prb = (table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms))
+    same = mobile_identity_batch(ref, prb, ref_index=run.slot_ds, max_nodes=max_nodes, engine=run.eng)
+    P = same.verdict.numel()
+    rate = lambda hit: float(hit.double().mean()) if P else 0.0
+    entry = dict(verdict=same.verdict, layer=same.layer, identity_rate=rate(same.identical), strict_rate=rate(same.strict == 1),
+                 normalised_hits=int((same.layer == 1).sum()), undecided=int(same.undecided.sum()), invalid=int((same.verdict == 3).sum()))
+    if top_k > 1:
+        entry["top_k"] = topk_identity(same.verdict, top_k)
+    return entry
+
+
 def _scaffold_summary(run, table, top_k: int, scaffold_fn, min_rings: int) -> Dict:
     """The "Scaf" number of one finished run against the test table (``scaffold_fn``: ``get_scaffold_metric`` of its records) and, over the
     pairs of ``_structure_summary``, whether every generated molecule shares the scaffold of its ground truth."""
@@ -219,7 +235,7 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     accuracy over all slots), ``undecided`` (pairs whose search ran out of budget; they count as misses), ``unique_fraction`` of the
     generated records (``graph_classes``) and, with K > 1, ``top_k = topk_identity(...)`` whose ``acc_at_k`` is the Top-K accuracy.  Identity
     is constitution-level (atom type, formal charge, bond order): unlike the reference's InChIKey comparison (``compute_metrics.py:222-230``)
-    it has no stereo layer and no InChI normalisation of tautomers or charges.
+    it has no stereo layer and no InChI normalisation of tautomers or charges (``config.eval.mobile_identity`` below adds the latter).
     ``metrics['structure']['mces']`` grades the misses: ``dist`` / ``status`` (device tensors of ``ds_mces_records``: the exact
     maximum-common-edge-subgraph distance of every slot's molecule from its ground truth on heavy atoms, bond weight = bond order; status 0
     exact, 2 undecided = ``dist`` is an upper bound, 3 invalid), ``mean`` over the valid pairs (the reference's "MCES (Average)",
@@ -301,6 +317,15 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     0.5; they are definitions, nobody has measured how generated molecules distribute around them.  Four-coordinate centres and double bonds
     only, no InChI normalisation, parity with RDKit / InChI unpinned (``include/diffspectra_stereo.h``).  Without the flag the dict has no such key.
 
+    With ``config.eval.mobile_identity`` true ``metrics['structure']['mobile']`` is Top-1 up to mobile hydrogens (tautomers), acid / base forms
+    and Kekule drawings (``structure_metrics.mobile_identity_batch``: ``graph_identity_batch`` on the normal forms of ``dsm_normal_records``;
+    the level of the main layer of the standard InChI behind the reference's Top-1, ``compute_metrics.py:222-230``): ``verdict`` (u8 device
+    tensor, one per slot: 0 different, 1 identical, 2 undecided, 3 invalid), ``layer`` (i8: 0 identical as drawn, 1 identical only after the
+    normalisation, -1 not identical), ``identity_rate`` (verdict 1 over all slots), ``strict_rate`` (what ``graph`` calls identical),
+    ``normalised_hits`` (the slots with layer 1), ``undecided`` and ``invalid`` (counts) and, with K > 1, ``top_k = topk_identity(verdict, K)``.
+    ``config.eval.mobile_max_nodes`` replaces the budget of 4096.  The rule restates InChI's as remembered and is unpinned against it; the
+    stereo layer is not combined with it (``include/diffspectra_mobile.h``).  Without the flag the dict has no such key.
+
     With ``config.eval.smiles`` true ``metrics['structure']['smiles']`` holds the molecules as text, where the reference calls ``Chem.MolToSmiles``
     (``run_lib.py:111-112``, ``compute_metrics.py:73-78,209-220``; ``dsl_smiles_records``): ``generated`` (one canonical SMILES string per slot,
     ``None`` for an overflow or unusable record), ``ground_truth`` (the string of every slot's ground truth), ``same`` / ``status`` / ``pair_status``
@@ -363,6 +388,8 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
             if getattr(config.eval, "stereo", False):
                 metrics["structure"]["stereo"] = _stereo_summary(run, test_ds, top_k, getattr(config.eval, "stereo_min_volume", None),
                                                                  getattr(config.eval, "stereo_min_planarity", None))
+            if getattr(config.eval, "mobile_identity", False):
+                metrics["structure"]["mobile"] = _mobile_summary(run, test_ds, top_k, int(getattr(config.eval, "mobile_max_nodes", 4096)))
             if getattr(config.eval, "sub_geometry", False):
                 from .structure_metrics import get_sub_geometry_metric
                 if geometry_fn is None:

@@ -13,7 +13,7 @@ The accuracy itself - is a generated molecule THE ground-truth molecule - is ``g
 conformation-independent decision per pair by ``ds_graph_identity_records`` (``csrc/ds_graph.hip``), and ``graph_classes`` gives the
 uniqueness figure of ``evaluation/rdkit_metric.py`` from a permutation-invariant hash plus the same decision.  Identity here is
 constitution-level (atom type, formal charge, bond order under a bijection, whole molecules): it is NOT InChIKey identity - no stereo
-layer, no InChI normalisation of tautomers or charges.
+layer, no InChI normalisation of tautomers or charges (``mobile_identity_batch`` compares at that level).
 
 How far a wrong molecule is from the right one is ``mces_batch`` / ``topk_mces``: the exact maximum-common-edge-subgraph distance per pair by
 ``ds_mces_records`` (``csrc/ds_mces.hip``), the reference's "MCES (Average)" (``compute_metrics.py:235-243``: one ``myopic_mces`` ILP per
@@ -235,8 +235,8 @@ class GraphIdentity(NamedTuple):
 
 
 def graph_identity_batch(ref, prb, ref_index=None, max_nodes: int = 4096, engine=None) -> GraphIdentity:
-    """Constitution-level identity (atom type, formal charge, bond order; no stereo, no tautomer / charge normalisation - not InChIKey
-    identity) of every generated molecule with its ground truth, independent of the conformation.  ``ref`` and ``prb`` are ``(records
+    """Constitution-level identity (atom type, formal charge, bond order; no stereo - ``stereo_identity_batch`` -, no tautomer / charge
+    normalisation - ``mobile_identity_batch`` -: not InChIKey identity) of every generated molecule with its ground truth, independent of the conformation.  ``ref`` and ``prb`` are ``(records
     [*, 1248] u8, n_atoms [*])`` pairs on the GPU, ground truth first as in ``hungarian_rmsd_batch``; ``ref_index [P]`` names the ground-truth
     row of every generated molecule (``None``: row p).  Device tensors, no synchronisation."""
     return GraphIdentity(*_pair_call("graph_identity_records", engine, ref, prb, ref_index, max_nodes))
@@ -1481,3 +1481,123 @@ def chirality(records: torch.Tensor, n_atoms, max_nodes: int = 4096, min_volume:
     decided = own.verdict == 1
     chiral = torch.where(decided, ((own.sites[:, 0] > 0) & (own.found[:, 2] == 0)).to(torch.uint8), torch.full_like(own.verdict, 2))
     return Chirality(chiral, torch.where(own.verdict == 2, torch.full_like(own.found[:, 0], -1), own.found[:, 0]))
+
+
+# ------------------------------------------------------------------------------------------------------------------ mobile hydrogens, the normal form
+
+class MobileHydrogens(NamedTuple):
+    """Per-record device tensors of ``dsm_mobile_records``."""
+    fixed_h: torch.Tensor         # [P, 29] u8: fixed H of every kept atom (0 for a group member); 0xff for a folded hydrogen and for atoms >= n
+    q_res: torch.Tensor           # [P, 29] i8: residual charge after the (de)protonation rule
+    group_of: torch.Tensor        # [P, 29] u8: the mobile group of every member, 0xff elsewhere
+    group_h: torch.Tensor         # [P, 14] u8: mobile H of every group, 0xff where unused
+    summary: torch.Tensor         # [P, 4] i32: kept atoms, groups, mobile H in all, proton balance
+    nodes: torch.Tensor           # [P] i32 search nodes used
+    status: torch.Tensor          # [P] u8: 0 ok, 2 undecided (budget), 3 unusable: the byte outputs 0xff, the rest 0
+
+    @property
+    def ok(self) -> torch.Tensor:
+        return self.status == 0
+
+    @property
+    def n_groups(self) -> torch.Tensor:
+        return self.summary[:, 1]
+
+    @property
+    def proton_balance(self) -> torch.Tensor:
+        return self.summary[:, 3]
+
+
+class MobileIdentity(NamedTuple):
+    """Per-pair device tensors of ``mobile_identity_batch``."""
+    verdict: torch.Tensor         # [P] u8: 1 identical in the normal form, 0 different, 2 undecided (a budget, or a normal form over 29 nodes), 3 invalid
+    strict: torch.Tensor          # [P] u8: the verdict of ``graph_identity_batch`` on the records as drawn
+    layer: torch.Tensor           # [P] i8: 0 identical as drawn, 1 identical only in the normal form, -1 not identical
+    map: torch.Tensor             # [P, 29] i32: ground-truth kept atom of every generated kept atom when identical, else -1
+    prb_status: torch.Tensor      # [P] u8 status of the generated record's normal form (0 ok, 2 undecided, 3 unusable, 4 overflow)
+    ref_status: torch.Tensor      # [P] u8 the same of its ground truth (3 for an invalid row)
+    nodes: torch.Tensor           # [P] i32 search nodes of the comparison of the normal forms
+
+    @property
+    def identical(self) -> torch.Tensor:
+        return self.verdict == 1
+
+    @property
+    def undecided(self) -> torch.Tensor:
+        return self.verdict == 2
+
+
+def _i32_on(records, n_atoms):
+    return torch.as_tensor(n_atoms).to(device=records.device, dtype=torch.int32).contiguous()
+
+
+def mobile_hydrogens(records: torch.Tensor, n_atoms, max_nodes: Optional[int] = None, engine=None) -> MobileHydrogens:
+    """The mobile-hydrogen groups (tautomers), fixed hydrogens, residual charges and proton balance of every record of ``records [P, 1248] u8``
+    (GPU) in one launch of ``dsm_mobile_records`` (``csrc/ds_mobile.hip``; every definition in ``include/diffspectra_mobile.h``).  The rule
+    restates InChI's mobile-H and (de)protonation normalisation as remembered and is unpinned against InChI, which cannot be run here.
+    ``max_nodes``: the budget of the path search per record (``None``: 4096).  Device tensors, no synchronisation."""
+    from . import engine as E
+    return MobileHydrogens(*(engine if engine is not None else E).mobile_records(records, _i32_on(records, n_atoms), max_nodes))
+
+
+def normal_form_records(records: torch.Tensor, n_atoms, max_nodes: Optional[int] = None, engine=None):
+    """``(out_rec [P, 1248] u8, out_n [P] i32, out_source [P, 29] u8, status [P] u8)``: every record in the normal form of
+    ``include/diffspectra_mobile.h`` (``dsm_normal_records``), row p for record p: the kept atoms with their fixed hydrogens and residual
+    charge in the charge byte, every bond as byte 1, a group node per mobile group, a proton node for a balance that is not 0.  ``out_source``
+    is the original atom of every kept atom of the row.  Such records are outside the alphabet of the other analytics; ``graph_classes`` and
+    ``graph_identity_batch`` compare raw bytes and decide their identity.  A row whose status is not 0 is empty.  No synchronisation."""
+    from . import engine as E
+    return (engine if engine is not None else E).normal_records(records, _i32_on(records, n_atoms), max_nodes)
+
+
+def mobile_identity_batch(ref, prb, ref_index=None, max_nodes: int = 4096, engine=None) -> MobileIdentity:
+    """Identity of every generated molecule with its ground truth up to mobile hydrogens (tautomers), acid / base forms and Kekule drawings:
+    ``graph_identity_batch`` on the normal forms of ``normal_form_records`` - the level of the main layer of the standard InChI behind the
+    reference's Top-1 (``compute_metrics.py:222-230``), with the deviations ``include/diffspectra_mobile.h`` states (the rule is unpinned
+    against InChI; the stereo layer of ``stereo_identity_batch`` is not combined with it).  ``ref`` and ``prb`` are ``(records [*, 1248] u8,
+    n_atoms [*])`` pairs on the GPU, ground truth first; ``ref_index [P]`` names the ground-truth row of every generated molecule (``None``:
+    row p); ``max_nodes`` is the budget of the path searches and of both graph comparisons.  A pair with an unusable side is invalid (3), a
+    pair with a side whose search ran out of its budget or whose normal form has more than 29 nodes is undecided (2).  ``topk_identity``
+    works on ``verdict`` unchanged.  Device tensors, no synchronisation."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
+    dev = prb_rec.device
+    ref_n, prb_n = _i32_on(ref_rec, ref_n), _i32_on(prb_rec, prb_n)
+    P, M = prb_rec.shape[0], ref_rec.shape[0]
+    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=dev, dtype=torch.int64).contiguous()
+    compare = min(max_nodes, E.GRAPH_MAX_NODES) if isinstance(max_nodes, int) else max_nodes      # (the bindings check the type)
+    strict = eng.graph_identity_records(prb_rec, prb_n, ref_rec, ref_n, idx, compare)[0]
+    p_rec, p_n, p_src, p_st = eng.normal_records(prb_rec, prb_n, max_nodes)
+    r_rec, r_n, r_src, r_st = eng.normal_records(ref_rec, ref_n, max_nodes)
+    verdict, nodes, image = eng.graph_identity_records(p_rec, p_n, r_rec, r_n, idx, compare)
+    rows = torch.arange(P, device=dev) if idx is None else idx
+    inside = (rows >= 0) & (rows < M)
+    safe = torch.where(inside, rows, torch.zeros_like(rows))
+    unusable, ok = E.MOBILE_UNUSABLE, E.MOBILE_OK
+    ref_status = torch.where(inside, r_st[safe] if M else torch.zeros_like(p_st), torch.full_like(p_st, unusable))
+    not_ok = (p_st != ok) | (ref_status != ok)
+    invalid = (verdict == E.GRAPH_INVALID) | (p_st == unusable) | (ref_status == unusable)
+    verdict = torch.where(invalid, torch.full_like(verdict, E.GRAPH_INVALID), torch.where(not_ok, torch.full_like(verdict, E.GRAPH_UNDECIDED), verdict))
+    same = verdict == E.GRAPH_IDENTICAL
+    layer = torch.where(same, (strict != E.GRAPH_IDENTICAL).to(torch.int8), torch.full((P,), -1, dtype=torch.int8, device=dev))
+    # the map between normal-form rows, translated to original kept atoms on both sides
+    out = torch.full((P, p_src.shape[1]), -1, dtype=torch.int32, device=dev)
+    if P and M:
+        target = r_src[safe].gather(1, image.clamp(min=0).to(torch.int64)).to(torch.int32)       # the original ground-truth atom of every row atom
+        kept = same.unsqueeze(1) & (p_src != 0xff)
+        p_at, slot = kept.nonzero(as_tuple=True)
+        out[p_at, p_src[p_at, slot].to(torch.int64)] = target[p_at, slot]
+    return MobileIdentity(verdict, strict, layer, out, p_st, ref_status, nodes)
+
+
+def mobile_classes(records: torch.Tensor, n_atoms, max_nodes: Optional[int] = None, engine=None) -> torch.Tensor:
+    """``class_id [P] i64``: the lowest row whose molecule has the same normal form as row p's - ``graph_classes`` on the normal forms, for
+    uniqueness and novelty up to tautomers, acid / base forms and Kekule drawings.  A row without a normal form (unusable, undecided or
+    over 29 nodes) is a class of its own.  One read of the statuses."""
+    out_rec, out_n, _, status = normal_form_records(records, n_atoms, max_nodes, engine)
+    class_id = torch.arange(records.shape[0], dtype=torch.int64, device=records.device)
+    rows = (status == 0).nonzero(as_tuple=True)[0]
+    if rows.numel():
+        class_id[rows] = rows[graph_classes(out_rec[rows].contiguous(), out_n[rows].contiguous(), engine)]
+    return class_id

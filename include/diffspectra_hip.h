@@ -333,7 +333,7 @@ int ds_match_records(const uint8_t* prb_rec, const int32_t* prb_n, int64_t P, co
  * counts are different; two 0-atom molecules are identical with an empty map.
  *   This is identity of the CONSTITUTION.  It is not InChIKey identity, which the reference compares (compute_metrics.py:222-230): there is
  *   no stereo layer (enantiomers and E/Z isomers are identical here) and no InChI normalisation (two tautomers, or two ways of writing a
- *   charge-separated group, are different here).
+ *   charge-separated group, are different here; dsm_normal_records of diffspectra_mobile.h rewrites a record so that they are not).
  * Method: individualisation-refinement.  Colour = joint rank of (type, charge) over both molecules; a refinement round ranks, again jointly,
  * (own colour, multiset of (bond order, neighbour colour) over the bonded neighbours) until the number of classes stops growing.  Differing
  * colour histograms prove the graphs different; all classes singletons leaves one candidate bijection, which is verified byte by byte;

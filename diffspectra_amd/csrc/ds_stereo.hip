@@ -4,14 +4,14 @@
 // site, what an isomorphism does to a site, the verdicts); DESIGN.md section 21 has the method, the soundness of the twin rule and the figures.
 //
 // One wave64 per pair, one wave per workgroup: the generated molecule in lanes 0..28, the ground truth in lanes 32..60, as k_graph_identity
-// (ds_graph.hip), whose search this is - the joint colour refinement of ds_refine.h with depth-first individualisation - with two changes:
-// the initial colour also holds the twin ordinal, and the search goes on after a verified leaf, so that it meets every ordinal-respecting
-// isomorphism exactly once (every isomorphism sends the individualised atom to exactly one atom of its class).  perceive() is the prologue,
-// run per half wave: twins, ordinals and the site bits in fp64, a site per lane.  After it the kernel is integers only; no atomics.
+// (ds_graph.hip).  k_stereo_identity calls the pair search of ds_refine.h, where the argument for it stands, and adds two things: the
+// initial colour and the leaf's labels also hold the twin ordinal, and the search goes on after a verified leaf, so that it meets every
+// ordinal-respecting isomorphism exactly once.  perceive() is the prologue, run per half wave: twins, ordinals and the site bits in fp64, a
+// site per lane.  After it the kernel is integers only; no atomics.
 //
-// Soundness, in the lines the code keeps true: a leaf counts only after verify() has compared every type, charge, ordinal and bond byte under
-// an explicit bijection; DSC_DIFFERENT needs an exhausted search without such a leaf; DSC_MIRROR / DSC_STEREOISOMER need an exhausted search,
-// so that no same phi was missed; a search the budget stops is DSC_UNDECIDED whatever it had found.
+// Soundness, in the lines the code keeps true: a leaf counts only after ds_refine::verify() has compared every type, charge, ordinal and bond
+// byte under an explicit bijection; DSC_DIFFERENT needs an exhausted search without such a leaf; DSC_MIRROR / DSC_STEREOISOMER need an
+// exhausted search, so that no same phi was missed; a search the budget stops is DSC_UNDECIDED whatever it had found.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -23,8 +23,6 @@
 namespace {
 
 using ds_rec::MA;
-using ds_rec::uniform_i;
-constexpr int FRESH = 63;                 // colour of an individualised atom: ranks stay below 2 * 29 = 58
 constexpr unsigned ALL = ~0u;             // keep mask of ds_rec::load_bonds: every atom (the rows are read up to n only)
 
 __device__ __forceinline__ unsigned half_of(unsigned long long ballot, int side) { return (unsigned)(ballot >> (32 * side)); }
@@ -39,9 +37,9 @@ struct Geometry {                         // what the prologue stages of both mo
 struct Pair : Geometry {
   unsigned char type[64], fc[64], ord[64];
   unsigned long long sig[64], f[64];      // signatures being ranked; per-atom colour hash of the running round
-  unsigned char stack[MA][64];            // colours (ranks below 64) of every open level of the search, before its individualisation
-  int cell[MA], atom[MA], cursor[MA];     // per level: the class that is split, its generated atom, the next ground-truth atom to try
-  unsigned char inv[64], img[32];         // leaf: ground-truth atom of a colour; image of every generated atom
+  unsigned char stack[MA][64];            // the pair search's fields, as ds_refine.h names them
+  int cell[MA], atom[MA], cursor[MA];
+  unsigned char inv[64], img[32];
   unsigned char positive[64], cis[64], low[64];   // the site bits a leaf is tested against: sign of a centre, cis bit and lowest substituent of an end
   __device__ __forceinline__ const unsigned char* bonds(int side) const { return adj[side]; }
 };
@@ -170,31 +168,6 @@ using ds_refine::DISCRETE;
 using ds_refine::CELLS;
 constexpr ds_refine::Block SYNC{};        // one wave per workgroup: the workgroup barrier orders the pair's LDS traffic
 
-// Leaf of the search, as in ds_graph.hip with the ordinal added: every colour names one atom per side, which is the only bijection this
-// branch allows.  It is checked in full before it counts.  Leaves S.img = the map.
-__device__ bool verify(Pair& S, int colour, bool active, int n, int lane) {
-  const int idx = lane & 31;
-  const bool left = active && lane < 32, right = active && lane >= 32;
-  if (right) S.inv[colour] = (unsigned char)idx;
-  __syncthreads();
-  int m = 0;
-  if (left) { m = S.inv[colour] & 31; S.img[idx] = (unsigned char)m; }   // (& 31: an index inside the arrays whatever LDS held)
-  __syncthreads();
-  bool bad = false;
-  if (left) {
-    bad = m >= n || S.type[lane] != S.type[32 + m] || S.fc[lane] != S.fc[32 + m] || S.ord[lane] != S.ord[32 + m];
-    if (!bad)
-      for (int j = 0; j < n; ++j) bad |= S.adj[0][j * 32 + idx] != S.adj[1][S.img[j] * 32 + m];
-  }
-  if (right) {
-    int hits = 0;
-    for (int j = 0; j < n; ++j) hits += S.img[j] == idx;
-    bad = hits != 1;
-  }
-  __syncthreads();
-  return __ballot(bad) == 0ull;
-}
-
 __global__ __launch_bounds__(64) void k_stereo_identity(const unsigned char* __restrict__ prb_rec, const int32_t* __restrict__ prb_n,
                                                         const unsigned char* __restrict__ ref_rec, const int32_t* __restrict__ ref_n,
                                                         const int64_t* __restrict__ ref_index, int64_t M, int max_nodes, double min_volume,
@@ -240,8 +213,9 @@ __global__ __launch_bounds__(64) void k_stereo_identity(const unsigned char* __r
       int depth = 0;                                         // open levels: S.stack[0 .. depth-1]
       int first_iso = -1, first_same = -1, first_mirror = -1; // this lane's image under the first isomorphism of each kind
       bool ended = false;                                    // the search stopped for another reason than the budget
+      const auto same_label = [](int a, int b) { return S.type[a] == S.type[b] && S.fc[a] == S.fc[b] && S.ord[a] == S.ord[b]; };
       for (int it = 0; it <= max_nodes; ++it) {              // every pass but the last spends one search node
-        if (st == DISCRETE && verify(S, colour, active, n, lane)) {
+        if (st == DISCRETE && ds_refine::verify(S, colour, active, n, lane, same_label)) {
           const int mine = active && side == 0 ? S.img[idx] : -1;
           if (isos++ == 0) first_iso = mine;
           bool same = false;
@@ -271,35 +245,13 @@ __global__ __launch_bounds__(64) void k_stereo_identity(const unsigned char* __r
         }
         if (st == CELLS) {
           if (depth >= MA) break;                            // (cannot happen: every level makes one more generated atom a class of its own)
-          // open a level on the lowest class with several atoms: its lowest generated atom will be individualised
-          int c = (active && side == 0 && ((multi >> lane) & 1ull)) ? colour : 64;
-#pragma unroll
-          for (int o = 16; o > 0; o >>= 1) c = min(c, __shfl_xor(c, o, 64));
-          c = uniform_i(c);
-          const int v = __ffsll((long long)__ballot(active && side == 0 && colour == c)) - 1;
-          S.stack[depth][lane] = (unsigned char)colour;
-          if (lane == 0) { S.cell[depth] = c; S.atom[depth] = v; S.cursor[depth] = 0; }
-          __syncthreads();
-          ++depth;
+          ds_refine::open_level(S, depth, colour, active, lane, multi);
         }
-        // the next untried ground-truth atom of the deepest level that has one; levels without are closed
-        int v = -1, w = -1;
-        while (depth > 0) {                                  // at most 29 levels
-          const int f = depth - 1;
-          const int c = uniform_i(S.cell[f]), from = uniform_i(S.cursor[f]);
-          colour = S.stack[f][lane];
-          const unsigned long long cand = __ballot(active && side == 1 && colour == c && idx >= from);
-          if (cand) { v = uniform_i(S.atom[f]); w = __ffsll((long long)cand) - 1 - 32; break; }
-          --depth;
-        }
-        if (w < 0) { ended = true; break; }                  // nothing left to try anywhere: every isomorphism has been met
+        const ds_refine::Try t = ds_refine::next_try(S, depth, colour, active, lane);
+        if (t.w < 0) { ended = true; break; }                // nothing left to try anywhere: every isomorphism has been met
         if (used >= max_nodes) break;                        // the budget does not cover this try: undecided
         ++used;
-        __syncthreads();                                     // every lane has read the level's cursor
-        if (lane == 0) S.cursor[depth - 1] = w + 1;
-        if (active && (lane == v || lane == 32 + w)) colour = FRESH;
-        __syncthreads();
-        st = ds_refine::refine<true>(S, colour, active, n, lane, multi, SYNC);
+        st = ds_refine::individualise(S, depth, t, colour, active, n, lane, multi);
       }
       out = DSC_UNDECIDED;
       if (ended) {

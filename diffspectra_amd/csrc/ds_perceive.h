@@ -1,6 +1,7 @@
 // diffspectra_amd - perception of one result record by one wave64, an atom per lane: what the per-record evaluation kernels share
-// (ds_valence.hip, ds_groups.hip, ds_scaffold.hip, ds_smiles.hip, ds_substructure.hip, ds_brics.hip, ds_mobile.hip).  The definitions are those of the
-// public headers: applied charges and the valence check in include/diffspectra_valence.h, ring bonds and the candidate / electron rule in
+// (ds_valence.hip, ds_groups.hip, ds_scaffold.hip, ds_smiles.hip, ds_substructure.hip, ds_brics.hip, ds_mobile.hip, ds_fraggle.hip).  The
+// definitions are those of the public headers: applied charges and the valence check in include/diffspectra_valence.h, ring bonds and the
+// candidate / electron rule in
 // include/diffspectra_groups.h, the plain-hydrogen fold in include/diffspectra_smiles.h, the matched graph in
 // include/diffspectra_substructure.h.  Everything here is inlined into its caller, which keeps its own LDS struct and passes the arrays: a
 // result that a caller does not read costs it nothing.

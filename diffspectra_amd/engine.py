@@ -63,6 +63,7 @@ def load_library() -> C.CDLL:
     abi.STEREO.bind(lib)
     abi.BRICS.bind(lib)
     abi.MOBILE.bind(lib)
+    abi.FRAGGLE.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
     sizes = (C.c_int64 * 4)()
@@ -956,6 +957,67 @@ def normal_records(rec: torch.Tensor, n: torch.Tensor, max_nodes: Optional[int] 
                         [(torch.uint8, (RECORD_BYTES,)), (torch.int32, ()), (torch.uint8, (MAX_ATOMS,)), (torch.uint8, ())], prefix="dsm_")
 
 
+# ----------------------------------------------------------------------------------------- Fraggle similarity
+
+FRAGGLE_CONSTS = abi.FRAGGLE.consts       # include/diffspectra_fraggle.h
+FRAGGLE_OK, FRAGGLE_UNDECIDED, FRAGGLE_UNUSABLE, FRAGGLE_INVALID = (FRAGGLE_CONSTS["DSF_" + k] for k in ("OK", "UNDECIDED", "UNUSABLE", "INVALID"))
+FRAGGLE_MAX_NODES, FRAGGLE_DEFAULT_NODES = FRAGGLE_CONSTS["DSF_MAX_NODES"], FRAGGLE_CONSTS["DSF_DEFAULT_NODES"]
+FRAGGLE_MAX_FRAGMENTATIONS, FRAGGLE_TRUNCATED, FRAGGLE_NO_CUT = (FRAGGLE_CONSTS["DSF_" + k] for k in ("MAX_FRAGMENTATIONS", "TRUNCATED", "NO_CUT"))
+FRAGGLE_FP_WORDS = FRAGGLE_CONSTS["DSF_FP_WORDS"]
+
+
+def _fraggle_budget(max_nodes):
+    if max_nodes is None:
+        return FRAGGLE_DEFAULT_NODES
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, int):
+        raise TypeError(f"max_nodes must be an int, got {type(max_nodes).__name__}")
+    if not 1 <= max_nodes <= FRAGGLE_MAX_NODES:
+        raise ValueError(f"max_nodes must lie in [1, {FRAGGLE_MAX_NODES}], got {max_nodes}")
+    return max_nodes
+
+
+def fraggle_fragmentations(rec: torch.Tensor, n: torch.Tensor, max_nodes: Optional[int] = None):
+    """``dsf_fraggle_fragmentations``: the Fraggle fragmentations of every record - one or two chain cuts, two ring cuts, two ring cuts and a
+    chain cut - in the order and under the size rules of ``include/diffspectra_fraggle.h`` (a restatement of RDKit's Fraggle as remembered,
+    unpinned against RDKit).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(rows [P, 256, 4] i32, summary [P, 4] i32, status [P] u8)`` on the current stream
+    without synchronising: a row is (kept-atom mask, cuts packed ten bits each as lower atom | higher atom << 5 with ``FRAGGLE_NO_CUT`` for an
+    unused one, kind, sum of the kept sizes), unused rows are -1; ``summary`` is (matchable atoms, chain cut bonds, ring cut bonds, fragmentations
+    with ``FRAGGLE_TRUNCATED`` set when there are more than rows).  Status ``FRAGGLE_UNUSABLE`` (2) or ``FRAGGLE_UNDECIDED`` (1: the graph has more
+    than ``max_nodes`` connected bond sets, default 32768) gives rows of -1 and a zero summary.  Checked, never converted; no CPU path."""
+    return _record_call("fraggle_fragmentations", [(rec, n)], None, [_fraggle_budget(max_nodes)],
+                        [(torch.int32, (FRAGGLE_MAX_FRAGMENTATIONS, 4)), (torch.int32, (4,)), (torch.uint8, ())], prefix="dsf_")
+
+
+def path_fingerprints(rec: torch.Tensor, n: torch.Tensor, max_nodes: Optional[int] = None):
+    """``dsf_path_fingerprints``: the branched path fingerprint of every record (every connected set of 1..5 bonds sets 2 of 1024 bits; the
+    project's own hash, stated in ``include/diffspectra_fraggle.h``) with the bits of every atom.
+
+    -> the device tensors ``(fp [P, 32] i32, atom_bits [P, 29, 32] i32, count [P] i32, status [P] u8)`` on the current stream without
+    synchronising; ``count`` is the number of bond sets, -1 for ``FRAGGLE_UNDECIDED`` (more than ``max_nodes``), 0 for ``FRAGGLE_UNUSABLE``; a row
+    that is not ok has ``fp = atom_bits = 0``.  Checked, never converted; no CPU path."""
+    return _record_call("path_fingerprints", [(rec, n)], None, [_fraggle_budget(max_nodes)],
+                        [(torch.int32, (FRAGGLE_FP_WORDS,)), (torch.int32, (MAX_ATOMS, FRAGGLE_FP_WORDS)), (torch.int32, ()), (torch.uint8, ())], prefix="dsf_")
+
+
+def fraggle_similarity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                               ref_index: Optional[torch.Tensor] = None, max_nodes: Optional[int] = None):
+    """``dsf_fraggle_similarity_records``: the Fraggle similarity of P (generated, ground-truth) pairs as integers - the ground truth is the
+    query that is fragmented, as in the reference's ``GetFraggleSimilarity(true_mol, pred_mol)``.
+
+    The tensors are those of ``match_records``.  Returns the device tensors ``(plain [P, 2] i32, modified [P, 2] i32, best_index [P] i32,
+    n_fragmentations [P] i32, marked [P, 2] i32, status [P] u8)``, enqueued on the current stream without synchronising: ``plain`` and ``modified``
+    are (common, either) bit counts of the plain fingerprints and of the best marked pair over all fragmentations (-1, -1 without one),
+    ``marked`` the marked-atom masks of the ground truth and of the generated molecule for that fragmentation; status ``FRAGGLE_OK`` (0),
+    ``FRAGGLE_UNDECIDED`` (1: a fingerprint needed more than ``max_nodes`` bond sets), ``FRAGGLE_UNUSABLE`` (2) or ``FRAGGLE_INVALID`` (3:
+    ``ref_index`` outside the table); a pair that is not ok has -1 in ``plain``, ``modified`` and ``best_index`` and 0 elsewhere.  Checked, never
+    converted."""
+    i32, two = (torch.int32, ()), (torch.int32, (2,))
+    return _record_call("fraggle_similarity_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index, [_fraggle_budget(max_nodes)],
+                        [two, two, i32, i32, two, (torch.uint8, ())], prefix="dsf_")
+
+
 # ----------------------------------------------------------------------------------------- canonical SMILES
 
 SMILES_CONSTS = abi.SMILES.consts         # include/diffspectra_smiles.h
@@ -1274,6 +1336,18 @@ class DmtEngine:
     def brics_fragment_records(self, rec, n, first, rows: int, aromatic: bool = True):
         """``engine.brics_fragment_records`` on this engine's library."""
         return brics_fragment_records(rec, n, first, rows, aromatic)
+
+    def fraggle_fragmentations(self, rec, n, max_nodes=None):
+        """``engine.fraggle_fragmentations`` on this engine's library (the Fraggle analysis needs no weights)."""
+        return fraggle_fragmentations(rec, n, max_nodes)
+
+    def path_fingerprints(self, rec, n, max_nodes=None):
+        """``engine.path_fingerprints`` on this engine's library."""
+        return path_fingerprints(rec, n, max_nodes)
+
+    def fraggle_similarity_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, max_nodes=None):
+        """``engine.fraggle_similarity_records`` on this engine's library."""
+        return fraggle_similarity_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, max_nodes)
 
     def mobile_records(self, rec, n, max_nodes: Optional[int] = None):
         """``engine.mobile_records`` on this engine's library (the mobile-hydrogen analysis needs no weights)."""

@@ -138,6 +138,23 @@ def _maccs_summary(run, table, top_k: int, max_nodes: Optional[int] = None) -> D
     return entry
 
 
+def _fraggle_summary(run, table, top_k: int, max_nodes: Optional[int] = None) -> Dict:
+    """The reference's "Fraggle similarity" line of one finished run (the pairs of ``_structure_summary``; the ground truth is the molecule
+    that is fragmented); ``max_nodes``: the bond sets one fingerprint may have, ``None`` for the header's default."""
+    from .structure_metrics import _host_sum, fraggle_similarity_batch, topk_fraggle
+    dev = run.records_by_slot.device
+    alike = fraggle_similarity_batch(run.records_by_slot, torch.tensor(run.n_atoms), table.gt_records.to(dev), table.num_atom, ref_index=run.slot_ds,
+                                     max_nodes=max_nodes, engine=run.eng)
+    ok = alike.valid
+    n_ok = int(ok.sum())
+    entry = dict(fraggle=alike.fraggle, status=alike.status, mean=_host_sum(alike.fraggle[ok]) / n_ok if n_ok else None, scored=n_ok,
+                 undecided=int((alike.status == 1).sum()), unusable=int((alike.status == 2).sum()),
+                 no_fragmentation=int((ok & (alike.n_fragmentations == 0)).sum()))
+    if top_k > 1:
+        entry["top_k"] = topk_fraggle(alike.fraggle, alike.status, top_k)
+    return entry
+
+
 def _stereo_summary(run, table, top_k: int, min_volume: Optional[float] = None, min_planarity: Optional[float] = None) -> Dict:
     """The stereo-aware Top-1 / Top-K of one finished run (the pairs of ``_structure_summary``): ``dsc_stereo_identity_records`` per slot, and
     how many of the slots' ground truths are chiral.  The thresholds: ``None`` for the header's defaults."""
@@ -306,6 +323,16 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     default when absent; such keys are a lower bound) and, with K > 1, ``top_k = topk_maccs(...)``.  The key table restates RDKit's as remembered: parity with RDKit is unpinned
     (``structure_metrics.maccs_similarity_batch``).  Without the flag the dict has no such key.
 
+    With ``config.eval.fraggle`` true ``metrics['structure']['fraggle']`` is the reference's "Fraggle similarity" (``compute_metrics.py:273-291``,
+    ``GetFraggleSimilarity(true_mol, pred_mol)``; ``dsf_fraggle_similarity_records``): ``fraggle`` (f64 device tensor, one per slot: 0 when the
+    ground truth has no fragmentation, else the larger of the plain path-fingerprint Tanimoto and the best Tanimoto of the marked molecules over
+    all fragmentations; NaN for a pair that is not ok), ``status`` (0 ok, 1 undecided, 2 a record of the pair is unusable, 3 invalid), ``mean``
+    over the ok pairs (summed on the host; ``None`` without any), ``scored`` (the ok pairs), ``undecided`` (a fingerprint needed more than
+    ``config.eval.fraggle_max_nodes`` bond sets, the header's default when absent), ``unusable``, ``no_fragmentation`` (the ok pairs scored 0
+    for that reason) and, with K > 1, ``top_k = topk_fraggle(...)``.  The rule restates RDKit's Fraggle as remembered, with the project's own
+    fingerprint hash and aromaticity: parity with RDKit is unpinned (``include/diffspectra_fraggle.h`` names every deviation).  Without the
+    flag the dict has no such key.
+
     With ``config.eval.stereo`` true ``metrics['structure']['stereo']`` is the stereo-aware Top-1 (``dsc_stereo_identity_records``; the reference's
     Top-1 compares InChIKeys, ``compute_metrics.py:222-230``, which ``metrics['structure']['graph']`` does at constitution level only): ``verdict``
     (u8 device tensor, one per slot: 0 different, 1 identical, 2 undecided, 3 invalid, 4 mirror image, 5 another stereoisomer, 6 a site too
@@ -385,6 +412,8 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                 metrics["structure"]["functional_groups"] = _functional_group_summary(run, test_ds, top_k)
             if getattr(config.eval, "maccs", False):
                 metrics["structure"]["maccs"] = _maccs_summary(run, test_ds, top_k, getattr(config.eval, "maccs_max_nodes", None))
+            if getattr(config.eval, "fraggle", False):
+                metrics["structure"]["fraggle"] = _fraggle_summary(run, test_ds, top_k, getattr(config.eval, "fraggle_max_nodes", None))
             if getattr(config.eval, "stereo", False):
                 metrics["structure"]["stereo"] = _stereo_summary(run, test_ds, top_k, getattr(config.eval, "stereo_min_volume", None),
                                                                  getattr(config.eval, "stereo_min_planarity", None))

@@ -93,6 +93,12 @@ Whether a molecule contains a substructure, how many times and on which atoms is
 Similarity (MACCS)" (``compute_metrics.py:248-252``) from the key table of ``maccs.py``, which restates RDKit's as remembered: parity with RDKit
 is unpinned.
 
+The reference's "Fraggle Similarity" (``compute_metrics.py:273-291``) is ``fraggle_similarity_batch`` / ``topk_fraggle``
+(``dsf_fraggle_similarity_records``, ``csrc/ds_fraggle.hip``; every definition in ``include/diffspectra_fraggle.h``): the ground truth is
+fragmented by one to three cuts, every fragmentation marks the atoms of both molecules that it does not explain, and the best Tanimoto of the
+marked pair's path fingerprints, or the plain one if larger, is the similarity; ``fraggle_fragmentations`` and ``path_fingerprints`` show the
+parts.  The rule restates RDKit's Fraggle as remembered with the project's own fingerprint hash: parity with RDKit is unpinned.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -1393,6 +1399,97 @@ def topk_maccs(tanimoto: torch.Tensor, status: torch.Tensor, top_k: int) -> Dict
     if top_k < 1 or tanimoto.numel() % top_k or status.shape != tanimoto.shape:
         raise ValueError(f"{tanimoto.numel()} pairs (status: {status.numel()}) are not a whole number of top_k = {top_k} groups")
     return topk_morgan(torch.where(status == 0, tanimoto.to(torch.float64), torch.full_like(tanimoto, float("nan"), dtype=torch.float64)), top_k)
+
+
+# ------------------------------------------------------------------------------------------------------------------ Fraggle similarity
+
+class FraggleFragmentations(NamedTuple):
+    """Per-record device tensors of ``dsf_fraggle_fragmentations``."""
+    rows: torch.Tensor            # [P, 256, 4] i32: (kept-atom mask, cuts packed, kind, sum of the kept sizes) in the header's order; unused rows -1
+    summary: torch.Tensor         # [P, 4] i32: matchable atoms, chain cut bonds, ring cut bonds, fragmentations (all of them)
+    truncated: torch.Tensor       # [P] bool: there are more fragmentations than rows
+    status: torch.Tensor          # [P] u8: 0 ok, 1 undecided, 2 unusable
+
+    @property
+    def n_fragmentations(self) -> torch.Tensor:
+        return self.summary[:, 3]
+
+
+class PathFingerprints(NamedTuple):
+    """Per-record device tensors of ``dsf_path_fingerprints``."""
+    fp: torch.Tensor              # [P, 32] i32: 1024 bits
+    atom_bits: torch.Tensor       # [P, 29, 32] i32: the bits of every atom
+    count: torch.Tensor           # [P] i32: connected bond sets; -1 undecided, 0 unusable
+    status: torch.Tensor          # [P] u8: 0 ok, 1 undecided, 2 unusable
+
+
+class FraggleSimilarity(NamedTuple):
+    """Per-pair device tensors of ``fraggle_similarity_batch``."""
+    plain: torch.Tensor           # [P] f64: Tanimoto of the plain path fingerprints; NaN for a pair that is not ok
+    modified: torch.Tensor        # [P] f64: the best Tanimoto of the marked molecules over the fragmentations; NaN without one or when not ok
+    fraggle: torch.Tensor         # [P] f64: 0 without a fragmentation, else max(plain, modified); NaN for a pair that is not ok
+    best_index: torch.Tensor      # [P] i32: the fragmentation behind ``modified``, -1 without one
+    n_fragmentations: torch.Tensor  # [P] i32: the fragmentations of the ground truth
+    marked: torch.Tensor          # [P, 2] i32: the marked-atom masks of the ground truth and of the generated molecule for that fragmentation
+    status: torch.Tensor          # [P] u8: 0 ok, 1 undecided, 2 a record of the pair is unusable, 3 invalid row
+    counts: torch.Tensor          # [P, 4] i32: (common, either) of plain and of modified, as the kernel gives them
+
+    @property
+    def valid(self) -> torch.Tensor:
+        return self.status == 0
+
+
+def fraggle_fragmentations(records: torch.Tensor, n_atoms, max_nodes: Optional[int] = None, engine=None) -> FraggleFragmentations:
+    """The Fraggle fragmentations of every record of ``records [P, 1248] u8`` (GPU) in one launch of ``dsf_fraggle_fragmentations``
+    (``csrc/ds_fraggle.hip``; every definition in ``include/diffspectra_fraggle.h``, a restatement of RDKit's Fraggle as remembered and
+    unpinned against it).  Device tensors, no synchronisation."""
+    from . import engine as E
+    rows, summary, status = (engine if engine is not None else E).fraggle_fragmentations(records, _i32_on(records, n_atoms), max_nodes)
+    flag = E.FRAGGLE_TRUNCATED
+    return FraggleFragmentations(rows, torch.bitwise_and(summary, torch.tensor([-1, -1, -1, flag - 1], dtype=torch.int32, device=summary.device)),
+                                 torch.bitwise_and(summary[:, 3], flag) != 0, status)
+
+
+def path_fingerprints(records: torch.Tensor, n_atoms, max_nodes: Optional[int] = None, engine=None) -> PathFingerprints:
+    """The branched path fingerprint (1..5 bonds, 1024 bits, 2 bits per bond set; the project's own hash) of every record of ``records
+    [P, 1248] u8`` (GPU) with the bits of every atom, in one launch of ``dsf_path_fingerprints``.  Device tensors, no synchronisation."""
+    from . import engine as E
+    return PathFingerprints(*(engine if engine is not None else E).path_fingerprints(records, _i32_on(records, n_atoms), max_nodes))
+
+
+def fraggle_similarity_batch(prb, prb_n, ref, ref_n, ref_index=None, max_nodes: Optional[int] = None, engine=None) -> FraggleSimilarity:
+    """The reference's "Fraggle similarity" (``compute_metrics.py:273-291``: ``GetFraggleSimilarity(true_mol, pred_mol)``) of every generated
+    record ``prb [P, 1248] u8`` and its ground truth among ``ref [M, 1248] u8`` (both on the GPU; ``ref_index [P]`` names the row, ``None``: row p
+    for pair p - the record-pairs contract) in one launch of ``dsf_fraggle_similarity_records``; the floats are one division per pair on its
+    integers.  ``fraggle`` is 0 when the ground truth has no fragmentation (as RDKit gives it, even for identical molecules), else the larger
+    of ``plain`` and ``modified``.  ``max_nodes``: the connected bond sets one fingerprint may have (``None``: ``DSF_DEFAULT_NODES``); a pair
+    beyond it is undecided (status 1).  Stated deviations (``include/diffspectra_fraggle.h``): the rule is as remembered and unpinned against
+    RDKit; the fingerprint hash and the aromaticity are the project's; ring cuts and the ring step of the marking are order-free restatements
+    of RDKit's SSSR-based ones; both valid pieces of a ring cut count.  Device tensors, no synchronisation."""
+    from . import engine as E
+    dev = prb.device
+    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=dev, dtype=torch.int64).contiguous()
+    plain, modified, best, found, marked, status = (engine if engine is not None else E).fraggle_similarity_records(
+        prb, _i32_on(prb, prb_n), ref, _i32_on(ref, ref_n), idx, max_nodes)
+    nan = torch.full((prb.shape[0],), float("nan"), dtype=torch.float64, device=dev)
+
+    def ratio(pair, defined):
+        c, e = pair[:, 0].double(), pair[:, 1].double()
+        return torch.where(defined, torch.where(pair[:, 1] == 0, torch.ones_like(c), c / torch.where(pair[:, 1] == 0, torch.ones_like(e), e)), nan)
+    ok = status == 0
+    has = ok & (found > 0)
+    t_plain, t_modified = ratio(plain, ok), ratio(modified, has)
+    fraggle = torch.where(ok, torch.where(has, torch.maximum(t_plain, torch.where(has, t_modified, t_plain)), torch.zeros_like(nan)), nan)
+    return FraggleSimilarity(t_plain, t_modified, fraggle, best, found, marked, status, torch.cat([plain, modified], dim=1))
+
+
+def topk_fraggle(fraggle: torch.Tensor, status: torch.Tensor, top_k: int) -> Dict[str, torch.Tensor]:
+    """Best-of-K reductions of ``fraggle_similarity_batch`` over the K consecutive candidates of every spectrum, shaped like ``topk_maccs``:
+    ``best [S] f64`` (the largest similarity among the ok candidates, NaN when none of the K is ok), ``best_index [S] i64`` (the first candidate
+    with it, -1 when none is ok) and ``mean_best`` (a 0-dim f64 tensor; NaN without any).  Plain torch reductions on the tensors' device."""
+    if top_k < 1 or fraggle.numel() % top_k or status.shape != fraggle.shape:
+        raise ValueError(f"{fraggle.numel()} pairs (status: {status.numel()}) are not a whole number of top_k = {top_k} groups")
+    return topk_morgan(torch.where(status == 0, fraggle.to(torch.float64), torch.full_like(fraggle, float("nan"), dtype=torch.float64)), top_k)
 
 
 # ------------------------------------------------------------------------------------------------------------------ stereo-aware identity

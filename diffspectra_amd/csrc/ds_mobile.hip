@@ -14,134 +14,12 @@
 #include <stdint.h>
 
 #include "../../include/diffspectra_mobile.h"
-#include "ds_perceive.h"
+#include "ds_mobile.h"      // the analysis of one record: Wave, Found, analyse()
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
-using namespace ds_perceive;
-
-struct Wave {                             // one record's staging area
-  unsigned char adj[MA * 32];             // symmetric bond orders over original atom indices, diagonal 0
-  unsigned todo[DSM_LEVELS][32];          // [level][donor lane]: the interior atoms still to be tried from the level's last atom
-  unsigned short step[DSM_LEVELS][32];    // [level][donor lane]: the atoms v | w << 8 that the extension into this level put on the path
-  unsigned single[32];                    // bit j = bonded to atom j by order 1 and atom j is an interior atom
-  unsigned found[32];                     // a donor's acceptors
-  unsigned char partner[32];              // the other end of an interior atom's double bond
-  unsigned char ht[32];                   // normalised hydrogen count
-};
-
-struct Found {                            // what the analysis leaves; kept, roots, groups, p, nodes, mobile and status are wave-uniform
-  int status;                             // DSM_OK, DSM_UNUSABLE or DSM_UNDECIDED
-  bool kept_atom, member;                 // this lane holds a kept atom / a member of a group
-  int q_res, ht, group;                   // of this lane's atom; group = -1 for no member
-  unsigned kept_nb, kept, comp, roots;    // kept neighbours; kept atoms; the members of this atom's group; the lowest atom of every group
-  int groups, p, nodes, mobile;
-};
-
-__device__ __forceinline__ Found analyse(Wave& S, const unsigned char* __restrict__ mine, int n, int lane, int max_nodes) {
-  const ds_refine::Wave sync{};
-  const Atom A = scan(S.adj, mine, n, lane, sync);
-  const bool usable = usable_record(A, n), on = usable && A.active;
-  const int t = min(A.type, MAX_TYPE);
-  const unsigned nb = on ? A.nb : 0u, nb1 = on ? A.nb1 : 0u, nb2 = on ? A.nb2 : 0u, nb3 = on ? A.nb3 : 0u;
-  const unsigned me = lane < 32 ? 1u << lane : 0u;
-
-  // 1. the fold
-  const unsigned isH = low32(__ballot(on && t == H));
-  const unsigned folded = low32(__ballot(plain_hydrogen(on, t, A.raw, nb, isH) && nb1 == nb));
-  const unsigned kept = low32(__ballot(on)) & ~folded;
-  const bool kept_atom = (kept & me) != 0u;
-  const int q = on ? applied_charge(t, A.raw) : 0;
-  int ht = kept_atom ? __popc(nb & folded) + max(0, max_valence(t, q) - A.val) : 0;
-  const int dbl = __popc(nb2), trp = __popc(nb3);
-
-  // 2. charges, judged on the input
-  const unsigned plus = low32(__ballot(kept_atom && q > 0)), minus = low32(__ballot(kept_atom && q < 0));
-  const bool paired = (q > 0 && (nb & minus)) || (q < 0 && (nb & plus));
-  int q_res = kept_atom ? q : 0, dp = 0;
-  if (kept_atom && !paired) {
-    if (t == N && q == 1 && ht >= 1) { ht -= 1; q_res = 0; dp = 1; }
-    else if ((t == N || t == O) && q == -1) { ht += 1; q_res = 0; dp = -1; }
-  }
-  const int p = wave_sum(dp);
-
-  // 3. endpoints and interior atoms
-  const bool candidate = kept_atom && (t == N || t == O) && q_res == 0 && trp == 0 && dbl <= 1;
-  const bool donor = candidate && ht >= 1 && dbl == 0, acceptor = candidate && dbl == 1;
-  const unsigned acceptors = low32(__ballot(acceptor));
-  const unsigned interior = low32(__ballot(kept_atom && (t == C || t == N) && q_res == 0 && dbl == 1 && trp == 0));
-  if (lane < 32) {
-    S.single[lane] = nb1 & interior;
-    S.partner[lane] = (unsigned char)(nb2 ? __ffs((int)nb2) - 1 : 0);
-    S.ht[lane] = (unsigned char)ht;
-    S.found[lane] = 0u;
-  }
-  sync();
-
-  // 4. and 6. the search of this lane's donor: at most max_nodes + 1 extensions, each followed by one pop at the most
-  int count = 0;
-  if (donor && acceptors) {
-    unsigned onpath = me, found = 0u;
-    int depth = 0;
-    S.todo[0][lane] = nb1 & interior;
-    for (int it = 0; it <= 2 * max_nodes + 2; ++it) {
-      const unsigned left = S.todo[depth][lane];
-      if (!left) {
-        if (depth == 0) break;
-        const unsigned s = S.step[depth][lane];
-        onpath &= ~((1u << (s & 31u)) | (1u << ((s >> 8) & 31u)));
-        --depth;
-        continue;
-      }
-      const int v = __ffs((int)left) - 1;
-      S.todo[depth][lane] = left & (left - 1u);
-      if (++count > max_nodes) break;
-      const int w = S.partner[v] & 31;
-      const unsigned wbit = 1u << w;
-      if (onpath & wbit) continue;
-      if (acceptors & wbit) {
-        found |= wbit;
-        if (found == acceptors) break;
-      }
-      if ((interior & wbit) && depth + 1 < DSM_LEVELS) {
-        const unsigned both = (1u << v) | wbit, next = S.single[w] & ~(onpath | both);
-        if (next) {
-          ++depth;
-          onpath |= both;
-          S.todo[depth][lane] = next;
-          S.step[depth][lane] = (unsigned short)(v | (w << 8));
-        }
-      }
-    }
-    S.found[lane] = found;
-  }
-  const int nodes = wave_sum(min(count, max_nodes + 1));                          // (29 * (DSM_MAX_NODES + 1) fits an int)
-  const bool decided = nodes <= max_nodes;
-  sync();
-
-  // 5. groups: ~ made symmetric, then its components
-  unsigned comp = 0u;
-  if (donor) comp = S.found[lane];
-  if (acceptor)
-    for (int j = 0; j < n; ++j)
-      if ((S.found[j] >> lane) & 1u) comp |= 1u << j;
-  if (comp) comp |= me;
-  comp = components(comp, n);
-  const bool member = usable && decided && comp != 0u;
-  const unsigned roots = low32(__ballot(member && (unsigned)(__ffs((int)comp) - 1) == (unsigned)lane));
-  const int group = member ? (int)__popc(roots & ((1u << (__ffs((int)comp) - 1)) - 1u)) : -1;
-  const int mobile = wave_sum(member ? ht : 0);
-  const int status = !usable ? DSM_UNUSABLE : !decided ? DSM_UNDECIDED : DSM_OK;
-  return {status, kept_atom, member, q_res, ht, group, nb & kept, kept, comp, roots, (int)__popc(roots), p, nodes, mobile};
-}
-
-// the mobile H of the group whose lowest atom is this lane's (asked by the root lanes only)
-__device__ __forceinline__ int group_hydrogens(const Wave& S, unsigned comp) {
-  int h = 0;
-  for (unsigned m = comp; m; m &= m - 1u) h += S.ht[__ffs((int)m) - 1];
-  return h;
-}
+using namespace ds_mobile;              // Wave, Found, analyse(), group_hydrogens(): shared with ds_key.hip
 
 __global__ __launch_bounds__(64 * DSM_WAVES) void k_mobile(const unsigned char* __restrict__ rec, const int32_t* __restrict__ n_atoms, int64_t P,
                                                            int max_nodes, unsigned char* __restrict__ fixed_h, signed char* __restrict__ q_res,
@@ -241,10 +119,8 @@ __global__ __launch_bounds__(64 * DSM_WAVES) void k_mobile_normal(const unsigned
 }
 
 static_assert(DSM_WAVES >= 1 && 64 * DSM_WAVES <= 1024, "a workgroup of whole waves");
-static_assert(DSM_MAX_GROUPS == MA / 2 && DSM_LEVELS >= (MA - 1) / 2 + 1, "groups of two atoms at least; a simple path of MA atoms has (MA - 1) / 2 extensions");
 static_assert(DS_REC_POS % 4 == 0 && DS_RECORD_BYTES % 4 == 0, "positions and rows as dwords");
 static_assert(DSM_GROUP_TYPE > MAX_TYPE && DSM_PROTON_TYPE > DSM_GROUP_TYPE, "normal-form records are outside the alphabet of the analytics");
-static_assert(DSM_MAX_NODES <= (0x7fffffff - 2) / 2 && DSM_MAX_NODES < 0x7fffffff / 64, "the search's pass counter and the wave's node sum fit an int");
 
 }  // namespace
 

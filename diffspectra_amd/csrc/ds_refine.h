@@ -1,6 +1,6 @@
 // diffspectra_amd - colour refinement of molecular graphs, shared by the pair kernels (two molecules at once, one per half wave: PAIR = true;
-// k_graph_identity in ds_graph.hip and k_stereo_identity in ds_stereo.hip) and ds_smiles.hip (one molecule per wave, atoms in lanes 0..28:
-// PAIR = false), and below it the individualise-and-refine search that the two pair kernels run.  The signature and its order are those of
+// k_graph_identity in ds_graph.hip, k_stereo_identity in ds_stereo.hip and k_key_identity in ds_key.hip) and ds_smiles.hip (one molecule per wave, atoms in lanes 0..28:
+// PAIR = false), and below it the individualise-and-refine search that those pair kernels run.  The signature and its order are those of
 // include/diffspectra_smiles.h: the atom's colour in the top 6 bits (so a round only ever splits classes), below it the commutative sum over
 // its bonded neighbours j of fmix(colour_j + 1) * (2 bond_ij + 1), shifted right by 6.
 //

@@ -18,6 +18,7 @@
 #include "../../include/diffspectra_stereo.h"
 #include "ds_records.h"
 #include "ds_refine.h"
+#include "ds_vec.h"
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
@@ -51,12 +52,7 @@ struct Site {                             // what a lane knows of its atom after
   double V;
 };
 
-struct Vec { double x, y, z; };
-__device__ __forceinline__ Vec operator-(Vec a, Vec b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ Vec operator*(Vec a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ double dot(Vec a, Vec b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ Vec cross(Vec a, Vec b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ bool finite(Vec a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
+using namespace ds_vec;                   // Vec and its operations: shared with ds_key.hip
 __device__ __forceinline__ Vec at(const Geometry& S, int slot) { return {(double)S.pos[slot][0], (double)S.pos[slot][1], (double)S.pos[slot][2]}; }
 
 // The prologue of one molecule per half wave (side = lane >> 5; n = the side's atom count, 0 for a half without a molecule, whose record is

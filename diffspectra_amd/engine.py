@@ -63,6 +63,7 @@ def load_library() -> C.CDLL:
     abi.STEREO.bind(lib)
     abi.BRICS.bind(lib)
     abi.MOBILE.bind(lib)
+    abi.KEY.bind(lib)
     abi.FRAGGLE.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
@@ -1124,6 +1125,48 @@ def stereo_sites(rec: torch.Tensor, n: torch.Tensor, min_volume: Optional[float]
                         [(torch.int32, (STEREO_NUM_MASKS,)), (torch.float64, (MAX_ATOMS,)), (torch.uint8, ())], prefix="dsc_")
 
 
+# ----------------------------------------------------------------------------------------- key-level identity: normal form and stereo at once
+
+KEY_CONSTS = abi.KEY.consts               # include/diffspectra_key.h
+KEY_KIND_MASK, KEY_KIND_CENTRE, KEY_KIND_END = (KEY_CONSTS["DSI_KIND_" + k] for k in ("MASK", "CENTRE", "END"))
+KEY_FLAG_ASSIGNED, KEY_FLAG_SIGN, KEY_FLAG_HSLOT = (KEY_CONSTS["DSI_FLAG_" + k] for k in ("ASSIGNED", "SIGN", "HSLOT"))
+KEY_NO_PARTNER, KEY_NUM_MASKS = KEY_CONSTS["DSI_NO_PARTNER"], KEY_CONSTS["DSI_NUM_MASKS"]
+_KEY_SITE = (torch.uint8, (MAX_ATOMS, 2))
+
+
+def key_sites(rec: torch.Tensor, n: torch.Tensor, max_nodes: Optional[int] = None, min_volume: Optional[float] = None,
+              min_planarity: Optional[float] = None):
+    """``dsi_key_sites``: the stereo sites of every ORIGINAL record at the level of its normal form (every definition in
+    ``include/diffspectra_key.h``: excluded atoms, the hydrogen slot, centres, E/Z sites off every shift path and off every ring; a
+    restatement of InChI as remembered, unpinned against it).
+
+    ``rec [P, 1248] u8``, ``n [P] i32`` -> the device tensors ``(site [P, 29, 2] u8, masks [P, 9] i32, volume [P, 29] f64, nodes [P] i32,
+    status [P] u8)`` on the current stream without synchronising, all in normal-form numbering (row p lines up with row p of
+    ``normal_records`` with the same ``max_nodes``): ``site`` = (flags, partner) of every node; ``masks`` = the seven ``DSC_MASK_*`` rows, the
+    ends of the double bonds on a shift path, the ends of the ring double bonds; ``volume`` = V of every centre, 0 elsewhere; a row whose
+    status is not ``MOBILE_OK`` (undecided, unusable, overflow) is flags 0, partner 255, zeros.  Checked, never converted; no CPU path."""
+    return _record_call("key_sites", [(rec, n)], None, [_mobile_budget(max_nodes), *_stereo_thresholds(min_volume, min_planarity)],
+                        [_KEY_SITE, (torch.int32, (KEY_NUM_MASKS,)), (torch.float64, (MAX_ATOMS,)), (torch.int32, ()), (torch.uint8, ())],
+                        prefix="dsi_")
+
+
+def key_identity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, prb_site: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                         ref_site: torch.Tensor, ref_index: Optional[torch.Tensor] = None, max_nodes: int = 4096, exhaustive: bool = False):
+    """``dsi_key_identity_records``: the verdicts of ``stereo_identity_records`` for P pairs of NORMAL-FORM records (``normal_records``) with
+    the site rows of ``key_sites`` beside them (``prb_site [P, 29, 2] u8``, ``ref_site [M, 29, 2] u8``): every isomorphism of the normal forms
+    is tested against the sites (``include/diffspectra_key.h``).  Returns ``(verdict [P] u8, nodes [P] i32, found [P, 3] i32, sites [P, 4]
+    i32, map [P, 29] i32)`` as there, the map in normal-form indices, on the current stream without synchronising.  Checked, never
+    converted."""
+    if not isinstance(exhaustive, (bool, int)) or exhaustive not in (0, 1):
+        raise TypeError(f"exhaustive must be a bool, got {exhaustive!r}")
+    _want(prb_site, "prb_site", torch.uint8, (prb_rec.shape[0], MAX_ATOMS, 2))
+    _want(ref_site, "ref_site", torch.uint8, (ref_rec.shape[0], MAX_ATOMS, 2))
+    return _record_call("key_identity_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index,
+                        [ptr(prb_site), ptr(ref_site), _node_budget(max_nodes, GRAPH_MAX_NODES), int(exhaustive)],
+                        [(torch.uint8, ()), (torch.int32, ()), (torch.int32, (3,)), (torch.int32, (4,)), _MAP], prefix="dsi_",
+                        also=(prb_site, ref_site))
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -1356,6 +1399,15 @@ class DmtEngine:
     def normal_records(self, rec, n, max_nodes: Optional[int] = None):
         """``engine.normal_records`` on this engine's library."""
         return normal_records(rec, n, max_nodes)
+
+    def key_sites(self, rec, n, max_nodes: Optional[int] = None, min_volume=None, min_planarity=None):
+        """``engine.key_sites`` on this engine's library (the perception needs no weights)."""
+        return key_sites(rec, n, max_nodes, min_volume, min_planarity)
+
+    def key_identity_records(self, prb_rec, prb_n, prb_site, ref_rec, ref_n, ref_site, ref_index=None, max_nodes: int = 4096,
+                             exhaustive: bool = False):
+        """``engine.key_identity_records`` on this engine's library (the comparison needs no weights)."""
+        return key_identity_records(prb_rec, prb_n, prb_site, ref_rec, ref_n, ref_site, ref_index, max_nodes, exhaustive)
 
     def smiles_records(self, rec, n, max_nodes: int = 4096):
         """``engine.smiles_records`` on this engine's library (the strings need no weights)."""

@@ -190,6 +190,24 @@ def _mobile_summary(run, table, top_k: int, max_nodes: int = 4096) -> Dict:
     return entry
 
 
+def _key_summary(run, table, top_k: int, max_nodes: int = 4096, min_volume: Optional[float] = None, min_planarity: Optional[float] = None) -> Dict:
+    """Top-1 / Top-K at the level of an InChIKey of one finished run (the pairs of ``_structure_summary``): ``key_identity_batch`` per slot -
+    the normal form of ``_mobile_summary`` and the stereo verdicts of ``_stereo_summary`` at once.  Unpinned against InChI."""
+    from .structure_metrics import key_identity_batch, topk_identity
+    dev = run.records_by_slot.device
+    ref, prb = (table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms))
+    same = key_identity_batch(ref, prb, ref_index=run.slot_ds, max_nodes=max_nodes, min_volume=min_volume, min_planarity=min_planarity, engine=run.eng)
+    P = same.verdict.numel()
+    rate = lambda hit: float(hit.double().mean()) if P else 0.0
+    entry = dict(verdict=same.verdict, layer=same.layer, identity_rate=rate(same.identical), strict_rate=rate(same.strict == 1),
+                 normalised_hits=int((same.layer == 1).sum()), mirror=int(same.mirror.sum()), stereoisomer=int(same.stereoisomer.sum()),
+                 unassigned=int(same.unassigned.sum()), undecided=int(same.undecided.sum()), invalid=int((same.verdict == 3).sum()),
+                 sites=same.sites)
+    if top_k > 1:
+        entry["top_k"] = topk_identity(same.verdict, top_k)
+    return entry
+
+
 def _scaffold_summary(run, table, top_k: int, scaffold_fn, min_rings: int) -> Dict:
     """The "Scaf" number of one finished run against the test table (``scaffold_fn``: ``get_scaffold_metric`` of its records) and, over the
     pairs of ``_structure_summary``, whether every generated molecule shares the scaffold of its ground truth."""
@@ -351,7 +369,15 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     normalisation, -1 not identical), ``identity_rate`` (verdict 1 over all slots), ``strict_rate`` (what ``graph`` calls identical),
     ``normalised_hits`` (the slots with layer 1), ``undecided`` and ``invalid`` (counts) and, with K > 1, ``top_k = topk_identity(verdict, K)``.
     ``config.eval.mobile_max_nodes`` replaces the budget of 4096.  The rule restates InChI's as remembered and is unpinned against it; the
-    stereo layer is not combined with it (``include/diffspectra_mobile.h``).  Without the flag the dict has no such key.
+    stereo layer is not combined with it there (``include/diffspectra_mobile.h``); ``config.eval.key_identity`` below combines the two.
+    Without the flag the dict has no such key.
+
+    With ``config.eval.key_identity`` true ``metrics['structure']['key']`` is Top-1 at the level of an InChIKey - the normal form above AND
+    the stereo verdicts, at once (``structure_metrics.key_identity_batch``; ``include/diffspectra_key.h``): ``verdict`` (u8 device tensor, one
+    per slot, the codes of ``stereo`` above), ``layer``, ``identity_rate`` (the Top-1), ``strict_rate`` (the stereo-aware Top-1 on the records
+    as drawn), ``normalised_hits`` (hits with layer 1), ``mirror``, ``stereoisomer``, ``unassigned``, ``undecided`` and ``invalid`` (counts),
+    ``sites`` and, with K > 1, ``top_k``.  ``config.eval.key_max_nodes`` replaces the budget of 4096; the thresholds are those of ``stereo``.
+    Every rule restates InChI as remembered: the number is unpinned against InChI.  Without the flag the dict has no such key.
 
     With ``config.eval.smiles`` true ``metrics['structure']['smiles']`` holds the molecules as text, where the reference calls ``Chem.MolToSmiles``
     (``run_lib.py:111-112``, ``compute_metrics.py:73-78,209-220``; ``dsl_smiles_records``): ``generated`` (one canonical SMILES string per slot,
@@ -419,6 +445,10 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                                                                  getattr(config.eval, "stereo_min_planarity", None))
             if getattr(config.eval, "mobile_identity", False):
                 metrics["structure"]["mobile"] = _mobile_summary(run, test_ds, top_k, int(getattr(config.eval, "mobile_max_nodes", 4096)))
+            if getattr(config.eval, "key_identity", False):
+                metrics["structure"]["key"] = _key_summary(run, test_ds, top_k, int(getattr(config.eval, "key_max_nodes", 4096)),
+                                                           getattr(config.eval, "stereo_min_volume", None),
+                                                           getattr(config.eval, "stereo_min_planarity", None))
             if getattr(config.eval, "sub_geometry", False):
                 from .structure_metrics import get_sub_geometry_metric
                 if geometry_fn is None:

@@ -1698,3 +1698,116 @@ def mobile_classes(records: torch.Tensor, n_atoms, max_nodes: Optional[int] = No
     if rows.numel():
         class_id[rows] = rows[graph_classes(out_rec[rows].contiguous(), out_n[rows].contiguous(), engine)]
     return class_id
+
+
+# ------------------------------------------------------------------------------------------------------------------ key-level identity
+
+class KeySites(NamedTuple):
+    """Per-record device tensors of ``dsi_key_sites``, in normal-form numbering (row p lines up with row p of ``normal_form_records``)."""
+    site: torch.Tensor            # [P, 29, 2] u8: (flags, partner) of every node - kind 0 / 1 centre / 2 end in bits 0..1, 4 assigned, 8 sign or cis, 16 hydrogen slot; partner 255 off an E/Z site
+    masks: torch.Tensor           # [P, 9] i32, a bit per node: the seven rows of ``StereoSites``, the ends of the double bonds on a shift path, the ends of the ring double bonds
+    volume: torch.Tensor          # [P, 29] f64 V of every centre, 0 elsewhere
+    nodes: torch.Tensor           # [P] i32 nodes of the exhaustive shift-path search
+    status: torch.Tensor          # [P] u8: 0 ok, 2 undecided (budget), 3 unusable, 4 a normal form over 29 nodes: flags 0, partner 255, zeros
+
+    @property
+    def flags(self) -> torch.Tensor:
+        return self.site[..., 0]
+
+    @property
+    def partner(self) -> torch.Tensor:
+        return self.site[..., 1]
+
+    @property
+    def mobile_bond(self) -> torch.Tensor:
+        return self.masks[:, 7]
+
+    @property
+    def ring_bond(self) -> torch.Tensor:
+        return self.masks[:, 8]
+
+
+class KeyIdentity(NamedTuple):
+    """Per-pair device tensors of ``key_identity_batch``."""
+    verdict: torch.Tensor         # [P] u8: the codes of ``StereoIdentity`` at the level of the normal form
+    nodes: torch.Tensor           # [P] i32 search nodes of the comparison of the normal forms
+    found: torch.Tensor           # [P, 3] i32 isomorphisms of the normal forms, same, mirror met until the search stopped
+    sites: torch.Tensor           # [P, 4] i32 centres and E/Z sites of the generated molecule, unassigned sites of it and of the ground truth
+    map: torch.Tensor             # [P, 29] i32: ground-truth kept atom of every generated kept atom behind verdict 1, 4, 5 or 6, else -1 (original atoms)
+    strict: torch.Tensor          # [P] u8: the verdict of ``stereo_identity_batch`` on the records as drawn
+    layer: torch.Tensor           # [P] i8: 0 identical as drawn, 1 identical only at this level, -1 not identical
+    prb_status: torch.Tensor      # [P] u8 status of the generated record's sites (0 ok, 2 undecided, 3 unusable, 4 overflow)
+    ref_status: torch.Tensor      # [P] u8 the same of its ground truth (3 for an invalid row)
+
+    @property
+    def identical(self) -> torch.Tensor:
+        return self.verdict == 1
+
+    @property
+    def mirror(self) -> torch.Tensor:
+        return self.verdict == 4
+
+    @property
+    def stereoisomer(self) -> torch.Tensor:
+        return self.verdict == 5
+
+    @property
+    def unassigned(self) -> torch.Tensor:
+        return self.verdict == 6
+
+    @property
+    def undecided(self) -> torch.Tensor:
+        return self.verdict == 2
+
+
+def key_sites(records: torch.Tensor, n_atoms, max_nodes: Optional[int] = None, min_volume: Optional[float] = None,
+              min_planarity: Optional[float] = None, engine=None) -> KeySites:
+    """The stereo sites of every record of ``records [P, 1248] u8`` (GPU) at the level of its normal form, in one launch of ``dsi_key_sites``
+    (``csrc/ds_key.hip``; every definition in ``include/diffspectra_key.h``, which restates InChI as remembered and is unpinned against it).
+    ``max_nodes``: the budget of the shift-path search per record (``None``: 4096).  Device tensors, no synchronisation."""
+    from . import engine as E
+    return KeySites(*(engine if engine is not None else E).key_sites(records, _i32_on(records, n_atoms), max_nodes, min_volume, min_planarity))
+
+
+def key_identity_batch(ref, prb, ref_index=None, max_nodes: int = 4096, min_volume: Optional[float] = None, min_planarity: Optional[float] = None,
+                       exhaustive: bool = False, engine=None) -> KeyIdentity:
+    """Identity of every generated molecule with its ground truth at the level of an InChIKey: up to mobile hydrogens, acid / base forms and
+    Kekule drawings (``mobile_identity_batch``) AND in the arrangement of its centres and double bonds (``stereo_identity_batch``), both at
+    once - the comparison behind the reference's Top-1 (``compute_metrics.py:222-230``), with the deviations ``include/diffspectra_key.h``
+    states: the rules restate InChI as remembered and the number is UNPINNED against InChI.  ``ref`` and ``prb`` are ``(records [*, 1248] u8,
+    n_atoms [*])`` pairs on the GPU, ground truth first; ``ref_index [P]`` names the ground-truth row of every generated molecule (``None``:
+    row p); ``max_nodes`` is the budget of the path searches and of the comparisons.  A pair with an unusable side is invalid (3), a pair with
+    a side over a budget or over 29 nodes is undecided (2).  ``topk_identity`` works on ``verdict`` unchanged.  Device tensors, no
+    synchronisation."""
+    from . import engine as E
+    eng = engine if engine is not None else E
+    (ref_rec, ref_n), (prb_rec, prb_n) = ref, prb
+    dev = prb_rec.device
+    ref_n, prb_n = _i32_on(ref_rec, ref_n), _i32_on(prb_rec, prb_n)
+    P, M = prb_rec.shape[0], ref_rec.shape[0]
+    idx = None if ref_index is None else torch.as_tensor(ref_index).to(device=dev, dtype=torch.int64).contiguous()
+    compare = min(max_nodes, E.GRAPH_MAX_NODES) if isinstance(max_nodes, int) else max_nodes      # (the bindings check the type)
+    strict = eng.stereo_identity_records(prb_rec, prb_n, ref_rec, ref_n, idx, compare, min_volume, min_planarity, exhaustive)[0]
+    p_rec, p_n, p_src, _ = eng.normal_records(prb_rec, prb_n, max_nodes)
+    r_rec, r_n, r_src, _ = eng.normal_records(ref_rec, ref_n, max_nodes)
+    p_site, _, _, _, p_st = eng.key_sites(prb_rec, prb_n, max_nodes, min_volume, min_planarity)
+    r_site, _, _, _, r_st = eng.key_sites(ref_rec, ref_n, max_nodes, min_volume, min_planarity)
+    verdict, nodes, found, sites, image = eng.key_identity_records(p_rec, p_n, p_site, r_rec, r_n, r_site, idx, compare, exhaustive)
+    rows = torch.arange(P, device=dev) if idx is None else idx
+    inside = (rows >= 0) & (rows < M)
+    safe = torch.where(inside, rows, torch.zeros_like(rows))
+    unusable, ok = E.MOBILE_UNUSABLE, E.MOBILE_OK
+    ref_status = torch.where(inside, r_st[safe] if M else torch.zeros_like(p_st), torch.full_like(p_st, unusable))
+    not_ok = (p_st != ok) | (ref_status != ok)
+    invalid = (verdict == E.STEREO_INVALID) | (p_st == unusable) | (ref_status == unusable)
+    verdict = torch.where(invalid, torch.full_like(verdict, E.STEREO_INVALID), torch.where(not_ok, torch.full_like(verdict, E.STEREO_UNDECIDED), verdict))
+    same = verdict == E.STEREO_IDENTICAL
+    layer = torch.where(same, (strict != E.STEREO_IDENTICAL).to(torch.int8), torch.full((P,), -1, dtype=torch.int8, device=dev))
+    # the map between normal-form rows, translated to original kept atoms on both sides
+    out = torch.full((P, p_src.shape[1]), -1, dtype=torch.int32, device=dev)
+    if P and M:
+        target = r_src[safe].gather(1, image.clamp(min=0).to(torch.int64)).to(torch.int32)       # the original ground-truth atom of every row atom
+        mapped = (same | (verdict >= E.STEREO_MIRROR)).unsqueeze(1) & (p_src != 0xff) & (image >= 0)
+        p_at, slot = mapped.nonzero(as_tuple=True)
+        out[p_at, p_src[p_at, slot].to(torch.int64)] = target[p_at, slot]
+    return KeyIdentity(verdict, nodes, found, sites, out, strict, layer, p_st, ref_status)

@@ -64,8 +64,8 @@
  * ds_graph_identity_records and ds_graph_hash_records rank the raw type and charge bytes without clamping and decide unchanged.  The charge
  * byte is one-to-one while fixed H <= 15, which holds for every atom within its valence.
  *
- * Stated deviations from a standard InChI: the rule is as remembered and unpinned; no stereo layer here (dss_stereo_identity_records of
- * diffspectra_stereo.h has it, and the two are not combined); no metal disconnection, no (+)/(-) charge migration beyond rule 2, no
+ * Stated deviations from a standard InChI: the rule is as remembered and unpinned; no stereo layer here (dsc_stereo_identity_records of
+ * diffspectra_stereo.h has it on the graph as drawn; diffspectra_key.h combines the two: dsi_key_identity_records); no metal disconnection, no (+)/(-) charge migration beyond rule 2, no
  * ring-chain or 1,5-shift tautomerism beyond the paths of rule 4; a salt's components are compared as one record.  The groups are judged in one
  * pass on the drawing as given, where InChI iterates: moving one hydrogen along one path left the groups as they were in every molecule of the
  * test corpus in which no N or O is bonded to an N or O, but in a chain such as N(H)-N(H)-N=N(H) the shifted drawing N(H)-N=N-N(H2) has a path, from the first nitrogen,

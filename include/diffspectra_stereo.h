@@ -80,7 +80,8 @@
  * unassigned count so that a user sees the sensitivity.
  *
  * Deviations from InChIKey equality:
- *   - still no InChI normalisation of tautomers or charges (as ds_graph_identity_records; diffspectra_mobile.h has it, not combined with this);
+ *   - still no InChI normalisation of tautomers or charges (as ds_graph_identity_records; diffspectra_mobile.h has it, and diffspectra_key.h
+ *     combines it with the verdicts of this header: dsi_key_identity_records);
  *   - only four-coordinate centres: no three-coordinate N (or S, P), no allene axis, no helicity / atropisomers - a 1,3-disubstituted allene
  *     has no site and is DSC_IDENTICAL against its mirror image;
  *   - site perception is by twins (a centre with two leaf-identical neighbours is no site; a centre whose equal neighbours are larger groups

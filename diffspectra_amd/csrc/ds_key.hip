@@ -4,39 +4,30 @@
 // level, the hydrogen slot, the excluded atoms, the bonds on shift paths, what an isomorphism of normal forms does to a site); DESIGN.md
 // section 25 has the method and the figures.  All of it restates InChI as remembered and is unpinned against it.
 //
+// ds_sites.h has the twin key, the fp64 geometry of a site, the search with its leaf test and the argument for the verdicts.  This file adds:
+//
 // k_key_sites: one wave64 per ORIGINAL record, DSM_WAVES records per workgroup, an atom per lane, wave barriers only.  The mobile-hydrogen
 // analysis is that of ds_mobile.h; behind it every donor lane runs the same depth-first search once more without its early stop, on the same
 // LDS stack ([level][lane]: a register array indexed by the depth would go to scratch), and marks the double bonds of every path that ends on
-// an acceptor.  Then twins, sites and the fp64 geometry, a site per lane, in original indices; the outputs are written in normal-form
+// an acceptor.  Then twins, the hydrogen slot and the sites, a site per lane, in original indices; the outputs are written in normal-form
 // numbering (the rank of the atom among the kept atoms).
 //
-// k_key_identity: one wave64 per pair of NORMAL-FORM records, one wave per workgroup, the generated molecule in lanes 0..28 and the ground
-// truth in lanes 32..60, as k_stereo_identity (ds_stereo.hip).  Twins and ordinals from the normal form, the joint refinement and the pair
-// search of ds_refine.h, going on after a verified leaf; the leaf is tested against the site rows in integers.  No atomics.
-//
-// Soundness, in the lines the code keeps true: a leaf counts only after ds_refine::verify(); DSC_DIFFERENT needs an exhausted search without
-// a leaf; DSC_MIRROR / DSC_STEREOISOMER need an exhausted search; a search the budget stops is DSC_UNDECIDED whatever it had found.
+// k_key_identity: one wave64 per pair of NORMAL-FORM records, one wave per workgroup, as k_stereo_identity (ds_stereo.hip).  Its prologue
+// takes twins and ordinals from the normal form and the sites from the rows, and drops a row that contradicts its record.  No atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/diffspectra_key.h"
 #include "ds_mobile.h"
-#include "ds_refine.h"
-#include "ds_vec.h"
+#include "ds_sites.h"
 #include "ds_host.h"   // DST_CHECK_LAUNCH
 
 namespace {
 
 using namespace ds_perceive;
-using namespace ds_vec;
-
-constexpr unsigned HSLOT = 1u << 31;      // in a substituent word: the end has a hydrogen slot (atoms are bits 0..28)
-constexpr int NO_LOW = 31;                // "lowest kept substituent" of an end whose only substituent is its hydrogen slot
-
-// twin key of a node: a leaf's is (parent, type, charge byte), a bondless node's (type, charge byte), every other node's is its own
-__device__ __forceinline__ unsigned twin_key(int degree, int parent, unsigned type, unsigned charge, int self) {
-  return degree == 1 ? 1u << 29 | (unsigned)parent << 24 | type << 8 | charge : degree == 0 ? 2u << 29 | type << 8 | charge : 3u << 29 | (unsigned)self;
-}
+using ds_sites::half_of;
+using ds_sites::HSLOT;
+using ds_sites::NO_LOW;
 
 // ------------------------------------------------------------------------------------------------------------------------ the sites
 
@@ -50,8 +41,6 @@ struct Sites {                            // one record's staging area
   unsigned char row[32][2];               // the output row, in normal-form numbering
   double vol[32];
 };
-
-__device__ __forceinline__ Vec at(const Sites& S, int atom) { return widen(S.pos[atom]); }
 
 __global__ __launch_bounds__(64 * DSM_WAVES) void k_key_sites(const unsigned char* __restrict__ rec, const int32_t* __restrict__ n_atoms, int64_t P,
                                                               int max_nodes, double min_volume, double min_planarity,
@@ -135,19 +124,15 @@ __global__ __launch_bounds__(64 * DSM_WAVES) void k_key_sites(const unsigned cha
     if (ring_bond(S.any, me, r.nb, goal)) ring_nb |= goal;
   }
 
-  // twins and ordinals on the normal form: a member's bond to its group node counts
+  // twins on the normal form: a member's bond to its group node counts, and no bond has an order.  Only a kept atom that is no member can
+  // have another atom's key, so the count may run over all n
   const bool excluded = r.member || r.moved;
   const unsigned charge = (unsigned)((r.member ? 0 : r.ht) + 16 * (r.q_res + 1)) & 255u;
   const int degree = (int)__popc(r.kept_nb) + (r.member ? 1 : 0);
-  const unsigned key = twin_key(kept_atom && !r.member ? degree : 2, __ffs((int)r.kept_nb) - 1, (unsigned)mine[DS_REC_TYPE + (in ? lane : 0)], charge, lane);
+  const unsigned key = ds_sites::twin_key(kept_atom && !r.member ? degree : 2, __ffs((int)r.kept_nb) - 1, 0u, (unsigned)mine[DS_REC_TYPE + (in ? lane : 0)], charge, lane);
   if (lane < 32) S.key[lane] = key;
   sync();
-  bool twin = false;
-  if (kept_atom)
-    for (unsigned m = r.kept; m; m &= m - 1u) {
-      const int j = __ffs((int)m) - 1;
-      twin |= j != lane && S.key[j] == key;
-    }
+  const bool twin = kept_atom && ds_sites::count_twins(S.key, key, n, lane).twin;
   const unsigned twins = low32(__ballot(twin));
 
   // the hydrogen slot
@@ -155,24 +140,14 @@ __global__ __launch_bounds__(64 * DSM_WAVES) void k_key_sites(const unsigned cha
   const bool hslot = kept_atom && !excluded && r.ht == 1 && __popc(own_h) == 1;
   if (lane < 32) S.hatom[lane] = (unsigned char)(hslot ? __ffs((int)own_h) - 1 : 0);
 
+  const auto at = [&S](int atom) { return ds_vec::widen(S.pos[atom]); };
   // tetrahedral site: kept neighbours + hydrogen slot = 4, no twins among them
   const bool tetra = kept_atom && !excluded && (int)__popc(r.kept_nb) + (hslot ? 1 : 0) == 4 && !(r.kept_nb & twins);
   double V = 0.0;
   bool t_assigned = false;
-  if (tetra) {
-    const Vec x = at(S, lane);
-    bool fin = finite(x);
-    unsigned m = r.kept_nb;
-    auto unit = [&]() {                   // the kept neighbours in ascending index, the hydrogen slot last
-      const int j = m ? __ffs((int)m) - 1 : __ffs((int)own_h) - 1;
-      m &= m - 1u;
-      const Vec y = at(S, j);
-      fin &= finite(y);
-      const Vec d = y - x;
-      return d * (1.0 / sqrt(dot(d, d)));
-    };
-    const Vec u1 = unit(), u2 = unit(), u3 = unit(), u4 = unit();
-    V = dot(u1 - u4, cross(u2 - u4, u3 - u4));
+  if (tetra) {                            // the kept neighbours in ascending index, the hydrogen slot last
+    bool fin;
+    V = ds_sites::tetra_volume(at, lane, r.kept_nb, __ffs((int)own_h) - 1, fin);
     t_assigned = fin && fabs(V) >= min_volume;              // a V that is not a number is below every threshold
   }
   const bool t_positive = t_assigned && V > 0.0;
@@ -191,30 +166,7 @@ __global__ __launch_bounds__(64 * DSM_WAVES) void k_key_sites(const unsigned cha
   const bool ez = end_ok && mate_subs != 0u;
   unsigned res = 0u;
   if (ez && lane < mate) {                // the lower end works the site out for both
-    const Vec xa = at(S, lane), xb = at(S, mate), e = xb - xa;
-    const double ee = dot(e, e);
-    bool good = finite(xa) && finite(xb);
-    unsigned cis = 0u;
-    int k = 0;                             // pair (i-th substituent of a, j-th of b) -> bit i * nt + j
-    const auto atom_of = [&](unsigned word, int end) { return (word & ~HSLOT) ? __ffs((int)(word & ~HSLOT)) - 1 : (int)S.hatom[end]; };
-    const auto rest_of = [](unsigned word) { return (word & ~HSLOT) ? word & (word - 1u) : 0u; };
-    for (unsigned sm = subs; sm; sm = rest_of(sm))
-      for (unsigned tm = mate_subs; tm; tm = rest_of(tm), ++k) {
-        const Vec xs = at(S, atom_of(sm, lane)), xt = at(S, atom_of(tm, mate));
-        const Vec v = xs - xa, w = xt - xb;
-        const Vec pp = v - e * (dot(v, e) / ee), qq = w - e * (dot(w, e) / ee);
-        const double lp = sqrt(dot(pp, pp)), lq = sqrt(dot(qq, qq));
-        const double c = dot(pp, qq) / (lp * lq);
-        good &= finite(xs) && finite(xt) && lp > 0.0 && lq > 0.0 && fabs(c) >= min_planarity;
-        cis |= (c > 0.0 ? 1u : 0u) << k;
-      }
-    const int ns = __popc(subs), nt = __popc(mate_subs);
-    auto bit = [&](int i, int j) { return (cis >> (i * nt + j)) & 1u; };
-    if (ns == 2)
-      for (int j = 0; j < nt; ++j) good &= bit(0, j) != bit(1, j);
-    if (nt == 2)
-      for (int i = 0; i < ns; ++i) good &= bit(i, 0) != bit(i, 1);
-    res = (good ? 1u : 0u) | (cis & 1u) << 1;
+    res = ds_sites::ez_result(at, lane, mate, subs, mate_subs, S.hatom[lane], S.hatom[mate], min_planarity);
     S.ezres[lane] = (unsigned char)res;
   }
   sync();
@@ -263,14 +215,6 @@ struct Pair {                             // arrays of 64 are indexed by lane
   __device__ __forceinline__ const unsigned char* bonds(int side) const { return adj[side]; }
 };
 
-using ds_refine::Ranked;
-using ds_refine::MISMATCH;
-using ds_refine::DISCRETE;
-using ds_refine::CELLS;
-constexpr ds_refine::Block SYNC{};        // one wave per workgroup: the workgroup barrier orders the pair's LDS traffic
-
-__device__ __forceinline__ unsigned half_of(unsigned long long ballot, int side) { return (unsigned)(ballot >> (32 * side)); }
-
 __global__ __launch_bounds__(64) void k_key_identity(const unsigned char* __restrict__ prb_rec, const int32_t* __restrict__ prb_n,
                                                      const unsigned char* __restrict__ ref_rec, const int32_t* __restrict__ ref_n,
                                                      const int64_t* __restrict__ ref_index, int64_t M, const unsigned char* __restrict__ prb_site,
@@ -281,8 +225,8 @@ __global__ __launch_bounds__(64) void k_key_identity(const unsigned char* __rest
   const int64_t p = blockIdx.x;
   const int lane = threadIdx.x, idx = lane & 31, side = lane >> 5;
   const ds_rec::Pair q = ds_rec::pair_of(p, prb_rec, prb_n, ref_rec, ref_n, ref_index, M);
-  int out = DSC_INVALID, used = 0, image = -1;
-  int isos = 0, sames = 0, mirrors = 0, tetra_a = 0, ez_a = 0, open_a = 0, open_b = 0;
+  ds_sites::Found r = {DSC_INVALID, -1, 0, 0, 0, 0};
+  ds_sites::Census c = {0u, false, 0, 0, 0, 0};
   if (q.valid) {
     const int ng = q.n_prb(), nr = q.n_ref();
     ds_rec::load_bonds(S.adj[0], q.prb, ~0u, lane);
@@ -304,12 +248,10 @@ __global__ __launch_bounds__(64) void k_key_identity(const unsigned char* __rest
       for (int j = 0; j < mine_n; ++j) nbr |= (S.adj[side][idx * 32 + j] ? 1u : 0u) << j;
     }
     const int deg = __popc(nbr);
-    const unsigned key = twin_key(here ? deg : 2, __ffs((int)nbr) - 1, type, fc, lane);
+    const unsigned key = ds_sites::twin_key(here ? deg : 2, __ffs((int)nbr) - 1, 0u, type, fc, lane);
     S.key[lane] = key;
     __syncthreads();
-    int ord = 0;
-    if (here)
-      for (int j = 0; j < mine_n; ++j) ord += S.key[side * 32 + j] == key && j < idx;
+    const int ord = here ? ds_sites::count_twins(S.key + side * 32, key, mine_n, idx).ord : 0;
     // a site row that contradicts its record is no site
     const bool hslot = (fl & DSI_FLAG_HSLOT) != 0u;
     const bool centre = here && (fl & DSI_KIND_MASK) == DSI_KIND_CENTRE && deg + (hslot ? 1 : 0) == 4;
@@ -321,114 +263,27 @@ __global__ __launch_bounds__(64) void k_key_identity(const unsigned char* __rest
     const bool assigned_here = (fl & DSI_FLAG_ASSIGNED) != 0u, sign = (fl & DSI_FLAG_SIGN) != 0u;
     const int low = end && kept_subs ? __ffs((int)kept_subs) - 1 : NO_LOW;
     const bool ez_low = end && idx < mate;                   // an E/Z site counts once, at its lower end
-    const unsigned centres = half_of(__ballot(centre), 0);
-    const unsigned long long open = __ballot((centre || ez_low) && !assigned_here);
-    tetra_a = __popc(centres);
-    ez_a = __popc(half_of(__ballot(ez_low), 0));
-    open_a = __popc(half_of(open, 0));
-    open_b = __popc(half_of(open, 1));
-    const bool assigned = open == 0ull;
-    out = DSC_DIFFERENT;
+    c = ds_sites::census(centre, ez_low, (centre || ez_low) && !assigned_here);
+    r.out = DSC_DIFFERENT;
     if (ng == nr) {
-      const int n = ng;
-      const bool active = here;
-      S.type[lane] = (unsigned char)type;
-      S.fc[lane] = (unsigned char)fc;
-      S.ord[lane] = (unsigned char)ord;
-      S.flag[lane] = (unsigned char)(kind | (sign ? DSI_FLAG_SIGN : 0u) | (hslot && kind ? DSI_FLAG_HSLOT : 0u));
-      S.mate[lane] = (unsigned char)mate;
-      S.low[lane] = (unsigned char)low;
-      __syncthreads();
-      // initial colour: (type, charge, ordinal) ranked jointly
-      const Ranked first = ds_refine::rank_jointly<true>(S, (unsigned long long)(type << 16 | fc << 8 | (unsigned)ord), n, lane, SYNC);
-      int colour = active ? first.colour : 0;
-      unsigned long long multi = 0ull;
-      int st = __ballot(active && first.eq_g != first.eq_r) ? MISMATCH : ds_refine::refine<true>(S, colour, active, n, lane, multi, SYNC);
-      int depth = 0;                                         // open levels: S.stack[0 .. depth-1]
-      int first_iso = -1, first_same = -1, first_mirror = -1; // this lane's image under the first isomorphism of each kind
-      bool ended = false;                                    // the search stopped for another reason than the budget
-      const auto same_label = [](int a, int b) { return S.type[a] == S.type[b] && S.fc[a] == S.fc[b] && S.ord[a] == S.ord[b]; };
-      for (int it = 0; it <= max_nodes; ++it) {              // every pass but the last spends one search node
-        if (st == DISCRETE && ds_refine::verify(S, colour, active, n, lane, same_label)) {
-          const int to = active && side == 0 ? S.img[idx] : -1;
-          if (isos++ == 0) first_iso = to;
-          bool same = false;
-          if (assigned) {                                    // the leaf against the site rows, in integers
-            bool off = false, inverted = false, ez_bad = false;
-            if (side == 0 && active) {
-              const unsigned there = S.flag[32 + to];
-              // sites onto sites: the same kind and hydrogen-slot flag at the image (a bijection: B's sites are then all met), the partner's
-              // image the image's partner
-              off = ((there ^ S.flag[lane]) & (DSI_KIND_MASK | DSI_FLAG_HSLOT)) != 0u || (end && S.img[mate] != S.mate[32 + to]);
-              if (centre && !off) {                          // B's sign at the image, times the parity of the order of the images of the kept
-                unsigned m = nbr;                            // neighbours: the hydrogen slot goes to the hydrogen slot, last on both sides
-                const int a = S.img[__ffs((int)m) - 1]; m &= m - 1u;
-                const int b = S.img[__ffs((int)m) - 1]; m &= m - 1u;
-                const int c = S.img[__ffs((int)m) - 1]; m &= m - 1u;
-                const int d = m ? S.img[__ffs((int)m) - 1] : 64;
-                const unsigned odd = (unsigned)((a > b) + (a > c) + (a > d) + (b > c) + (b > d) + (c > d)) & 1u;
-                inverted = (sign ? 1u : 0u) != ((there & DSI_FLAG_SIGN ? 1u : 0u) ^ odd);
-              }
-              if (end && !off) {                             // B's cis bit, flipped for every end whose lowest kept substituent goes elsewhere
-                const int mate_to = S.img[mate], mate_low = S.low[mate];
-                const unsigned flips = (low != NO_LOW && S.img[low] != S.low[32 + to] ? 1u : 0u) ^
-                                       (mate_low != NO_LOW && S.img[mate_low & 31] != S.low[32 + mate_to] ? 1u : 0u);
-                ez_bad = (sign ? 1u : 0u) != ((there & DSI_FLAG_SIGN ? 1u : 0u) ^ flips);
-              }
-            }
-            const bool onto = __ballot(off) == 0ull;
-            const unsigned turned = half_of(__ballot(inverted), 0);
-            const bool ez_kept = __ballot(ez_bad) == 0ull;
-            same = onto && turned == 0u && ez_kept;
-            if (same && sames++ == 0) first_same = to;
-            if (onto && centres != 0u && turned == centres && ez_kept && mirrors++ == 0) first_mirror = to;
-          }
-          if (!exhaustive && (same || !assigned)) { ended = true; break; }
-        }
-        if (st == CELLS) {
-          if (depth >= MA) break;                            // (cannot happen: every level makes one more generated atom a class of its own)
-          ds_refine::open_level(S, depth, colour, active, lane, multi);
-        }
-        const ds_refine::Try t = ds_refine::next_try(S, depth, colour, active, lane);
-        if (t.w < 0) { ended = true; break; }                // nothing left to try anywhere: every isomorphism has been met
-        if (used >= max_nodes) break;                        // the budget does not cover this try: undecided
-        ++used;
-        st = ds_refine::individualise(S, depth, t, colour, active, n, lane, multi);
-      }
-      out = DSC_UNDECIDED;
-      if (ended) {
-        if (isos == 0) out = DSC_DIFFERENT;
-        else if (!assigned) { out = DSC_UNASSIGNED; image = first_iso; }
-        else if (sames) { out = DSC_IDENTICAL; image = first_same; }
-        else if (mirrors) { out = DSC_MIRROR; image = first_mirror; }
-        else { out = DSC_STEREOISOMER; image = first_iso; }
-      }
+      const ds_sites::Node node = {type, fc, ord, nbr, kind, sign, hslot, mate, low};
+      r = ds_sites::search(S, node, ng, lane, c.assigned, c.centres, max_nodes, exhaustive);
     }
   }
-  if (lane < MA) map[p * MA + lane] = image;                 // -1 unless this lane is a generated node and the verdict has a map
-  if (lane < 3) found[p * 3 + lane] = lane == 0 ? isos : lane == 1 ? sames : mirrors;
-  if (lane < 4) sites[p * 4 + lane] = lane == 0 ? tetra_a : lane == 1 ? ez_a : lane == 2 ? open_a : open_b;
-  if (lane == 0) {
-    verdict[p] = (unsigned char)out;
-    nodes[p] = used;
-  }
+  ds_sites::write_out(p, lane, r, c, verdict, nodes, found, sites, map);
 }
 
-static_assert(DSI_MASK_MOBILE_BOND == DSC_NUM_MASKS && DSI_MASK_RING_BOND == DSC_NUM_MASKS + 1 && DSI_NUM_MASKS == DSC_NUM_MASKS + 2 &&
-              DSC_MASK_TETRA_SITE == 0 && DSC_MASK_TETRA_ASSIGNED == 1 && DSC_MASK_TETRA_POSITIVE == 2 && DSC_MASK_EZ_SITE == 3 &&
-              DSC_MASK_EZ_ASSIGNED == 4 && DSC_MASK_EZ_CIS == 5 && DSC_MASK_TWIN == 6, "the order of flags[] in k_key_sites");
+static_assert(DSI_MASK_MOBILE_BOND == DSC_NUM_MASKS && DSI_MASK_RING_BOND == DSC_NUM_MASKS + 1 &&
+              DSI_NUM_MASKS == DSC_NUM_MASKS + 2, "flags[] in k_key_sites: the DSC_MASK_* rows (their order is asserted in ds_sites.h), then these two");
 static_assert(DSI_SITE_BYTES == 2 * MA && DSI_NO_PARTNER >= MA, "a site row is (flags, partner) per node");
 static_assert((DSI_KIND_MASK & (DSI_FLAG_ASSIGNED | DSI_FLAG_SIGN | DSI_FLAG_HSLOT)) == 0 && DSI_KIND_CENTRE <= DSI_KIND_MASK && DSI_KIND_END <= DSI_KIND_MASK,
               "the fields of a flags byte are apart");
-static_assert(MA <= 29, "bits 29..31 of an atom mask are free: HSLOT, NO_LOW");
-
-bool thresholds_ok(double min_volume, double min_planarity) { return min_volume >= 0.0 && min_planarity >= 0.0; }   // false for a NaN
 
 }  // namespace
 
 extern "C" int dsi_key_sites(const uint8_t* rec, const int32_t* n, int64_t P, int32_t max_nodes, double min_volume, double min_planarity,
                              uint8_t* site, int32_t* masks, double* volume, int32_t* nodes, uint8_t* status, void* stream) {
-  const bool scalars_ok = max_nodes >= 1 && max_nodes <= DSM_MAX_NODES && thresholds_ok(min_volume, min_planarity);
+  const bool scalars_ok = max_nodes >= 1 && max_nodes <= DSM_MAX_NODES && ds_sites::thresholds_ok(min_volume, min_planarity);
   const int go = ds_rec::check_table(scalars_ok, P, rec, n, {site, masks, volume, nodes, status});
   if (go != ds_rec::LAUNCH) return go;
   hipLaunchKernelGGL(k_key_sites, dim3((unsigned)((P + DSM_WAVES - 1) / DSM_WAVES)), dim3(64 * DSM_WAVES), 0, (hipStream_t)stream, rec, n, P,

@@ -1,6 +1,7 @@
 // diffspectra_amd - colour refinement of molecular graphs, shared by the pair kernels (two molecules at once, one per half wave: PAIR = true;
-// k_graph_identity in ds_graph.hip, k_stereo_identity in ds_stereo.hip and k_key_identity in ds_key.hip) and ds_smiles.hip (one molecule per wave, atoms in lanes 0..28:
-// PAIR = false), and below it the individualise-and-refine search that those pair kernels run.  The signature and its order are those of
+// k_graph_identity in ds_graph.hip; k_stereo_identity in ds_stereo.hip and k_key_identity in ds_key.hip through ds_sites.h) and ds_smiles.hip
+// (one molecule per wave, atoms in lanes 0..28: PAIR = false), and below it the pieces of the individualise-and-refine search that those pair
+// kernels run: k_graph_identity's own loop stops at its first leaf, ds_sites::search goes on and tests every leaf against the stereo sites.  The signature and its order are those of
 // include/diffspectra_smiles.h: the atom's colour in the top 6 bits (so a round only ever splits classes), below it the commutative sum over
 // its bonded neighbours j of fmix(colour_j + 1) * (2 bond_ij + 1), shifted right by 6.
 //
@@ -100,7 +101,7 @@ __device__ __forceinline__ int refine(Store& S, int& colour, bool active, int n,
 
 // ---------------------------------------------------------------------------------------------------------------------- the pair search
 // Depth-first individualisation over the joint refinement, one wave64 per pair and one wave per workgroup (Block).  The loop that joins the
-// pieces stays in the kernel (k_graph_identity has the plainest), with its own leaf action and its own meaning for the three ways out: per
+// pieces stays with the caller (k_graph_identity has the plainest, ds_sites::search the enumerating one), with its own leaf action and its own meaning for the three ways out: per
 // pass a leaf test, open_level() if the colouring has cells, next_try(), then "exhausted" (t.w < 0), the budget test, ++used, individualise().
 // What the kernels' verdicts lean on is kept true here:
 //   a leaf counts only after verify() has compared every label and every bond byte under an explicit bijection;

@@ -1248,10 +1248,13 @@ __global__ __launch_bounds__(512) void k_node_update64(Ctx c, int blk) {
 
 // Block stage E (pairs): h_edge = node2edge(h_a + h_b), gated residual, LN, modulate, FF(64->128->64), gated residual,
 // readout slice (64->16), edge+dist part of equi_update.input_lin (128->256).  dmt.py:156-157,165-169,388.
-// ROW-PARALLEL: every wave owns 32 pair rows from staging to the last store, with wave-private LDS tiles and NO workgroup
+// ROW-PARALLEL up to the split-fp16 rewrite of e_out: every wave owns 32 pair rows, with wave-private LDS tiles and no workgroup
 // barrier (the five barrier-separated GEMM phases of the tile-parallel form cost ~15k cycles of dead time each).  The FF is
 // chained in registers: FF3 is computed transposed (lane = row, registers = hidden features) and its SiLU'd accumulators
 // are the B operand of the FF4 MFMAs; the gated residual is applied in that transposed layout with 16-byte LDS accesses.
+// ONE workgroup barrier follows, and the ed product (the kernel's largest weight stream: 128 kB per pass) is CO-OPERATIVE: the four
+// wave tiles are one contiguous 128-row split-fp16 operand, wave w computes column chunks 2w, 2w+1 for all of it, so every ed weight
+// fragment is fetched once per 128 rows instead of once per 32: -8 % per launch, same bits (profiles/HISTORY.md, round 8).
 __global__ __launch_bounds__(256, 2) void k_edge_update(Ctx c, int blk) {
   ds_fp16_saturate();
   DS_STAMP_INIT();   // diagnostic build (tools/stamp_attn.py k_edge_update): wave 0's cycles per stage
@@ -1268,9 +1271,10 @@ __global__ __launch_bounds__(256, 2) void k_edge_update(Ctx c, int blk) {
   int* rpa = idx_s[wave][1];
   int* rpb = idx_s[wave][2];
   const int Pp = c.L.Pp;
-  const int row0 = (blockIdx.x * 4 + wave) * R;
-  if (row0 >= Pp) return;                    // whole wave leaves; nothing below synchronises across waves
-  const int valid = min(R, Pp - row0);
+  const int wg_row0 = blockIdx.x * 4 * R, row0 = wg_row0 + wave * R;
+  // A wave whose tile lies wholly behind Pp does NOT leave: it runs as a tile of zero valid rows (clamped gathers, zero operand rows, every
+  // store guarded off), so its LDS tile is defined, it reaches the workgroup barrier and it takes its two chunks of the ed product.
+  const int valid = max(0, min(R, Pp - row0));
   const float* ada = c.ws.ada + blk * DS_ADA_BLOCK_STRIDE + DS_ADA_EDGE;
   if (lane < R) {
     const int p = min(row0 + lane, Pp - 1);
@@ -1427,6 +1431,14 @@ __global__ __launch_bounds__(256, 2) void k_edge_update(Ctx c, int blk) {
     }
   }
   DS_STAMP(4);
+  // the ed weights depend on nothing the workgroup computes: this wave's first ED_PF k-blocks are requested here, ahead of the rewrite and
+  // of the barrier, and the ring then runs ED_PF blocks ahead through both of the wave's chunks (16 k-blocks in one stream).
+  // Measured 2 / 4 / 6 / 8 (183 / 191 / 203 / 219 VGPRs): all inside the run-to-run spread (profiles/r08_edge_update_ab.txt).
+  constexpr int ED_PF = 4;
+  const float* Wd = BW(c, blk, DS_BW_ED_H);
+  const WStreamH wsd[2] = {wstream_h(Wd, 256, 128, (2 * wave) * 32), wstream_h(Wd, 256, 128, (2 * wave + 1) * 32)};
+  WRingH<ED_PF> ring;
+  wring_h<ED_PF>(ring, wsd[0], 0);
   {
     float4 v[8];
 #pragma unroll
@@ -1437,24 +1449,59 @@ __global__ __launch_bounds__(256, 2) void k_edge_update(Ctx c, int blk) {
     for (int u = 0; u < 8; ++u) split_store4(E2h + ((lane + u * 64) >> 4) * LDW2, 64, 4 * (lane & 15), v[u]);
   }
   DS_STAMP(5);
+  // ---- the one workgroup barrier: behind it the four wave tiles are ONE 128-row split-fp16 operand (E2s and Ds are contiguous, a row
+  //      is 272 bytes in both views) that nothing writes any more, so no second barrier follows.  Every wave reaches it (see `valid`).
+  __syncthreads();
+  DS_STAMP(6);
+  // ---- co-operative ed phase: wave w owns column chunks 2w, 2w+1 for all four row tiles, so a weight fragment pair (hi, lo plane) is
+  //      loaded once per 128 rows and feeds 4 x 3 MFMAs.  Per element the k order (e_out k-blocks 0-3, then the features 4-7) and the
+  //      order of the MFMAs into each accumulator (hi: x1 w1; lo: x2 w1, then x1 w2) are those of the one-tile product: the same bits.
   {
     const float* bd = BW(c, blk, DS_BW_ED_B);
-    const float* Wd = BW(c, blk, DS_BW_ED_H);
-    float* ed = c.ws.ed + (size_t)row0 * 256;
-    for (int ch = 0; ch < 8; ++ch) {
-      asm volatile("" ::: "memory");
-      f32x16 acc[1], lo[1];
+    const _Float16* xe = reinterpret_cast<const _Float16*>(&E2s[0][0][0]) + r31 * LDW2 + 8 * hh;
+    const _Float16* xd = reinterpret_cast<const _Float16*>(&Ds[0][0][0]) + r31 * LDW2 + 8 * hh;
+    float* ed = c.ws.ed + (size_t)wg_row0 * 256;
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+      const int ch = 2 * wave + c2;
+      f32x16 acc[4], lo[4];
       const float b = bd[ch * 32 + r31];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[0][i] = b;   // accumulate onto the bias: no epilogue arithmetic left
-      acc_zero<1>(lo);
-      wave_mma_h<1>(E2h, 64, Wd, 256, 128, ch * 32, 0, 4, acc, lo);
-      wave_mma_h<1>(Dh, 64, Wd, 256, 128, ch * 32, 4, 8, acc, lo, 4);
-      split_finish<1>(acc, lo);
-      acc_store<1, 256>(acc, ed + ch * 32, valid, [](int, float v) { return v; });
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[m][i] = b;   // accumulate onto the bias: no epilogue arithmetic left
+      acc_zero<4>(lo);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        __builtin_amdgcn_sched_barrier(0);
+        const _Float16* xr = (i < 4 ? xe : xd) + (i & 3) * 16;
+        h8 x1[4], x2[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          x1[m] = *reinterpret_cast<const h8*>(xr + m * R * LDW2);
+          x2[m] = *reinterpret_cast<const h8*>(xr + m * R * LDW2 + 64);
+        }
+        const h8 w1 = ring.w1[i % ED_PF], w2 = ring.w2[i % ED_PF];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) lo[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x2[m], w1, lo[m], 0, 0, 0);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1[m], w1, acc[m], 0, 0, 0);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) lo[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1[m], w2, lo[m], 0, 0, 0);
+        // the slot just consumed takes the block ED_PF ahead in the wave's stream: the rest of this chunk, then the next chunk's first
+        // blocks (in flight under this chunk's stores)
+        if (i + ED_PF < 8) {
+          ring.w1[i % ED_PF] = wload_h(wsd[c2], 0, i + ED_PF); ring.w2[i % ED_PF] = wload_h(wsd[c2], 1, i + ED_PF);
+        } else if (c2 == 0) {
+          ring.w1[i % ED_PF] = wload_h(wsd[1], 0, i + ED_PF - 8); ring.w2[i % ED_PF] = wload_h(wsd[1], 1, i + ED_PF - 8);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      split_finish<4>(acc, lo);
+      acc_store<4, 256>(acc, ed + ch * 32, Pp - wg_row0, [](int, float v) { return v; });   // rows at or behind Pp are never stored
     }
   }
-  DS_STAMP(6);
+  DS_STAMP(7);
   DS_STAMP_FLUSH(0);
 }
 

@@ -5,6 +5,8 @@
 consumer: P0 prologue | P1 wait for the first tile | P2 logits, P3 barrier | P4 softmax phase | P5 alpha rows + first tile | P6 visits, P7 barrier
 producer: P8 prologue | P9 first projection | P10 commit + fetch + projection, P11 barrier | P12 softmax phase | P13 first projection |
           P14 commit + fetch + projection, P15 barrier
+k_edge_update (wave 0): P0 pair indices | P1 gathers, LayerNorm, RBF, staging | P2 FF | P3 gated residual, e_out store | P4 readout slice |
+          P5 first ed weight requests, split-fp16 rewrite | P6 the workgroup barrier | P7 co-operative ed product and stores
 Development tool, never part of the product build.
 """
 import os

@@ -65,6 +65,7 @@ def load_library() -> C.CDLL:
     abi.MOBILE.bind(lib)
     abi.KEY.bind(lib)
     abi.FRAGGLE.bind(lib)
+    abi.RMSD.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
     sizes = (C.c_int64 * 4)()
@@ -1167,6 +1168,38 @@ def key_identity_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, prb_site: t
                         also=(prb_site, ref_site))
 
 
+# ----------------------------------------------------------------------------------------- symmetry-corrected Kabsch RMSD
+
+RMSD_CONSTS = abi.RMSD.consts             # include/diffspectra_rmsd.h
+RMSD_DIFFERENT, RMSD_DECIDED, RMSD_UNDECIDED, RMSD_INVALID = (RMSD_CONSTS["DSR_" + k] for k in ("DIFFERENT", "DECIDED", "UNDECIDED", "INVALID"))
+RMSD_ATOMS = {"heavy": RMSD_CONSTS["DSR_ATOMS_HEAVY"], "all": RMSD_CONSTS["DSR_ATOMS_ALL"]}
+
+
+def _rmsd_atoms(atoms) -> int:
+    """``'heavy'`` / ``'all'`` as the header's ``DSR_ATOMS_*`` number."""
+    if not isinstance(atoms, str) or atoms not in RMSD_ATOMS:
+        raise ValueError(f"atoms must be 'heavy' or 'all', got {atoms!r}")
+    return RMSD_ATOMS[atoms]
+
+
+def best_rmsd_records(prb_rec: torch.Tensor, prb_n: torch.Tensor, ref_rec: torch.Tensor, ref_n: torch.Tensor,
+                      ref_index: Optional[torch.Tensor] = None, max_nodes: int = 4096, atoms="heavy"):
+    """``dsr_best_rmsd_records``: the smallest Kabsch RMSD over ALL graph isomorphisms between the generated molecule and its ground truth of
+    each of P pairs, for a rotation and for the mirror image (every definition in ``include/diffspectra_rmsd.h``: the selection ``atoms`` -
+    ``'heavy'``: type byte not 0, ``'all'`` -, the trace formula, the twins of hydrogen leaves, the verdicts).
+
+    The tensors are those of ``match_records``.  Returns the device tensors ``(verdict [P] u8, rmsd [P, 2] f64, count [P] i32, nodes [P] i32,
+    found [P] i32, map [P, 2, 29] i32)``, enqueued on the current stream without synchronising: verdict ``RMSD_DIFFERENT`` (0: no isomorphism,
+    proven), ``RMSD_DECIDED`` (1: ``rmsd[:, 0]`` / ``rmsd[:, 1]`` are the minima of the proper / improper fit over every isomorphism and ``map``
+    holds the two isomorphisms that attain them), ``RMSD_UNDECIDED`` (2: the search needed more than ``max_nodes`` tries) or ``RMSD_INVALID`` (3);
+    for every verdict but 1 ``rmsd`` is NaN and ``map`` -1.  ``count`` = selected atoms of the generated molecule, ``found`` = isomorphisms met.
+    An exact copy scores around 1e-7, not 0 (the trace formula).  The arguments are checked, never converted."""
+    return _record_call("best_rmsd_records", [(prb_rec, prb_n), (ref_rec, ref_n)], ref_index,
+                        [_node_budget(max_nodes, GRAPH_MAX_NODES), _rmsd_atoms(atoms)],
+                        [(torch.uint8, ()), (torch.float64, (2,)), (torch.int32, ()), (torch.int32, ()), (torch.int32, ()), (torch.int32, (2, MAX_ATOMS))],
+                        prefix="dsr_")
+
+
 # ----------------------------------------------------------------------------------------- engine
 
 class DmtEngine:
@@ -1421,6 +1454,10 @@ class DmtEngine:
                                 min_planarity=None, exhaustive: bool = False):
         """``engine.stereo_identity_records`` on this engine's library (the comparison needs no weights)."""
         return stereo_identity_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, max_nodes, min_volume, min_planarity, exhaustive)
+
+    def best_rmsd_records(self, prb_rec, prb_n, ref_rec, ref_n, ref_index=None, max_nodes: int = 4096, atoms="heavy"):
+        """``engine.best_rmsd_records`` on this engine's library (the fit needs no weights)."""
+        return best_rmsd_records(prb_rec, prb_n, ref_rec, ref_n, ref_index, max_nodes, atoms)
 
     def stereo_sites(self, rec, n, min_volume=None, min_planarity=None):
         """``engine.stereo_sites`` on this engine's library (the perception needs no weights)."""

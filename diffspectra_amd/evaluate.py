@@ -208,6 +208,31 @@ def _key_summary(run, table, top_k: int, max_nodes: int = 4096, min_volume: Opti
     return entry
 
 
+BEST_RMSD_THRESHOLDS = (0.1, 0.25, 0.5, 1.0)      # Angstrom; definitions of "close", not measurements
+
+
+def _best_rmsd_summary(run, table, top_k: int, atoms: str = "heavy", max_nodes: int = 4096, thresholds=BEST_RMSD_THRESHOLDS) -> Dict:
+    """How good the geometry of every hit of one finished run is (the pairs of ``_structure_summary``): ``best_rmsd_batch`` per slot, the
+    smallest Kabsch RMSD over all graph isomorphisms.  A HIT is a slot with verdict 1; ``mean`` / ``median`` / ``within`` are over the hits
+    with a finite value (``None`` / empty shares without any).  The ``thresholds`` of ``within`` are definitions, not measurements: nobody
+    has measured where the values of generated molecules fall."""
+    from .structure_metrics import best_rmsd_batch, topk_best_rmsd
+    dev = run.records_by_slot.device
+    ref, prb = (table.gt_records.to(dev), table.num_atom), (run.records_by_slot, torch.tensor(run.n_atoms))
+    best = best_rmsd_batch(ref, prb, ref_index=run.slot_ds, atoms=atoms, max_nodes=max_nodes, engine=run.eng)
+    hit = best.verdict == 1
+    proper = best.rmsd[:, 0]
+    values = proper[hit & torch.isfinite(proper)].cpu()                # (summed on the host: one order of summation everywhere)
+    n = values.numel()
+    entry = dict(verdict=best.verdict, rmsd=best.rmsd, hits=int(hit.sum()), undecided=int((best.verdict == 2).sum()),
+                 invalid=int((best.verdict == 3).sum()), mean=float(values.mean()) if n else None, median=float(values.median()) if n else None,
+                 mirror_better=int(best.mirror_better.sum()),
+                 within={float(t): float((values < float(t)).double().mean()) if n else None for t in thresholds})
+    if top_k > 1:
+        entry["top_k"] = topk_best_rmsd(best, top_k)
+    return entry
+
+
 def _scaffold_summary(run, table, top_k: int, scaffold_fn, min_rings: int) -> Dict:
     """The "Scaf" number of one finished run against the test table (``scaffold_fn``: ``get_scaffold_metric`` of its records) and, over the
     pairs of ``_structure_summary``, whether every generated molecule shares the scaffold of its ground truth."""
@@ -379,6 +404,18 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
     ``sites`` and, with K > 1, ``top_k``.  ``config.eval.key_max_nodes`` replaces the budget of 4096; the thresholds are those of ``stereo``.
     Every rule restates InChI as remembered: the number is unpinned against InChI.  Without the flag the dict has no such key.
 
+    With ``config.eval.best_rmsd`` true ``metrics['structure']['best_rmsd']`` says how good the geometry of every hit is: the smallest Kabsch
+    RMSD over ALL graph isomorphisms between the generated molecule and its ground truth (``structure_metrics.best_rmsd_batch``;
+    ``include/diffspectra_rmsd.h``; what RDKit's ``GetBestRMS`` and ``spyrmsd`` compute, where ``rmsd_list`` above is the reference's Hungarian
+    match): ``verdict`` (u8 device tensor, one per slot: 0 no isomorphism, 1 a hit with its values, 2 undecided, 3 invalid), ``rmsd`` (f64 device
+    tensor [slots, 2]: the best fit by a rotation and the best fit of the mirror image, NaN unless verdict 1), ``hits``, ``undecided`` and
+    ``invalid`` (counts, which with the slots of verdict 0 add up to the slots), ``mean`` and ``median`` (of the proper value over the hits with a
+    finite one, ``None`` without any), ``mirror_better`` (hits whose mirror image fits better), ``within`` (``{threshold: share of those hits
+    below it}`` for ``config.eval.best_rmsd_thresholds``, default 0.1, 0.25, 0.5 and 1.0 Angstrom: definitions of "close", not measurements -
+    nobody has measured where generated molecules fall) and, with K > 1, ``top_k = topk_best_rmsd(...)``.  ``config.eval.best_rmsd_atoms``
+    (``'heavy'``, the default, or ``'all'``) and ``config.eval.best_rmsd_max_nodes`` (4096) pass through.  Unpinned against RDKit / spyrmsd, no
+    mass weighting, the ``'all'`` mode is bound by the budget.  Without the flag the dict has no such key.
+
     With ``config.eval.smiles`` true ``metrics['structure']['smiles']`` holds the molecules as text, where the reference calls ``Chem.MolToSmiles``
     (``run_lib.py:111-112``, ``compute_metrics.py:73-78,209-220``; ``dsl_smiles_records``): ``generated`` (one canonical SMILES string per slot,
     ``None`` for an overflow or unusable record), ``ground_truth`` (the string of every slot's ground truth), ``same`` / ``status`` / ``pair_status``
@@ -449,6 +486,10 @@ def diffspectra_evaluate(config, workdir: str, test_ds=None, eval_folder: str = 
                 metrics["structure"]["key"] = _key_summary(run, test_ds, top_k, int(getattr(config.eval, "key_max_nodes", 4096)),
                                                            getattr(config.eval, "stereo_min_volume", None),
                                                            getattr(config.eval, "stereo_min_planarity", None))
+            if getattr(config.eval, "best_rmsd", False):
+                metrics["structure"]["best_rmsd"] = _best_rmsd_summary(run, test_ds, top_k, getattr(config.eval, "best_rmsd_atoms", "heavy"),
+                                                                       int(getattr(config.eval, "best_rmsd_max_nodes", 4096)),
+                                                                       tuple(getattr(config.eval, "best_rmsd_thresholds", BEST_RMSD_THRESHOLDS)))
             if getattr(config.eval, "sub_geometry", False):
                 from .structure_metrics import get_sub_geometry_metric
                 if geometry_fn is None:

@@ -99,6 +99,11 @@ fragmented by one to three cuts, every fragmentation marks the atoms of both mol
 marked pair's path fingerprints, or the plain one if larger, is the similarity; ``fraggle_fragmentations`` and ``path_fingerprints`` show the
 parts.  The rule restates RDKit's Fraggle as remembered with the project's own fingerprint hash: parity with RDKit is unpinned.
 
+How good the geometry of a hit is says ``best_rmsd_batch`` / ``topk_best_rmsd`` (``dsr_best_rmsd_records``, ``csrc/ds_bestrmsd.hip``; every
+definition in ``include/diffspectra_rmsd.h``): the smallest Kabsch RMSD over all graph isomorphisms of the pair, what RDKit's ``GetBestRMS``
+and ``spyrmsd`` compute, with the best fit of the mirror image beside it.  Unlike the Hungarian-matched RMSD above it is rotation invariant
+and bond consistent, and symmetry cannot inflate it.  Unpinned against RDKit / spyrmsd, no mass weighting.
+
 One rule restates RDKit behaviour that cannot be executed here (RDKit is absent): among equally large fragments the one holding the lowest
 atom index wins (``Chem.GetMolFrags`` lists fragments by their first atom, Python's ``max`` keeps the first maximum, ``rmsd.py:84-86``).
 """
@@ -1811,3 +1816,59 @@ def key_identity_batch(ref, prb, ref_index=None, max_nodes: int = 4096, min_volu
         p_at, slot = mapped.nonzero(as_tuple=True)
         out[p_at, p_src[p_at, slot].to(torch.int64)] = target[p_at, slot]
     return KeyIdentity(verdict, nodes, found, sites, out, strict, layer, p_st, ref_status)
+
+
+# ------------------------------------------------------------------------------------------------------------------ symmetry-corrected Kabsch RMSD
+
+class BestRmsd(NamedTuple):
+    """Per-pair device tensors of ``dsr_best_rmsd_records``."""
+    verdict: torch.Tensor     # [P] u8: 0 no isomorphism (proven), 1 decided, 2 undecided (budget), 3 invalid row (as ``GraphIdentity``)
+    rmsd: torch.Tensor        # [P, 2] f64 the smallest proper / improper (mirror image) Kabsch RMSD over every isomorphism; NaN unless verdict 1
+    count: torch.Tensor       # [P] i32 selected atoms of the generated molecule
+    nodes: torch.Tensor       # [P] i32 search nodes used
+    found: torch.Tensor       # [P] i32 isomorphisms met
+    map: torch.Tensor         # [P, 2, 29] i32 the isomorphisms behind the two values (ground-truth atom of every generated atom), else -1
+
+    @property
+    def decided(self) -> torch.Tensor:
+        return self.verdict == 1
+
+    @property
+    def undecided(self) -> torch.Tensor:
+        return self.verdict == 2
+
+    @property
+    def mirror_better(self) -> torch.Tensor:
+        """The mirror image of the generated molecule fits the ground truth better than the molecule itself."""
+        return (self.verdict == 1) & (self.rmsd[:, 1] < self.rmsd[:, 0])
+
+
+def best_rmsd_batch(ref, prb, ref_index=None, atoms: str = "heavy", max_nodes: int = 4096, engine=None) -> BestRmsd:
+    """How good the geometry of every hit is: the smallest Kabsch RMSD over ALL graph isomorphisms between every generated molecule and its
+    ground truth (``dsr_best_rmsd_records``; every definition in ``include/diffspectra_rmsd.h``), what RDKit's ``GetBestRMS`` and ``spyrmsd``
+    compute - rotation invariant, bond consistent, and symmetry (methyl groups, CF2, benzene, cubane) cannot inflate it - with the value of the
+    best fit of the mirror image beside it.  ``atoms``: ``'heavy'`` (type not 0; twin hydrogens are not permuted) or ``'all'`` (every
+    isomorphism is enumerated: ``max_nodes`` decides).  Stated deviations: unpinned against RDKit / spyrmsd, no mass weighting.  ``ref`` and
+    ``prb`` are ``(records [*, 1248] u8, n_atoms [*])`` pairs on the GPU, ground truth first as in ``graph_identity_batch``; ``ref_index [P]``
+    names the ground-truth row of every generated molecule (``None``: row p).  Device tensors, no synchronisation."""
+    return BestRmsd(*_pair_call("best_rmsd_records", engine, ref, prb, ref_index, max_nodes, atoms))
+
+
+def topk_best_rmsd(best, top_k: int) -> Dict[str, torch.Tensor]:
+    """Best-of-K reductions over the K consecutive candidates of every spectrum from a ``BestRmsd`` (or any object / dict with ``verdict [S*K]``
+    and ``rmsd [S*K, 2]``): ``hit [S] bool`` (a candidate is the ground-truth graph: verdict 1), ``best_rmsd [S] f64`` (the lowest proper RMSD
+    among the spectrum's hits with a value, NaN if none), ``best_index [S] i64`` (that candidate, -1 if none) and ``undecided`` (0-dim i64
+    count).  Plain torch reductions on the tensors' device."""
+    get = (lambda k: best[k]) if isinstance(best, dict) else (lambda k: getattr(best, k))
+    verdict, rmsd = get("verdict"), get("rmsd")
+    if top_k < 1 or verdict.numel() % top_k:
+        raise ValueError(f"{verdict.numel()} pairs are not a whole number of top_k = {top_k} groups")
+    same = (verdict == 1).reshape(-1, top_k)
+    r = rmsd[:, 0].reshape(-1, top_k).to(torch.float64)
+    bad = torch.isnan(r) | ~same
+    filled = torch.where(bad, torch.full_like(r, float("inf")), r)
+    value, arg = filled.min(dim=1)
+    none = bad.all(dim=1)
+    value = torch.where(none, torch.full_like(value, float("nan")), value)
+    arg = torch.where(none, torch.full_like(arg, -1), arg)
+    return dict(hit=same.any(dim=1), best_rmsd=value, best_index=arg, undecided=(verdict == 2).sum())

@@ -66,6 +66,7 @@ def load_library() -> C.CDLL:
     abi.KEY.bind(lib)
     abi.FRAGGLE.bind(lib)
     abi.RMSD.bind(lib)
+    abi.READER.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
     sizes = (C.c_int64 * 4)()
@@ -1042,6 +1043,43 @@ def smiles_records(rec: torch.Tensor, n: torch.Tensor, max_nodes: int = 4096):
                         [(torch.uint8, (SMILES_TEXT_BYTES,)), (torch.int32, ()), (torch.uint8, ()), (torch.int32, ()), _MAP], prefix="dsl_")
 
 
+# ----------------------------------------------------------------------------------------- SMILES reader
+
+READER_CONSTS = abi.READER.consts         # include/diffspectra_reader.h
+READER_STATUSES = ("OK", "EMPTY", "SYNTAX", "ELEMENT", "KEKULE", "TOO_LARGE", "UNDECIDED", "TOO_LONG")
+READER_OK, READER_EMPTY, READER_SYNTAX, READER_ELEMENT, READER_KEKULE, READER_TOO_LARGE, READER_UNDECIDED, READER_TOO_LONG = \
+    (READER_CONSTS["DSP_" + k] for k in READER_STATUSES)
+READER_TEXT_BYTES, READER_WAVES = READER_CONSTS["DSP_TEXT_BYTES"], READER_CONSTS["DSP_WAVES"]
+
+
+def read_smiles(text: torch.Tensor, length: torch.Tensor, max_nodes: int = 4096):
+    """``dsp_read_smiles``: the result record of every SMILES string (every definition in ``include/diffspectra_reader.h``: the accepted
+    OpenSMILES subset, the first error and its offset, aromatic bonds as ring bonds between lower-case atoms, the first Kekule structure of a
+    stated depth-first order, implied hydrogens appended behind the atoms of the string; not RDKit's reader).
+
+    ``text [P, stride] u8`` (ASCII rows; the stride a multiple of 4 in [4, 384]), ``length [P] i32`` -> the device tensors ``(rec [P, 1248] u8,
+    n [P] i32, status [P] u8, where [P] i32, string_atoms [P] i32, flags [P] u32-as-i32, aromatic [P] u32-as-i32, atom_pos [P, 29] i32, nodes
+    [P] i32)`` on the current stream without synchronising; status ``READER_OK`` (0) .. ``READER_TOO_LONG`` (7); unless it is 0 the record is
+    zero and ``n`` is 0.  Checked, never converted; no CPU path."""
+    _want(text, "text", torch.uint8, (None, None))
+    P, stride = text.shape
+    if stride % 4 or not 4 <= stride <= READER_TEXT_BYTES:
+        raise ValueError(f"text must have a stride that is a multiple of 4 in [4, {READER_TEXT_BYTES}], got {stride}")
+    _want(length, "length", torch.int32, (P,))
+    max_nodes = _node_budget(max_nodes, GRAPH_MAX_NODES)
+    dev = text.device
+    if dev.type != "cuda" or length.device != dev:
+        raise RuntimeError("read_smiles needs all its tensors on one HIP device (torch device type 'cuda'); there is no CPU path")
+    lib = load_library()
+    i32 = lambda *shape: torch.empty(P, *shape, dtype=torch.int32, device=dev)
+    out = (torch.empty(P, RECORD_BYTES, dtype=torch.uint8, device=dev), i32(), torch.empty(P, dtype=torch.uint8, device=dev), i32(), i32(), i32(),
+           i32(), i32(MAX_ATOMS), i32())
+    with torch.cuda.device(dev):
+        st = lib.dsp_read_smiles(ptr(text), stride, ptr(length), P, max_nodes, *(ptr(t) for t in out), _stream())
+    _check(st, "dsp_read_smiles")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- substructure queries
 
 SUBSTRUCTURE_CONSTS = abi.SUBSTRUCTURE.consts       # include/diffspectra_substructure.h
@@ -1445,6 +1483,10 @@ class DmtEngine:
     def smiles_records(self, rec, n, max_nodes: int = 4096):
         """``engine.smiles_records`` on this engine's library (the strings need no weights)."""
         return smiles_records(rec, n, max_nodes)
+
+    def read_smiles(self, text, length, max_nodes: int = 4096):
+        """``engine.read_smiles`` on this engine's library (the reader needs no weights)."""
+        return read_smiles(text, length, max_nodes)
 
     def substructure_records(self, rec, n, patterns, max_nodes: int = SUBSTRUCTURE_DEFAULT_NODES):
         """``engine.substructure_records`` on this engine's library (the matcher needs no weights)."""

@@ -87,6 +87,13 @@ What the molecules are as TEXT is ``smiles`` / ``smiles_strings``: one canonical
 molecules, never as text, with strings from elsewhere); the graph is the constitution-level one of ``graph_identity_batch`` with raw charge
 bytes; Kekule orders only, so two drawings of a ring give one string only where a symmetry maps one onto the other; any SMILES reader reads them.
 
+The way in FROM text is ``read_smiles`` / ``records_from_smiles`` / ``pack_smiles``: one result record per SMILES string (``dsp_read_smiles``,
+``csrc/ds_reader.hip``; every definition in ``include/diffspectra_reader.h``), which is what the reference gets from ``Chem.MolFromSmiles``
+(``compute_metrics.py:96-114,147-317``, ``evaluation/rdkit_metric.py:86``); ``text_metrics`` builds the reference's metric table for text pairs on
+it.  Deviations: an OpenSMILES subset over H, C, N, O, F, not RDKit's reader (parity unpinned); no sanitisation (``valence_batch`` checks the
+record); stereo marks, isotopes and classes are read and dropped with a flag; lower-case input gets the first Kekule structure of a stated
+search; positions are zero, so nothing that reads geometry applies to a read record.
+
 Whether a molecule contains a substructure, how many times and on which atoms is ``substructure_search`` (``dsq_match_records``,
 ``csrc/ds_substructure.hip``; every definition in ``include/diffspectra_substructure.h``): patterns are data, a SMARTS subset compiled by
 ``smarts.py``.  On top of it ``maccs_keys`` / ``maccs_similarity_batch`` / ``topk_maccs`` give the 166 MACCS keys and the reference's "Tanimoto
@@ -1252,6 +1259,70 @@ def smiles_exact_match(ref, prb, ref_index=None, max_nodes: int = 4096, engine=N
     status = torch.where(inside, torch.maximum(r_status, g.status), torch.full_like(g.status, 3))
     same = (status == 0) & (r_text == g.text).all(dim=1)
     return SmilesMatch(same, status)
+
+
+# ------------------------------------------------------------------------------------------------------------------ SMILES reader
+
+READER_STATUS_NAMES = ("ok", "empty", "syntax", "element", "kekule", "too large", "undecided", "too long")      # by DSP_* status
+
+
+class SmilesRecords(NamedTuple):
+    """Per-string device tensors of ``dsp_read_smiles``."""
+    records: torch.Tensor         # [P, 1248] u8: the record; zero unless status 0
+    n_atoms: torch.Tensor         # [P] i32: atoms of the record; 0 unless status 0
+    status: torch.Tensor          # [P] u8: index into ``READER_STATUS_NAMES``
+    where: torch.Tensor           # [P] i32: offset of the first offending byte (syntax, element, kekule), else -1
+    string_atoms: torch.Tensor    # [P] i32: atoms written in the string (ok, too large, kekule, undecided; else 0)
+    flags: torch.Tensor           # [P] i32: bit 0 isotope, 1 '@', 2 '/' '\', 3 atom class (read and ignored), 4 lower-case atoms
+    aromatic: torch.Tensor        # [P] i32: bit i = record atom i was written in lower case
+    atom_pos: torch.Tensor        # [P, 29] i32: offset of record atom i's symbol; -1 for appended hydrogens and atoms >= n
+    nodes: torch.Tensor           # [P] i32: tries of the Kekule search
+
+    @property
+    def ok(self) -> torch.Tensor:
+        return self.status == 0
+
+
+def pack_smiles(strings: Sequence[str], device=None):
+    """``(text [P, 384] u8, length [P] i32)`` of Python strings, packed on the host in one numpy pass: surrounding whitespace is stripped, a
+    string longer than 384 bytes keeps its true length (the kernel reports it as too long) and a non-ASCII character becomes byte 0xFF
+    (which the kernel reports as a syntax error)."""
+    import numpy as np
+    from . import engine as E
+    width = E.READER_TEXT_BYTES
+    rows = [(t if t.isascii() else "".join(c if c.isascii() else "\xff" for c in t)).encode("latin-1") for t in (s.strip() for s in strings)]
+    length = np.fromiter((len(r) for r in rows), np.int32, len(rows))
+    flat = np.frombuffer(b"".join(r[:width].ljust(width, b"\0") for r in rows), np.uint8)
+    text = torch.from_numpy(flat.reshape(len(rows), width).copy())
+    out = text, torch.from_numpy(length)
+    return out if device is None else tuple(t.to(device) for t in out)
+
+
+def read_smiles(strings_or_tensor, max_nodes: int = 4096, engine=None, device=None) -> SmilesRecords:
+    """The result record of every SMILES string in one launch of ``dsp_read_smiles`` (``csrc/ds_reader.hip``; every definition in
+    ``include/diffspectra_reader.h``): an OpenSMILES subset over H, C, N, O, F with aromatic symbols resolved to the first Kekule structure of a
+    stated search, implied hydrogens appended behind the atoms of the string, positions zero.  ``strings_or_tensor``: a list of ``str``
+    (``pack_smiles`` packs it on the host; ``device`` defaults to ``cuda``), a ``Smiles`` result, or a ``(text [P, stride] u8, length [P] i32)``
+    pair of GPU tensors.  NOT RDKit's reader: no sanitisation (``valence_batch`` checks the record), stereo marks, isotopes and classes are read
+    and dropped with a flag.  Device tensors, no synchronisation."""
+    from . import engine as E
+    if isinstance(strings_or_tensor, Smiles):
+        text, length = strings_or_tensor.text, strings_or_tensor.length
+    elif isinstance(strings_or_tensor, (tuple, list)) and len(strings_or_tensor) == 2 and torch.is_tensor(strings_or_tensor[0]):
+        text, length = strings_or_tensor
+    else:
+        text, length = pack_smiles(list(strings_or_tensor), device if device is not None else "cuda")
+    length = torch.as_tensor(length).to(device=text.device, dtype=torch.int32).contiguous()
+    return SmilesRecords(*(engine if engine is not None else E).read_smiles(text, length, max_nodes))
+
+
+def records_from_smiles(strings, max_nodes: int = 4096, engine=None, device=None):
+    """``(records, n_atoms)`` of the strings that read ok, for ``known_records=`` of ``diffspectra_evaluate``, ``novelty`` and
+    ``get_edm_metric_2d(known=...)``: a ``train_smiles`` list becomes a record table in one launch.  The strings that do not read are dropped
+    (``read_smiles`` says why)."""
+    got = read_smiles(strings, max_nodes=max_nodes, engine=engine, device=device)
+    keep = got.ok
+    return got.records[keep].contiguous(), got.n_atoms[keep].contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------------------ substructure queries, MACCS

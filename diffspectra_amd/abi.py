@@ -1,5 +1,5 @@
 """The one description of the C-ABI on the Python side: the headers (``include/diffspectra_hip.h`` for sampling, ``include/diffspectra_train.h``
-for training, ``include/diffspectra_sets.h`` for the set-against-set analytics, ``include/diffspectra_valence.h`` for the valence analytics, ``include/diffspectra_groups.h`` for the functional groups, ``include/diffspectra_scaffold.h`` for the scaffolds, ``include/diffspectra_smiles.h`` for the SMILES strings, ``include/diffspectra_substructure.h`` for the substructure matcher, ``include/diffspectra_stereo.h`` for the stereo-aware identity, ``include/diffspectra_brics.h`` for the BRICS fragments, ``include/diffspectra_mobile.h`` for the mobile-hydrogen normal form, ``include/diffspectra_key.h`` for the key-level identity, ``include/diffspectra_fraggle.h`` for the Fraggle similarity, ``include/diffspectra_rmsd.h`` for the symmetry-corrected RMSD, ``include/diffspectra_reader.h`` for the SMILES reader, ``include/diffspectra_tiles.h`` for the launch-form switches, ``include/diffspectra_step.h`` for the uniform-step entry points) are read here and nowhere else.  ``engine`` and ``train_engine`` build their ctypes types and ``struct`` packers from what this
+for training, ``include/diffspectra_sets.h`` for the set-against-set analytics, ``include/diffspectra_valence.h`` for the valence analytics, ``include/diffspectra_groups.h`` for the functional groups, ``include/diffspectra_scaffold.h`` for the scaffolds, ``include/diffspectra_smiles.h`` for the SMILES strings, ``include/diffspectra_substructure.h`` for the substructure matcher, ``include/diffspectra_stereo.h`` for the stereo-aware identity, ``include/diffspectra_brics.h`` for the BRICS fragments, ``include/diffspectra_mobile.h`` for the mobile-hydrogen normal form, ``include/diffspectra_key.h`` for the key-level identity, ``include/diffspectra_fraggle.h`` for the Fraggle similarity, ``include/diffspectra_rmsd.h`` for the symmetry-corrected RMSD, ``include/diffspectra_reader.h`` for the SMILES reader, ``include/diffspectra_tiles.h`` for the launch-form switches, ``include/diffspectra_step.h`` for the uniform-step entry points, ``include/diffspectra_solver.h`` for the multistep solver update) are read here and nowhere else.  ``engine`` and ``train_engine`` build their ctypes types and ``struct`` packers from what this
 module parsed, so a struct is described once, in its header; the library reports its ``sizeof``s and the loaders compare.  The function
 prototypes are read too: ``Header.bind`` gives every export its ``argtypes``, so a call site passes plain Python numbers and data pointers and
 ctypes refuses a call with too few arguments or with one of the wrong kind."""
@@ -144,3 +144,4 @@ RMSD = Header("diffspectra_rmsd.h")
 READER = Header("diffspectra_reader.h")
 TILES = Header("diffspectra_tiles.h")
 STEP = Header("diffspectra_step.h")
+SOLVER = Header("diffspectra_solver.h")

@@ -40,7 +40,8 @@ def qm9s_config(spectra_version: str = "allspectra", device="cpu", steps: int = 
         loss_weights="1., 0.25, 0.1", noise_align=True,                        # configs/diffspectra_qm9s.py:79-80
     )
     sde = Config(schedule="cosine", continuous_beta_0=0.1, continuous_beta_1=20.0)
-    sampling = Config(method="ancestral", steps=steps, noise_source="philox", seed=42)
+    # method: 'ancestral' (the reference's) or a multistep solver of sampling.SOLVERS; spacing / lower_order_final act on those solvers only
+    sampling = Config(method="ancestral", steps=steps, noise_source="philox", seed=42, spacing="time_uniform", lower_order_final=True)
     evaluate = Config(batch_size=batch_size, num_samples=num_samples, sampling_temperature=1.0, enable_sampling=True,
                       begin_ckpt=40, end_ckpt=40, ckpts="")
     # training side (configs/diffspectra_qm9s.py:85-127): batch 128 per GPU, AdamW-amsgrad lr 2e-4, warm-up 100 000 steps,

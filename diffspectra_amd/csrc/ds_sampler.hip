@@ -1,10 +1,12 @@
 // gfx950 kernels + C-ABI of the sampler side, which needs only a ds_layout: the ancestral update with host or in-kernel
-// (Philox4x32-10 + Box-Muller) noise, the graph-replayable step counter, post-processing and the stability check.
+// (Philox4x32-10 + Box-Muller) noise, the graph-replayable step counter, the multistep solver update (DDIM, DPM-Solver++(2M) ODE / SDE),
+// post-processing and the stability check.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/diffspectra_hip.h"
+#include "../../include/diffspectra_solver.h"
 #include "ds_bonds.h"
 #include "ds_host.h"
 
@@ -12,6 +14,13 @@ namespace {
 
 using dst::clear;
 using dst::layout_ok;
+
+// the float2 operands of k_solver_step; NULL passes (whether a pointer may be NULL is each entry point's check)
+bool edge_aligned8(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (reinterpret_cast<uintptr_t>(p) & 7) return false;
+  return true;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Ancestral update, one workgroup per molecule (sampling.py:604-624; models/utils.py:38-45,67-106).
@@ -173,6 +182,129 @@ __global__ __launch_bounds__(256) void k_step_begin(const float* __restrict__ ta
   for (int b = threadIdx.x; b < B; b += 256) noise_level[b] = nl;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Multistep solver update (include/diffspectra_solver.h): x_mean = ca x + cb pred + cc hist, x = x_mean + (cd noise) temp, in the frame of
+// k_noise_step: one workgroup per molecule, the same Philox counters, CoM projection and pair order.  MODE 0: noise from raw_pos /
+// raw_feat / raw_edge (the host twin, k_sampler_step's draws); MODE 1: in-kernel Philox; MODE 2: as MODE 1 with the row and the draw index
+// read from device memory, and hist := pred once the old hist is read (graph replay).  cc == 0 and cd == 0 are uniform over the grid:
+// the history is then not read, the noise neither generated nor loaded.  The two edge channels move as one float2.  Every sum is a
+// spelled-out fma: left to the compiler, the contraction differed between (i,j) and (j,i) of one pair and symmetric input gave edges that
+// differed in the last bit.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_solver_step(ds_layout L, float ca, float cb, float cc, float cd, float temp,
+                                                     unsigned long long seed, unsigned int draw, const int64_t* __restrict__ mol_id,
+                                                     float* __restrict__ x, float* __restrict__ edge_x, const float* __restrict__ pred,
+                                                     const float* __restrict__ edge_pred, float* __restrict__ hist,
+                                                     float* __restrict__ edge_hist, const float* __restrict__ raw_pos,
+                                                     const float* __restrict__ raw_feat, const float* __restrict__ raw_edge,
+                                                     float* __restrict__ x_mean, float* __restrict__ edge_mean,
+                                                     const float* __restrict__ table, const int32_t* __restrict__ step) {
+  __shared__ __attribute__((aligned(16))) float nz[32][12];
+  __shared__ float mean[3];
+  __shared__ int dn[32];
+  const int m = blockIdx.x, tid = threadIdx.x;
+  const int n0 = L.node_off[m], n = L.node_off[m + 1] - n0;
+  if (n <= 0) return;
+  if (MODE == 2) {
+    const int i = *step;
+    const float* row = table + (size_t)DS_SOLVER_ROW * i;
+    ca = row[0]; cb = row[1]; cc = row[2]; cd = row[3];
+    draw = (unsigned int)i + 1u;
+  }
+  const bool use_hist = cc != 0.0f, use_noise = cd != 0.0f;
+  if (tid < n) dn[tid] = L.node_dense[n0 + tid];
+  unsigned long long mol = 0;
+  if (use_noise) {
+    if (MODE == 0) {
+      __syncthreads();
+      for (int idx = tid; idx < n * 9; idx += 256) {
+        const int a = idx / 9, ch = idx - a * 9;
+        const size_t g = (size_t)dn[a];
+        nz[a][ch] = ch < 3 ? raw_pos[g * 3 + ch] : raw_feat[g * 6 + (ch - 3)];
+      }
+    } else {
+      mol = (unsigned long long)mol_id[m];
+      if (tid < n * 3) {
+        const int a = tid / 3, j = tid - a * 3;
+        const float4 v = philox_normal4((unsigned int)tid, draw, mol, 0u, seed);
+        reinterpret_cast<float4*>(&nz[a][4 * j])[0] = v;
+      }
+    }
+    __syncthreads();
+    if (tid < 3) {   // CoM projection of the position noise, atoms in ascending order (as k_sampler_step / k_noise_step)
+      float s = 0.0f;
+      for (int a = 0; a < n; ++a) s += nz[a][tid];
+      mean[tid] = s / (float)n;
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < n * 9; idx += 256) {
+    const int a = idx / 9, ch = idx - a * 9;
+    const size_t e = (size_t)dn[a] * 9 + ch;
+    const float p = pred[e];
+    float xm = __fmaf_rn(ca, x[e], cb * p);
+    if (use_hist) xm = __fmaf_rn(cc, hist[e], xm);
+    if (MODE == 2) hist[e] = p;
+    x_mean[e] = xm;
+    float xn = xm;
+    if (use_noise) {
+      const float v = ch < 3 ? nz[a][ch] - mean[ch] : nz[a][ch];
+      xn = __fmaf_rn(cd * v, temp, xm);
+    }
+    x[e] = xn;
+  }
+  const int N = L.N, P = n * (n - 1) / 2;
+  float2* __restrict__ ex2 = reinterpret_cast<float2*>(edge_x);
+  float2* __restrict__ em2 = reinterpret_cast<float2*>(edge_mean);
+  float2* __restrict__ eh2 = reinterpret_cast<float2*>(edge_hist);
+  const float2* __restrict__ ep2 = reinterpret_cast<const float2*>(edge_pred);
+  for (int p = tid; p < P; p += 256) {   // unordered pair lo < hi: p = hi(hi-1)/2 + lo, as k_noise_step
+    int hi = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
+    while (hi * (hi - 1) / 2 > p) --hi;
+    while ((hi + 1) * hi / 2 <= p) ++hi;
+    const int lo = p - hi * (hi - 1) / 2;
+    const int la = dn[lo] - m * N, lb = dn[hi] - m * N;
+    float2 nv = make_float2(0.0f, 0.0f);
+    if (use_noise) {
+      if (MODE == 0) {   // tril(-1) + transpose of raw_edge [B,2,N,N]
+        const int r = la > lb ? la : lb, q = la > lb ? lb : la;
+        nv.x = raw_edge[(((size_t)m * 2 + 0) * N + r) * N + q];
+        nv.y = raw_edge[(((size_t)m * 2 + 1) * N + r) * N + q];
+      } else {
+        const float4 v = philox_normal4((unsigned int)p, draw, mol, 1u, seed);
+        nv.x = v.x; nv.y = v.y;
+      }
+    }
+    const size_t o[2] = {(size_t)dn[lo] * N + lb, (size_t)dn[hi] * N + la};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float2 xv = ex2[o[s]], pv = ep2[o[s]];
+      float2 em = make_float2(__fmaf_rn(ca, xv.x, cb * pv.x), __fmaf_rn(ca, xv.y, cb * pv.y));
+      if (use_hist) {
+        const float2 hv = eh2[o[s]];
+        em.x = __fmaf_rn(cc, hv.x, em.x); em.y = __fmaf_rn(cc, hv.y, em.y);
+      }
+      if (MODE == 2) eh2[o[s]] = pv;
+      em2[o[s]] = em;
+      ex2[o[s]] = use_noise ? make_float2(__fmaf_rn(cd * nv.x, temp, em.x), __fmaf_rn(cd * nv.y, temp, em.y)) : em;
+    }
+  }
+}
+
+// k_step_begin for the solver's 32-byte rows: ++*step, noise_level[b] = table[*step][4] (one workgroup).
+__global__ __launch_bounds__(256) void k_solver_step_begin(const float* __restrict__ table, int n_steps, int32_t* __restrict__ step, int B,
+                                                           float* __restrict__ noise_level) {
+  __shared__ int cur;
+  if (threadIdx.x == 0) {
+    const int i = min(*step + 1, n_steps - 1);
+    *step = i;
+    cur = i;
+  }
+  __syncthreads();
+  const float nl = table[(size_t)DS_SOLVER_ROW * cur + 4];
+  for (int b = threadIdx.x; b < B; b += 256) noise_level[b] = nl;
+}
+
 // post_process (sampling.py:53-97) with the inverse scaler of utils.py:88-103 (norms 1,4,4,1; centered).
 __global__ void k_post_process(ds_layout L, const float* __restrict__ xh, const float* __restrict__ edge_x,
                                float* __restrict__ pos_out, int32_t* __restrict__ atom_type, int32_t* __restrict__ fc,
@@ -288,6 +420,51 @@ int ds_sampler_step_philox_dev(const ds_layout* L, const float* table, const int
   if (!layout_ok(L) || !table || !step || !mol_id || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean) return DS_ERR_ARG;
   hipLaunchKernelGGL(k_noise_step<2>, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, 0.0f, 0.0f, 0.0f, temperature,
                      (unsigned long long)seed, 0u, mol_id, x, edge_x, pred, edge_pred, x_mean, edge_mean, table, step);
+  return DST_CHECK_LAUNCH();
+}
+
+// ---- multistep solver update (include/diffspectra_solver.h) ----
+int ds_solver_step(const ds_layout* L, float a, float b, float c, float d, float temperature, float* x, float* edge_x, const float* pred,
+                   const float* edge_pred, const float* hist, const float* edge_hist, const float* raw_pos, const float* raw_feat,
+                   const float* raw_edge, float* x_mean, float* edge_mean, void* stream) {
+  if (!layout_ok(L) || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean) return DS_ERR_ARG;
+  if (c != 0.0f && (!hist || !edge_hist)) return DS_ERR_ARG;
+  if (d != 0.0f && (!raw_pos || !raw_feat || !raw_edge)) return DS_ERR_ARG;
+  if (!edge_aligned8({edge_x, edge_pred, edge_hist, edge_mean})) return DS_ERR_ARG;
+  hipLaunchKernelGGL(k_solver_step<0>, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, a, b, c, d, temperature, 0ull, 0u,
+                     (const int64_t*)nullptr, x, edge_x, pred, edge_pred, const_cast<float*>(hist), const_cast<float*>(edge_hist), raw_pos,
+                     raw_feat, raw_edge, x_mean, edge_mean, (const float*)nullptr, (const int32_t*)nullptr);
+  return DST_CHECK_LAUNCH();
+}
+
+int ds_solver_step_philox(const ds_layout* L, float a, float b, float c, float d, float temperature, uint64_t seed, int32_t step,
+                          const int64_t* mol_id, float* x, float* edge_x, const float* pred, const float* edge_pred, const float* hist,
+                          const float* edge_hist, float* x_mean, float* edge_mean, void* stream) {
+  if (!layout_ok(L) || !mol_id || !x || !edge_x || !pred || !edge_pred || !x_mean || !edge_mean || step < 0) return DS_ERR_ARG;
+  if (c != 0.0f && (!hist || !edge_hist)) return DS_ERR_ARG;
+  if (!edge_aligned8({edge_x, edge_pred, edge_hist, edge_mean})) return DS_ERR_ARG;
+  hipLaunchKernelGGL(k_solver_step<1>, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, a, b, c, d, temperature,
+                     (unsigned long long)seed, (unsigned int)step + 1u, mol_id, x, edge_x, pred, edge_pred, const_cast<float*>(hist),
+                     const_cast<float*>(edge_hist), (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, x_mean, edge_mean,
+                     (const float*)nullptr, (const int32_t*)nullptr);
+  return DST_CHECK_LAUNCH();
+}
+
+int ds_solver_step_begin(const float* table, int32_t n_steps, int32_t* step, int32_t B, float* noise_level, void* stream) {
+  if (!table || !step || !noise_level || B <= 0 || n_steps <= 0) return DS_ERR_ARG;
+  hipLaunchKernelGGL(k_solver_step_begin, dim3(1), dim3(256), 0, (hipStream_t)stream, table, n_steps, step, B, noise_level);
+  return DST_CHECK_LAUNCH();
+}
+
+int ds_solver_step_philox_dev(const ds_layout* L, const float* table, const int32_t* step, float temperature, uint64_t seed,
+                              const int64_t* mol_id, float* x, float* edge_x, const float* pred, const float* edge_pred, float* hist,
+                              float* edge_hist, float* x_mean, float* edge_mean, void* stream) {
+  if (!layout_ok(L) || !table || !step || !mol_id || !x || !edge_x || !pred || !edge_pred || !hist || !edge_hist || !x_mean || !edge_mean)
+    return DS_ERR_ARG;
+  if (!edge_aligned8({edge_x, edge_pred, edge_hist, edge_mean})) return DS_ERR_ARG;
+  hipLaunchKernelGGL(k_solver_step<2>, dim3(L->B), dim3(256), 0, (hipStream_t)stream, *L, 0.0f, 0.0f, 0.0f, 0.0f, temperature,
+                     (unsigned long long)seed, 0u, mol_id, x, edge_x, pred, edge_pred, hist, edge_hist, (const float*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr, x_mean, edge_mean, table, step);
   return DST_CHECK_LAUNCH();
 }
 

@@ -69,6 +69,7 @@ def load_library() -> C.CDLL:
     abi.READER.bind(lib)
     abi.TILES.bind(lib)
     abi.STEP.bind(lib)
+    abi.SOLVER.bind(lib)
     sizes = (C.c_int64 * 4)()
     lib.ds_struct_sizes(sizes)
     mine = [C.sizeof(t) for t in (DsWeights, DsLayout, DsWorkspace, DsGemmArgs)]
@@ -1360,6 +1361,29 @@ class DmtEngine:
         st = self.lib.ds_sampler_step_philox_dev(C.byref(L.c), ptr(table), ptr(step_dev), temperature, seed, ptr(mol_id), ptr(x),
                                                  ptr(edge_x), ptr(pred), ptr(edge_pred), ptr(x_mean), ptr(edge_mean), _stream())
         _check(st, "ds_sampler_step_philox_dev")
+
+    # multistep solver update (include/diffspectra_solver.h): row (a, b, c, d); hist / edge_hist may be None when c == 0, raw_* when d == 0
+    def solver_step(self, L, a, b, c, d, temperature, x, edge_x, pred, edge_pred, hist, edge_hist, raw_pos, raw_feat, raw_edge,
+                    x_mean, edge_mean):
+        st = self.lib.ds_solver_step(C.byref(L.c), a, b, c, d, temperature, ptr(x), ptr(edge_x), ptr(pred), ptr(edge_pred), ptr(hist),
+                                     ptr(edge_hist), ptr(raw_pos), ptr(raw_feat), ptr(raw_edge), ptr(x_mean), ptr(edge_mean), _stream())
+        _check(st, "ds_solver_step")
+
+    def solver_step_philox(self, L, a, b, c, d, temperature, seed: int, step: int, mol_id, x, edge_x, pred, edge_pred, hist, edge_hist,
+                           x_mean, edge_mean):
+        st = self.lib.ds_solver_step_philox(C.byref(L.c), a, b, c, d, temperature, seed, step, ptr(mol_id), ptr(x), ptr(edge_x), ptr(pred),
+                                            ptr(edge_pred), ptr(hist), ptr(edge_hist), ptr(x_mean), ptr(edge_mean), _stream())
+        _check(st, "ds_solver_step_philox")
+
+    def solver_step_begin(self, table, n_steps: int, step_dev, B: int, noise_level):
+        _check(self.lib.ds_solver_step_begin(ptr(table), n_steps, ptr(step_dev), B, ptr(noise_level), _stream()),
+               "ds_solver_step_begin")
+
+    def solver_step_philox_dev(self, L, table, step_dev, temperature, seed: int, mol_id, x, edge_x, pred, edge_pred, hist, edge_hist,
+                               x_mean, edge_mean):
+        st = self.lib.ds_solver_step_philox_dev(C.byref(L.c), ptr(table), ptr(step_dev), temperature, seed, ptr(mol_id), ptr(x), ptr(edge_x),
+                                                ptr(pred), ptr(edge_pred), ptr(hist), ptr(edge_hist), ptr(x_mean), ptr(edge_mean), _stream())
+        _check(st, "ds_solver_step_philox_dev")
 
     def check_stability(self, L, pos, atom_type, want_orders: bool = True):
         """``ds_check_stability`` on the tensors ``post_process`` left on the GPU: (mol_stable [B] bool, nr_stable [B],

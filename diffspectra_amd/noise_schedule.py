@@ -46,6 +46,18 @@ class NoiseScheduleVP:
         lm = self.marginal_log_mean_coeff(t)
         return lm - 0.5 * torch.log(1.0 - torch.exp(2.0 * lm))
 
+    def inverse_lambda(self, lamb):
+        """The time t with ``marginal_lambda(t) == lamb`` (``diffusion/noise_schedule.py`` has it for the DPM-Solver time grids; the
+        ``'logSNR'`` spacing of the multistep samplers needs it).  alpha^2 + sigma^2 = 1 gives log alpha = -1/2 log(1 + e^{-2 lambda});
+        the cosine schedule then inverts its cosine, the linear one solves its quadratic for the positive root, written without the
+        cancellation of -b + sqrt(b^2 + ...).  Works in the dtype of ``lamb``."""
+        neg2_log_alpha = torch.logaddexp(-2.0 * lamb, torch.zeros_like(lamb))
+        if self.schedule == "linear":
+            db = self.beta_1 - self.beta_0
+            return 2.0 * neg2_log_alpha / (torch.sqrt(self.beta_0 ** 2 + 2.0 * db * neg2_log_alpha) + self.beta_0)
+        log_alpha = -0.5 * neg2_log_alpha
+        return torch.arccos(torch.exp(log_alpha + self.cosine_log_alpha_0)) * 2.0 * (1.0 + self.cosine_s) / math.pi - self.cosine_s
+
     def get_noiseLevel(self, t):
         alpha_t, sigma_t = self.marginal_alpha(t), self.marginal_std(t)
         return torch.log(alpha_t ** 2 / sigma_t ** 2)

@@ -8,6 +8,10 @@ self_cond, cond_process_fn, sampling_temperature).sampling(model, z_T, node_mask
 What differs is how it runs: the loop-invariant spectra embedding is computed once (the reference re-encodes it
 every step, dmt.py:348-350), each step is one ``ds_forward`` + one fused ``ds_sampler_step``, the per-step
 scalars come from a table computed up front, and molecules leave the GPU in one copy.
+
+Beyond the reference: ``MultistepSampler`` (``config.sampling.method`` in ``SOLVERS``) runs DDIM and DPM-Solver++(2M), ODE and SDE form, on
+the same frame with one fused ``ds_solver_step`` per step (``solver_table``, ``time_grid``); the ancestral update is its first-order SDE
+row.  Closed forms pin it (tests/test_solver_cpu.py, tests/test_solver_gpu.py); parity with other implementations is not pinned.
 """
 from __future__ import annotations
 
@@ -106,7 +110,7 @@ class AncestralSampler:
         st.ctx = eng.context_embedding(context)                      # hoisted: loop-invariant
         tab = self.coefficient_table()
         st.coef = tab.tolist()
-        st.nl_rows = tab[:, 3].to(dev).reshape(-1, 1).expand(-1, B).contiguous()   # [S, B]: row i = noise level of step i
+        st.nl_rows = tab[:, -1].to(dev).reshape(-1, 1).expand(-1, B).contiguous()  # [S, B]: row i = noise level of step i
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         st.pred, st.edge_pred = [f(B, N, 9), f(B, N, 9)], [f(B, N, N, 2), f(B, N, N, 2)]
         st.x_mean, st.edge_mean = torch.zeros(B, N, 9, device=dev), torch.zeros(B, N, N, 2, device=dev)
@@ -134,13 +138,18 @@ class AncestralSampler:
         eng.sampler_step_philox_dev(L, g["table"], g["step"], float(self.sampling_temperature), st.seed, st.mol_ids, st.x,
                                     st.edge_x, g["pred"], g["edge_pred"], st.x_mean, st.edge_mean)
 
+    def _graph_open(self, st):
+        """The device-side state of graph replay, made when a pass (at st.i >= 1, after eager steps) turns to it."""
+        dev = st.eng.device
+        tab = self.coefficient_table().to(dev).contiguous()
+        return dict(table=tab, step=torch.zeros(1, dtype=torch.int32, device=dev), nl=torch.empty(st.L.B, device=dev),
+                    pred=st.cond_x, edge_pred=st.cond_edge_x, graph=None)
+
     def _graph_advance(self, st, end):
         """Iterations st.i .. end-1 by graph replay (st.i >= 1: the first iteration takes the no-conditioning branch)."""
         eng, dev = st.eng, st.eng.device
         if st.graph is None:
-            tab = self.coefficient_table().to(dev).contiguous()
-            g = dict(table=tab, step=torch.zeros(1, dtype=torch.int32, device=dev), nl=torch.empty(st.L.B, device=dev),
-                     pred=st.cond_x, edge_pred=st.cond_edge_x, graph=None)
+            g = self._graph_open(st)
             st.graph = g
             g["step"].fill_(st.i - 1)
             side = torch.cuda.Stream(device=dev)
@@ -166,13 +175,27 @@ class AncestralSampler:
             g["graph"].replay()
         st.i = end
 
+    def _step_has_noise(self, st, i):
+        """Whether step i consumes noise draws (the reference's loop draws at every step, also where sigma is 0)."""
+        return True
+
+    def _step_update(self, st, i, raw):
+        """The update kernel of eager step i on this step's prediction; ``raw``: the three host draws, None = in-kernel Philox."""
+        c_x, c_pred, sigma, _ = st.coef[i]
+        cur, temp = i & 1, float(self.sampling_temperature)
+        if raw is None:
+            st.eng.sampler_step_philox(st.L, c_x, c_pred, sigma, temp, st.seed, i, st.mol_ids, st.x, st.edge_x, st.pred[cur],
+                                       st.edge_pred[cur], st.x_mean, st.edge_mean)
+        else:
+            st.eng.sampler_step(st.L, c_x, c_pred, sigma, temp, st.x, st.edge_x, st.pred[cur], st.edge_pred[cur], raw[0], raw[1],
+                                raw[2], st.x_mean, st.edge_mean)
+
     @torch.no_grad()
     def advance(self, st, n_steps=None):
         """Run the next ``n_steps`` denoise steps of the pass (all remaining ones by default); True when it is complete."""
         eng, L, ws = st.eng, st.L, st.ws
         dev = eng.device
         B, N = L.B, L.N
-        temp = float(self.sampling_temperature)
         end = len(st.coef) if n_steps is None else min(len(st.coef), st.i + int(n_steps))
         if st.i >= 1 and st.i < end and self._graph_wanted(st):
             self._graph_advance(st, end)
@@ -181,24 +204,20 @@ class AncestralSampler:
         if st.i == 0 and end > 1 and self._graph_wanted(st):
             stop_eager = 1                                         # first iteration eagerly, the rest by graph replay
         for i in range(st.i, stop_eager):
-            c_x, c_pred, sigma, _ = st.coef[i]
             cur = i & 1
             eng.forward(L, ws, st.x, st.edge_x, st.nl_rows[i], st.cond_x, st.cond_edge_x, st.ctx, st.pred[cur], st.edge_pred[cur],
                         uniform_noise_level=True)                  # nl_rows[i] is one scalar expanded over the batch
             st.cond_x, st.cond_edge_x = st.pred[cur], st.edge_pred[cur]
             if self.cond_process_fn is not None:                   # sampling.py:590 ('ori' identity, 'clamp' in place)
                 st.cond_x, st.cond_edge_x = self.cond_process_fn(st.cond_x, st.cond_edge_x)
-            if st.mol_ids is not None and self.noise_fn is None:   # per-molecule Philox streams, generated in the kernel
-                eng.sampler_step_philox(L, c_x, c_pred, sigma, temp, st.seed, i, st.mol_ids, st.x, st.edge_x, st.pred[cur],
-                                        st.edge_pred[cur], st.x_mean, st.edge_mean)
-            else:
+            raw = None                                             # per-molecule Philox streams, generated in the kernel
+            if self._step_has_noise(st, i) and (st.mol_ids is None or self.noise_fn is not None):
                 if self.noise_fn is not None:
                     raw = [r.to(dev, torch.float32).contiguous() for r in self.noise_fn(i)]
                 else:                                              # reference draw order/shapes (models/utils.py:69,78,102)
                     raw = [torch.randn((B, N, 3), device=dev), torch.randn((B, N, 6), device=dev),
                            torch.randn((B, 2, N, N), device=dev)]
-                eng.sampler_step(L, c_x, c_pred, sigma, temp, st.x, st.edge_x, st.pred[cur], st.edge_pred[cur], raw[0], raw[1],
-                                 raw[2], st.x_mean, st.edge_mean)
+            self._step_update(st, i, raw)
             if self.progress_fn is not None and (i + 1) % 100 == 0:
                 self.progress_fn(i + 1, len(st.coef))
         st.i = stop_eager
@@ -217,6 +236,120 @@ class _Pass:
     """Mutable state of one in-flight sampling pass (``AncestralSampler.begin`` / ``advance``)."""
     __slots__ = ("eng", "L", "ws", "i", "x", "edge_x", "ctx", "coef", "nl_rows", "pred", "edge_pred", "x_mean", "edge_mean",
                  "cond_x", "cond_edge_x", "mol_ids", "seed", "graph")
+
+
+SOLVERS = ("ddim", "dpmpp_2m", "sde_dpmpp_2m")
+SPACINGS = ("time_uniform", "logSNR")
+SOLVER_ROW = 8      # floats per row of the device table (DS_SOLVER_ROW of include/diffspectra_solver.h)
+
+
+def time_grid(noise_scheduler, eps, steps, spacing="time_uniform", device=None):
+    """The sampling times t_0 = T > ... > t_{S-1} = eps.  ``'time_uniform'``: ``torch.linspace(T, eps, S)``, the reference's grid
+    (sampling.py:370).  ``'logSNR'``: lambda = log(alpha/sigma) uniform between lambda(T) and lambda(eps), computed in fp64, with the end
+    points exactly T and eps."""
+    if spacing == "time_uniform":
+        return torch.linspace(noise_scheduler.T, eps, steps, device=device)
+    if spacing != "logSNR":
+        raise ValueError(f"config.sampling.spacing must be one of {SPACINGS}")
+    ends = torch.tensor([noise_scheduler.T, eps], dtype=torch.float64)
+    lam = noise_scheduler.marginal_lambda(ends)
+    t = noise_scheduler.inverse_lambda(torch.linspace(float(lam[0]), float(lam[1]), steps, dtype=torch.float64))
+    t[0] = noise_scheduler.T                  # (linspace of one step is its start, as for the reference's grid)
+    if steps > 1:
+        t[-1] = eps
+    return t if device is None else t.to(device)
+
+
+def solver_table(noise_scheduler, t_array, solver, lower_order_final=True, max_order=2):
+    """fp64 rows (a, b, c, d, noise_level) of a multistep solver on the grid ``t_array``: step i evaluates the model at noise level
+    2 lambda_i, giving p_i, and sets x_mean = a x + b p_i + c p_{i-1}, x_{i+1} = x_mean + (d eps) temperature.
+
+    With alpha_i, sigma_i = marginal_prob(t_i), lambda_i = log(alpha_i / sigma_i), h_i = lambda_{i+1} - lambda_i, r_i = h_{i-1} / h_i,
+    E1 = -expm1(-h_i), E2 = -expm1(-2 h_i) (DPM-Solver++ for the data-prediction model, Lu et al. 2022, eq. of Algorithm 2 and its SDE
+    form):
+        ddim          a = sigma_{i+1}/sigma_i            k = alpha_{i+1} E1   b = k                c = 0         d = 0
+        dpmpp_2m      a = sigma_{i+1}/sigma_i            k = alpha_{i+1} E1   b = k (1 + 1/(2r))   c = -k/(2r)   d = 0
+        sde_dpmpp_2m  a = sigma_{i+1}/sigma_i e^{-h_i}   k = alpha_{i+1} E2   b = k (1 + 1/(2r))   c = -k/(2r)   d = sigma_{i+1} sqrt(E2)
+    A second-order row is first order (b = k, c = 0) at i = 0, where there is no history, at i = S-2 if ``lower_order_final`` (on a
+    time-uniform grid the last h is large, r small, and the extrapolation blows up), and everywhere with ``max_order=1`` - the first-order
+    sde row IS the ancestral update of sampling.py:576-580,604-606.  Row S-1 is (0, 1, 0, 0): the step to t = 0 returns the prediction,
+    as the reference's last ancestral step does; its h is infinite and is never formed."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}")
+    t = torch.as_tensor(t_array).detach().to("cpu", torch.float64)
+    S = t.numel()
+    alpha, sigma = noise_scheduler.marginal_prob(t)
+    lam = torch.log(alpha / sigma)
+    h = lam[1:] - lam[:-1]                                  # h_0 .. h_{S-2}
+    rows = torch.zeros(S, 5, dtype=torch.float64)
+    rows[:, 4] = 2.0 * lam
+    for i in range(S - 1):
+        sde = solver == "sde_dpmpp_2m"
+        a = sigma[i + 1] / sigma[i] * (torch.exp(-h[i]) if sde else 1.0)
+        E = -torch.expm1(-2.0 * h[i]) if sde else -torch.expm1(-h[i])
+        k = alpha[i + 1] * E
+        second = solver != "ddim" and max_order >= 2 and i >= 1 and not (lower_order_final and i == S - 2)
+        g = 0.5 * h[i] / h[i - 1] if second else 0.0       # 1 / (2 r_i)
+        rows[i, 0], rows[i, 1], rows[i, 2] = a, k * (1.0 + g), -k * g
+        rows[i, 3] = sigma[i + 1] * torch.sqrt(E) if sde else 0.0
+    rows[S - 1, :4] = torch.tensor([0.0, 1.0, 0.0, 0.0], dtype=torch.float64)
+    return rows
+
+
+class MultistepSampler(AncestralSampler):
+    """DDIM and DPM-Solver++(2M), ODE and SDE form, on the ancestral sampler's frame: the same per-molecule Philox streams, CoM projection,
+    symmetric pair noise, ``begin`` / ``advance`` / ``sampling``, ``noise_fn`` / ``progress_fn`` / ``use_graph``.  One step is one row of
+    ``solver_table`` applied by ``ds_solver_step*`` to x, this step's prediction and the previous step's (with 'clamp' self-conditioning:
+    the clamped one, the tensor the previous update used).  Eagerly the ping-pong ``st.pred[i & 1]`` holds that previous prediction; under
+    graph replay the prediction is written in place, so the kernel keeps the history in a buffer of its own, which the switch from eager
+    steps fills."""
+
+    def __init__(self, noise_scheduler, time_steps, model_pred_data, pred_edge=False, self_cond=False, cond_process_fn=None,
+                 sampling_temperature=1.0, solver="dpmpp_2m", lower_order_final=True):
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}")
+        super().__init__(noise_scheduler, time_steps, model_pred_data, pred_edge, self_cond, cond_process_fn, sampling_temperature)
+        self.solver, self.lower_order_final = solver, bool(lower_order_final)
+
+    def coefficient_table(self):
+        """Per-step (a, b, c, d, noise_level): ``solver_table`` in fp64, cast to fp32 once."""
+        if self._table is None:
+            self._table = solver_table(self.noise_scheduler, self.t_array, self.solver, self.lower_order_final).to(torch.float32)
+        return self._table
+
+    def _step_has_noise(self, st, i):
+        return st.coef[i][3] != 0.0
+
+    def _step_update(self, st, i, raw):
+        a, b, c, d, _ = st.coef[i]
+        cur, temp = i & 1, float(self.sampling_temperature)
+        hist, edge_hist = (st.pred[cur ^ 1], st.edge_pred[cur ^ 1]) if c != 0.0 else (None, None)
+        if d == 0.0 or raw is not None:                        # deterministic row (no noise operand at all), or host draws
+            raw = raw if d != 0.0 else (None, None, None)
+            st.eng.solver_step(st.L, a, b, c, d, temp, st.x, st.edge_x, st.pred[cur], st.edge_pred[cur], hist, edge_hist, raw[0], raw[1],
+                               raw[2], st.x_mean, st.edge_mean)
+        else:
+            st.eng.solver_step_philox(st.L, a, b, c, d, temp, st.seed, i, st.mol_ids, st.x, st.edge_x, st.pred[cur], st.edge_pred[cur],
+                                      hist, edge_hist, st.x_mean, st.edge_mean)
+
+    def _graph_open(self, st):
+        g = super()._graph_open(st)
+        tab = torch.zeros(len(st.coef), SOLVER_ROW)
+        tab[:, :5] = self.coefficient_table()
+        g["table"] = tab.to(st.eng.device)
+        prev, spare = (st.i - 1) & 1, st.i & 1                 # hand-over: p_{i-1} moves into the ping-pong buffer replay leaves unused
+        g["hist"], g["edge_hist"] = st.pred[spare], st.edge_pred[spare]
+        g["hist"].copy_(st.pred[prev])
+        g["edge_hist"].copy_(st.edge_pred[prev])
+        return g
+
+    def _graph_body(self, st):
+        eng, L, ws, g = st.eng, st.L, st.ws, st.graph
+        eng.solver_step_begin(g["table"], len(st.coef), g["step"], L.B, g["nl"])
+        eng.forward(L, ws, st.x, st.edge_x, g["nl"], g["pred"], g["edge_pred"], st.ctx, g["pred"], g["edge_pred"],
+                    uniform_noise_level=True)
+        eng.solver_step_philox_dev(L, g["table"], g["step"], float(self.sampling_temperature), st.seed, st.mol_ids, st.x, st.edge_x,
+                                   g["pred"], g["edge_pred"], g["hist"], g["edge_hist"], st.x_mean, st.edge_mean)
 
 
 def post_process(xh, atom_types, include_charge, node_mask, inverse_scaler, edge_x=None, edge_mask=None,
@@ -302,13 +435,19 @@ class MoleculeList(Sequence):
 
 
 def _make_sampler(config, noise_scheduler, eps, temperature):
-    if config.sampling.method != "ancestral":
+    method = config.sampling.method
+    if method != "ancestral" and method not in SOLVERS:
         raise ValueError("Invalid sampling method!")
     if config.only_2D:
         raise ValueError("only_2D sampling is outside the MI355X hot path (every shipped config has only_2D=False)")
-    time_steps = torch.linspace(noise_scheduler.T, eps, config.sampling.steps, device=config.device)
-    return AncestralSampler(noise_scheduler, time_steps, config.model.pred_data, config.pred_edge, config.model.self_cond,
-                            get_self_cond_fn(config), sampling_temperature=temperature)
+    if method == "ancestral":                                  # the reference's sampler on the reference's grid, whatever spacing says
+        time_steps = torch.linspace(noise_scheduler.T, eps, config.sampling.steps, device=config.device)
+        return AncestralSampler(noise_scheduler, time_steps, config.model.pred_data, config.pred_edge, config.model.self_cond,
+                                get_self_cond_fn(config), sampling_temperature=temperature)
+    time_steps = time_grid(noise_scheduler, eps, config.sampling.steps, getattr(config.sampling, "spacing", "time_uniform"), config.device)
+    return MultistepSampler(noise_scheduler, time_steps, config.model.pred_data, config.pred_edge, config.model.self_cond,
+                            get_self_cond_fn(config), sampling_temperature=temperature, solver=method,
+                            lower_order_final=getattr(config.sampling, "lower_order_final", True))
 
 
 def _assemble(ds, ids, version):
